@@ -15,10 +15,14 @@ interpreters, nothing is exec'ed over a process that touched the GPU) -- and rel
 A step = reset the synchroniser + one full pass of the stream through the HIP path (walker, stitch/plan, seek
 verification, payload MF, payload PLL, packet decode), decoded payloads copied back to the host, payload symbols left in HBM.
 The IQ is resident in HBM before the timed region starts.  Steps are issued through the library's submit/collect
-pipeline (--depth blocks in flight) and the timed region runs from an idle GPU to an idle GPU.  So that the fill and
-drain of that pipeline do not decide the number, the K-step schedule is repeated R times back to back inside ONE timed
-region, R chosen from the warm-up rate so that the region lasts at least --min-time seconds (default 1 s):
-ms_per_step = dt / (K R).  `steps`, `repeats` and `passes_timed` are reported.
+pipeline (--depth blocks in flight, no stage events) and the timed region runs from an idle GPU to an idle GPU: it holds
+exactly --steps steps, ms_per_step = dt / steps.  The decoded frames of the last timed step are checked against the
+injected payloads before a number is printed; --dump-outputs DIR writes them as DIR/<field>.npy (see dump_outputs).
+
+A plain run does only that.  Everything else moves behind --full: the same schedule repeated R times inside one region
+that lasts at least --min-time seconds (with the PLL's stage events, for the roofline line), per-kernel times, the
+secondary figures (constellation to the host, one continuing stream, IQ from host memory, the drop-in ABI) and the CPU
+baseline.
 
 Prints ONE JSON line on rank 0.
 """
@@ -202,7 +206,48 @@ def parse_args(argv=None):
                          "config 5: 1024 streams sharded over --gpus ranks)")
     ap.add_argument("--continuous", action="store_true",
                     help="feed the passes as consecutive blocks of ONE continuing stream (no reset in between): not the headline number")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: min-time region with the roofline line, per-kernel times, "
+                         "secondary figures, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames decoded in the last timed step as DIR/<field>.npy (float32 / float64)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_INT = ("stream", "start", "cfo_bin", "pfb_index", "header_valid", "payload_valid", "mod_scheme", "mod_bps", "check", "fec0", "fec1",
+            "num_framesyms")
+DUMP_FLT = ("rxy", "tau", "gamma", "dphi", "phi", "pilot_dphi", "pilot_phi", "pilot_gain", "evm_db", "rssi_db", "cfo", "evm_sum")
+
+
+def dump_outputs(d, frames):
+    """The frames a caller of the timed path receives (RxContext.results), one array per field: integer fields as float64
+    (exact), float fields as float32, header and payload bytes as float32 rows (payload rows padded with -1 to the longest,
+    payload_len beside them).  frame_index lists which frames are written: all of them, or -- should that exceed
+    DUMP_MAX_BYTES -- a fixed seeded sample, in order."""
+    os.makedirs(d, exist_ok=True)
+    n = len(frames)
+    width = max([len(f["payload"]) for f in frames] + [0])
+    per_frame = 8 * (len(DUMP_INT) + 2) + 4 * (len(DUMP_FLT) + 20 + width)
+    keep = np.arange(n)
+    if n * per_frame > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(20240901).choice(n, DUMP_MAX_BYTES // per_frame, replace=False))
+    sel = [frames[i] for i in keep]
+    out = {"frame_index": keep.astype(np.float64),
+           "payload_len": np.array([len(f["payload"]) for f in sel], np.float64)}
+    out.update({k: np.array([f[k] for f in sel], np.float64) for k in DUMP_INT})
+    out.update({k: np.array([f[k] for f in sel], np.float32) for k in DUMP_FLT})
+    out["header"] = np.array([np.frombuffer(f["header"], np.uint8) for f in sel], np.float32).reshape(len(sel), -1)
+    pay = np.full((len(sel), width), -1.0, np.float32)
+    for i, f in enumerate(sel):
+        pay[i, :len(f["payload"])] = np.frombuffer(f["payload"], np.uint8)
+    out["payload"] = pay
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    return sorted(out)
 
 
 class StubPath:
@@ -259,8 +304,7 @@ def main(argv=None):
 
     if stub:
         path = StubPath(rank)
-        run_steps = path.run_steps
-        kt = kt_live = None
+        run_head = run_live = path.run_steps
     else:
         fx = importlib.import_module("gr-liquiddsp_amd")
         x, injected = fx.synth_stream(a.samples, stream_id=sid)
@@ -274,27 +318,28 @@ def main(argv=None):
             ok = sum(1 for g, (_, pl) in zip(frames, injected) if g["payload_valid"] and g["payload"] == pl)
             if ok != len(injected):
                 raise SystemExit("bench: decoded %d of %d injected frames -- refusing to report a throughput" % (ok, len(injected)))
-            return ok
+            return frames
 
-        # per-kernel device times (HIP events on the library's own streams), taken un-pipelined so that they are
-        # pure kernel durations: these feed `kernels_ms_one_block_in_flight`
-        kt = dict(walk_ms=0.0, seekverify_ms=0.0, chain_ms=0.0, paymf_ms=0.0, paypll_ms=0.0, paydec_ms=0.0, total_ms=0.0)
-        for i in range(max(a.warmup, 1) + 3):
-            ctx.reset()
-            nres = ctx.process_raw(ptrs, counts, True)
-            if i >= max(a.warmup, 1):
-                tm = ctx.timing()
-                for k in kt: kt[k] += tm[k] / 3.0
-        ok = check(ctx, nres)
+        if a.full:
+            # per-kernel device times (HIP events on the library's own streams), taken un-pipelined so that they are
+            # pure kernel durations: these feed `kernels_ms_one_block_in_flight`
+            kt = dict(walk_ms=0.0, seekverify_ms=0.0, chain_ms=0.0, paymf_ms=0.0, paypll_ms=0.0, paydec_ms=0.0, total_ms=0.0)
+            for i in range(max(a.warmup, 1) + 3):
+                ctx.reset()
+                nres = ctx.process_raw(ptrs, counts, True)
+                if i >= max(a.warmup, 1):
+                    tm = ctx.timing()
+                    for k in kt: kt[k] += tm[k] / 3.0
+            check(ctx, nres)
 
         # timed region: each step a full pass (reset + walk + MF + PLL + decode + results to the host), issued
         # through the submit/collect pipeline the way a streaming receiver feeds consecutive blocks
         ctx.set_depth(depth)
         # Stage times come from HIP events recorded between a block's kernels; every event is one more packet in the block's queue, and
-        # with blocks in flight the packet rate is what limits throughput.  The timed region therefore records
-        # only the pair around the kernel the roofline line is quoted for (the PLL: fxrx_set_timing level 1); a second, shorter region
-        # with all stage events on fills `kernels_ms` (and is reported as value_with_all_stage_events).
-        ctx.set_timing(1)
+        # with blocks in flight the packet rate is what limits throughput.  The headline region therefore records
+        # none (fxrx_set_timing level 0).  With --full, a second region records the pair around the kernel the roofline line is quoted
+        # for (the PLL: level 1), and a third, shorter one all stage events (fills `kernels_ms`, reported as value_with_all_stage_events).
+        ctx.set_timing(0)
         kt_live = dict(walk_ms=0.0, seekverify_ms=0.0, chain_ms=0.0, paymf_ms=0.0, paypll_ms=0.0, paydec_ms=0.0, host_submit_ms=0.0, host_walkwait_ms=0.0, host_collectwait_ms=0.0)
 
         def make_runner(c, acc, src=None, on_dev=True, cont=None):
@@ -320,11 +365,22 @@ def main(argv=None):
                     last = collect(); inflight -= 1
                 return last
             return run
-        run_steps = make_runner(ctx, kt_live)
+        run_head = make_runner(ctx, None)
+        run_live = make_runner(ctx, kt_live)
+
+    def region(run, n):
+        """ONE timed region of n passes, barrier + device sync on both sides, max over ranks."""
+        if world > 1: dist.barrier()
+        if not stub: torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        nres = run(n)
+        if not stub: torch.cuda.synchronize()
+        if world > 1: dist.barrier()
+        return reduce_max_time(time.perf_counter() - t0, dist if world > 1 else None, rdev), nres
 
     def timed(run, steps, min_time):
-        """warm-up, pick the repeat count from the warm-up rate (same on every rank), then ONE timed region of
-        steps * repeats passes, barrier + device sync on both sides, max over ranks."""
+        """(--full) warm-up, pick the repeat count from the warm-up rate (same on every rank), then ONE timed region of
+        steps * repeats passes."""
         nw = max(a.warmup, 1) * 4
         run(nw)                                              # untimed warm-up of the pipelined path itself
         if not stub: torch.cuda.synchronize()
@@ -334,49 +390,69 @@ def main(argv=None):
         est = reduce_max_time(est, dist if world > 1 else None, rdev)
         reps = choose_repeats(est, steps, min_time)
         while True:
-            if world > 1: dist.barrier()
-            if not stub: torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            nres = run(steps * reps)
-            if not stub: torch.cuda.synchronize()
-            if world > 1: dist.barrier()
-            dt = time.perf_counter() - t0
-            dt = reduce_max_time(dt, dist if world > 1 else None, rdev)
+            dt, nres = region(run, steps * reps)
             # the warm-up estimate contains the fill and drain of the pipeline and is pessimistic: if the region came out
             # short, time a longer one (same decision on every rank: dt is the max over ranks)
             if dt >= 0.95 * min_time or reps >= 1 << 20: break
             reps = max(reps + 1, int(math.ceil(reps * min_time / max(dt, 1e-9) * 1.1)))
         return dt, reps, nres
 
-    dt, reps, nres = timed(run_steps, a.steps, a.min_time)
-    passes = a.steps * reps
-    ms_step = dt / passes * 1e3
-    value = world * a.samples / (dt / passes) / 1e6
+    # headline: untimed warm-up of the pipelined path (at least two rounds of the ring of blocks in flight), then exactly
+    # --steps passes in one region
+    run_head(max(max(a.warmup, 1) * 4, 2 * depth))
+    if not stub: torch.cuda.synchronize()
+    dt, nres = region(run_head, a.steps)
+    ms_step = dt / a.steps * 1e3
+    value = world * a.samples / (dt / a.steps) / 1e6
+
+    # the min-time region (--full): the K-step schedule repeated R times back to back inside ONE region that lasts at least
+    # --min-time seconds, so that the fill and drain of the pipeline are amortised; with the PLL's stage events on
+    def repeated_figure(dt_r, reps_r):
+        p = a.steps * reps_r
+        return dict(value=round(world * a.samples / (dt_r / p) / 1e6, 2), ms_per_step=round(dt_r / p * 1e3, 4), steps=a.steps, repeats=reps_r,
+                    passes_timed=p, timed_region_s=round(dt_r, 4))
 
     if stub:
+        rep = None
+        if a.full:
+            rep = repeated_figure(*timed(run_live, a.steps, a.min_time)[:2])
         if rank == 0:
-            print(json.dumps({"metric": "Msamples/s through flex_rx (QPSK r1/2 1024B)", "value": round(value, 2), "unit": "Msamples/s",
-                              "n_gpus": world, "steps": a.steps, "repeats": reps, "passes_timed": passes, "warmup": a.warmup,
-                              "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                              "dtype": "f32", "data": "stub", "config": {"workload": "BENCH_STUB=1: launch logic only, nothing measured"}}), flush=True)
+            out = {"metric": "Msamples/s through flex_rx (QPSK r1/2 1024B)", "value": round(value, 2), "unit": "Msamples/s",
+                   "n_gpus": world, "steps": a.steps, "repeats": 1, "passes_timed": a.steps, "warmup": a.warmup,
+                   "ms_per_step": round(ms_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                   "dtype": "f32", "data": "stub", "config": {"workload": "BENCH_STUB=1: launch logic only, nothing measured"}}
+            if rep is not None:
+                out["value_repeated_to_min_time"] = rep["value"]
+                out["repeated_to_min_time"] = rep
+            print(json.dumps(out), flush=True)
         if world > 1:
             dist.barrier(); dist.destroy_process_group()
         return 0
 
-    ok = check(ctx, nres)
-    live = {k: kt_live[k] / passes for k in kt_live}          # average launch duration inside the timed region (PLL; host times)
-    ctx.set_timing(2)
-    dt_ev, reps_ev, nres_ev = timed(run_steps, max(1, a.steps // 4), a.min_time / 2)
-    check(ctx, nres_ev)
-    p_ev = max(1, a.steps // 4) * reps_ev
-    live_all = {k: kt_live[k] / p_ev for k in kt_live}
-    all_events = dict(value=round(world * a.samples / (dt_ev / p_ev) / 1e6, 2), ms_per_step=round(dt_ev / p_ev * 1e3, 4), passes_timed=p_ev)
-    ctx.set_timing(1)
+    frames = check(ctx, nres)
+    tm = ctx.timing()                                        # counters of the last timed block (always recorded)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, frames)
+
+    if a.full:
+        ctx.set_timing(1)
+        dt_r, reps, nres_r = timed(run_live, a.steps, a.min_time)
+        check(ctx, nres_r)
+        repeated = repeated_figure(dt_r, reps)
+        repeated["stage_events"] = "PLL only (fxrx_set_timing level 1)"
+        live = {k: kt_live[k] / repeated["passes_timed"] for k in kt_live}   # average launch duration inside that region (PLL; host times)
+        ctx.set_timing(2)
+        dt_ev, reps_ev, nres_ev = timed(run_live, max(1, a.steps // 4), a.min_time / 2)
+        check(ctx, nres_ev)
+        p_ev = max(1, a.steps // 4) * reps_ev
+        live_all = {k: kt_live[k] / p_ev for k in kt_live}
+        all_events = dict(value=round(world * a.samples / (dt_ev / p_ev) / 1e6, 2), ms_per_step=round(dt_ev / p_ev * 1e3, 4), passes_timed=p_ev)
+        ctx.set_timing(1)
 
     # second figure: the same passes with the constellation (payload symbols after carrier recovery, what the reference
     # publishes per frame at lib/flex_rx_impl.cc:217-221) copied to the host with every block
     with_syms = None
-    if not a.no_constellation:
+    if a.full and not a.no_constellation:
         ctx2 = fx.RxContext(1, device=local, segment_len=a.segment, want_framesyms=True)
         ctx2.reset(); check(ctx2, ctx2.process_raw(ptrs, counts, True))
         ctx2.set_depth(depth)
@@ -390,7 +466,7 @@ def main(argv=None):
     # another secondary figure: the same passes fed as consecutive blocks of ONE continuing stream (no reset in between: the
     # state-dependent stretch of every block waits for the block before it)
     as_stream = None
-    if not a.no_constellation and not stub and not a.continuous:
+    if a.full and not a.no_constellation and not stub and not a.continuous:
         ctx.reset()
         dtc, repsc, nresc = timed(make_runner(ctx, None, cont=True), max(1, a.steps // 4), a.min_time / 2)
         check(ctx, nresc)                                    # (the capture ends in noise: every block of the continuing stream holds the same whole frames)
@@ -401,7 +477,7 @@ def main(argv=None):
     # third figure ("H2D excluded and included, both reported"): the same passes with the IQ in pinned host memory,
     # uploaded inside every submit -- never `value`
     with_h2d = None
-    if not a.no_constellation and not stub:
+    if a.full and not a.no_constellation and not stub:
         xh = torch.from_numpy(x).pin_memory()
         ctx3 = fx.RxContext(1, device=local, segment_len=a.segment)
         ctx3.reset(); check(ctx3, ctx3.process_raw([xh.data_ptr()], counts, False))
@@ -415,7 +491,7 @@ def main(argv=None):
     # fourth figure: what the reference's block really moves -- IQ from host memory in, the constellation of every frame out
     # (lib/flex_rx_impl.cc:208,217-221) -- both PCIe directions inside every step
     with_io = None
-    if not a.no_constellation and not stub:
+    if a.full and not a.no_constellation and not stub:
         ctx4 = fx.RxContext(1, device=local, segment_len=a.segment, want_framesyms=True)
         ctx4.reset(); check(ctx4, ctx4.process_raw([xh.data_ptr()], counts, False))
         ctx4.set_depth(depth)
@@ -430,7 +506,7 @@ def main(argv=None):
     # pageable memory, flexframesync_execute(q, in, 256) inside (lib/flex_rx_impl.cc:212-215), three messages per frame built
     # and checked (csrc/blocks/dropin_feed.cpp)
     dropin = None
-    if not a.no_constellation and not stub and world == 1:
+    if a.full and not a.no_constellation and not stub and world == 1:
         import ctypes as C
         F = fx._ffi.feed_lib()
         st = fx._ffi.DropinStats()
@@ -464,31 +540,35 @@ def main(argv=None):
                      paypll_ms="fx_paypll_kernel", paydec_ms="decode stage (fx_vbpre/vbfwd/vbfix/vbtrace/vbfinish_kernel + fx_paydec_kernel)")
         dom = "paypll_ms"      # (the largest share of all kernel time in the rocprofv3 summary of this command, profiles/README.md; the walker follows)
         alg_bytes = BYTES_PER_SAMPLE * a.samples
-        achieved = alg_bytes / (live[dom] * 1e-3) / 1e9
         out = {
             "metric": "Msamples/s through flex_rx (QPSK r1/2 1024B)", "value": round(value, 2), "unit": "Msamples/s",
-            "n_gpus": world, "steps": a.steps, "repeats": reps, "passes_timed": passes, "warmup": a.warmup, "ms_per_step": round(ms_step, 4),
+            "n_gpus": world, "steps": a.steps, "repeats": 1, "passes_timed": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_step, 4),
             "timed_region_s": round(dt, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "flex_rx single stream per GPU, %d samples (10 Msym), PSK4 r=1/2 (CONV_V27), 1024-B payload, CRC-24, "
                                    "256-sample gaps, CFO/phase/delay + AWGN Es/N0=20 dB" % a.samples,
-                       "frames_per_stream": len(injected), "frames_decoded_ok": ok, "streams_per_gpu": 1, "blocks_in_flight": depth, "stage_events": "PLL only (fxrx_set_timing level 1)",
-                       "passes_per_step": 1, "steps": a.steps, "repeats": reps,
+                       "frames_per_stream": len(injected), "frames_decoded_ok": len(injected), "streams_per_gpu": 1, "blocks_in_flight": depth,
+                       "stage_events": "none (fxrx_set_timing level 0)", "passes_per_step": 1, "steps": a.steps,
                        "passes": "consecutive blocks of one continuing stream" if a.continuous else "independent captures (reset between passes)",
                        "segments": int(tm["walk_jobs"]), "repairs": int(tm["repairs"])},
-            "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": pmc_traffic(names[dom]),
-                         "algorithmic_bytes_per_launch": int(alg_bytes), "avg_launch_ms": round(live[dom], 4),
-                         "note": "path is latency/VALU-bound, not HBM-bound: see DESIGN.md section 6"},
-            "kernels_ms": {names[k]: round(live_all[k], 4) for k in names},
-            "value_with_all_stage_events": all_events["value"], "with_all_stage_events": all_events,
-            "kernels_ms_one_block_in_flight": {names[k]: round(kt[k], 4) for k in names},
-            "device_ms_per_step": round(kt["total_ms"], 4),
-            "host_ms_per_step": {"in_submit": round(live["host_submit_ms"], 4), "of_which_waiting_for_walker": round(live["host_walkwait_ms"], 4),
-                                 "in_collect_waiting_for_results": round(live["host_collectwait_ms"], 4)},
-            "whole_path_hbm_gbs": round(alg_bytes / (dt / passes) / 1e9, 2),
-            "whole_path_hbm_frac": round(alg_bytes / (dt / passes) / 1e9 / HBM_PEAK_GBS, 5),
+            "whole_path_hbm_gbs": round(alg_bytes / (dt / a.steps) / 1e9, 2),
+            "whole_path_hbm_frac": round(alg_bytes / (dt / a.steps) / 1e9 / HBM_PEAK_GBS, 5),
         }
+        if a.full:
+            achieved = alg_bytes / (live[dom] * 1e-3) / 1e9
+            out.update({
+                "value_repeated_to_min_time": repeated["value"], "repeated_to_min_time": repeated,
+                "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": pmc_traffic(names[dom]),
+                             "algorithmic_bytes_per_launch": int(alg_bytes), "avg_launch_ms": round(live[dom], 4),
+                             "note": "path is latency/VALU-bound, not HBM-bound: see DESIGN.md section 6; PLL launch time from the repeated_to_min_time region"},
+                "kernels_ms": {names[k]: round(live_all[k], 4) for k in names},
+                "value_with_all_stage_events": all_events["value"], "with_all_stage_events": all_events,
+                "kernels_ms_one_block_in_flight": {names[k]: round(kt[k], 4) for k in names},
+                "device_ms_per_step": round(kt["total_ms"], 4),
+                "host_ms_per_step": {"in_submit": round(live["host_submit_ms"], 4), "of_which_waiting_for_walker": round(live["host_walkwait_ms"], 4),
+                                     "in_collect_waiting_for_results": round(live["host_collectwait_ms"], 4)},
+            })
         if with_syms is not None:
             out["value_with_constellation_d2h"] = with_syms["value"]
             out["with_constellation_d2h"] = with_syms
@@ -504,8 +584,8 @@ def main(argv=None):
         if dropin is not None:
             out["value_through_dropin_abi"] = dropin["value"]
             out["through_dropin_abi"] = dropin
-        out["whole_path_hbm_gbs_iq_only"] = round(8.0 * a.samples / (dt / passes) / 1e9, 2)        # the "IQ-only" figure (8 B/sample)
-        if world == 1 and not a.no_cpu_baseline:
+        out["whole_path_hbm_gbs_iq_only"] = round(8.0 * a.samples / (dt / a.steps) / 1e9, 2)        # the "IQ-only" figure (8 B/sample)
+        if a.full and world == 1 and not a.no_cpu_baseline:
             one, allc = cpu_baseline(x)
             out["cpu_baseline"] = one
             out["cpu_baseline_all_cores"] = allc

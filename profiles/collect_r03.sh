@@ -7,12 +7,12 @@ rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 step() { echo "[collect_r03] $1 ($(date +%T))"; }
 # 1. the bench line, as the driver runs it, and variants
-step "bench"; python3 "$R/bench.py" --steps 20 --warmup 5 > "$O/bench_k20.json" 2> "$O/bench_k20.err"
-python3 "$R/bench.py" --no-cpu-baseline --no-constellation --no-pipeline --steps 50 > "$O/bench_lat.json" 2>/dev/null
-python3 "$R/bench.py" --no-cpu-baseline --no-constellation --continuous > "$O/bench_cont.json" 2>/dev/null
+step "bench"; python3 "$R/bench.py" --full --steps 20 --warmup 5 > "$O/bench_k20.json" 2> "$O/bench_k20.err"
+python3 "$R/bench.py" --full --no-cpu-baseline --no-constellation --no-pipeline --steps 50 > "$O/bench_lat.json" 2>/dev/null
+python3 "$R/bench.py" --full --no-cpu-baseline --no-constellation --continuous > "$O/bench_cont.json" 2>/dev/null
 # 2. kernel trace of the default bench command: per-kernel stats + steady-state timeline
 step "bench trace"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench_trace" -o bench -- python3 "$R/bench.py" --no-cpu-baseline --no-constellation > "$O/bench_under_rocprof.json" 2> "$O/bench_trace.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench_trace" -o bench -- python3 "$R/bench.py" --full --no-cpu-baseline --no-constellation > "$O/bench_under_rocprof.json" 2> "$O/bench_trace.err"
 T=$(find "$O/bench_trace" -name "*kernel_trace.csv" | head -1)
 python3 "$R/tools/dev/trace_summary.py" "$T" > "$O/bench_timeline.txt"
 cp $(find "$O/bench_trace" -name "*kernel_stats.csv" | head -1) "$O/bench_kernel_stats.csv"

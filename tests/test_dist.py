@@ -60,17 +60,31 @@ def _run_bench(args, env_extra, timeout=240):
 def test_bench_gpus_flag_spawns_ranks_over_gloo():
     """`python bench.py --gpus 2` with no launcher: main() starts two fresh rank processes itself (RANK / WORLD_SIZE /
     MASTER_* set), they rendezvous (gloo here; the GPU part is stubbed by BENCH_STUB=1), rank 0 prints the line with
-    n_gpus = 2; the timed region is stretched to --min-time by repeating the K-step schedule."""
-    r = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.2"], {})
+    n_gpus = 2; the headline region holds exactly --steps steps, and with --full a second region is stretched to
+    --min-time by repeating the K-step schedule."""
+    r = _run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--min-time", "0.2", "--full"], {})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                         # ONE line, from rank 0
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["data"] == "stub" and d["scaling"] == "weak"
-    assert d["steps"] == 4 and d["repeats"] >= 2 and d["passes_timed"] == 4 * d["repeats"]
+    assert d["steps"] == 4 and d["passes_timed"] == 4
+    rep = d["repeated_to_min_time"]
+    assert rep["steps"] == 4 and rep["repeats"] >= 2 and rep["passes_timed"] == 4 * rep["repeats"]
     # max over ranks: rank 1's stub step is twice as slow as rank 0's, and the whole region lasted >= min-time
-    assert d["ms_per_step"] * d["passes_timed"] >= 190.0
-    assert d["ms_per_step"] >= 0.9
+    assert rep["ms_per_step"] * rep["passes_timed"] >= 190.0
+    assert rep["ms_per_step"] >= 0.9 and d["ms_per_step"] >= 0.9
+
+
+def test_bench_plain_run_times_exactly_the_given_steps():
+    """Without --full the line comes from one region of exactly --steps steps (nothing repeated, no second region)."""
+    r = _run_bench(["--gpus", "2", "--steps", "7", "--warmup", "1", "--min-time", "0.2"], {})
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["passes_timed"] == 7 and d["repeats"] == 1 and "repeated_to_min_time" not in d
+    assert 0.9 <= d["ms_per_step"] and d["ms_per_step"] * 7 < 190.0
 
 
 def test_bench_under_a_launcher_checks_world_size():
