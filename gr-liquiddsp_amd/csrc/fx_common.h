@@ -200,6 +200,7 @@ struct FxBlockHdr {                      // device memory, zeroed at submit; mir
 };
 
 // ---- one result record per chain frame, written straight into pinned host memory ----
+#define FX_REC_VB_CLEAN 1u               // FxOutRec.status: decoded by the batch path's codeword check, no trellis run
 struct FxOutRec {
     int64_t  start;                      // absolute sample index of aligned sample 0
     uint32_t stream; int32_t offset;
@@ -211,7 +212,7 @@ struct FxOutRec {
     uint32_t sym_off, out_off;           // payload symbols / decoded bytes of this frame in the block's arenas
     float    evm_sum;                    // fx_paypll_kernel
     uint32_t payload_valid;              // fx_paydec_kernel
-    uint32_t status;
+    uint32_t status;                     // batch Viterbi path: trellis blocks run again << 8, | FX_REC_VB_CLEAN
     uint8_t  header[FX_HDR_DEC];
     uint32_t byte_off;                   // the frame's offset in the byte arenas (soft values: 8 x this)
 };
@@ -275,8 +276,12 @@ struct FxPayJob {           // one per chain frame; nsym == 0: no payload stage 
     uint32_t pad_;          // 1: the frame has a payload stage
     uint32_t eq;            // 1: equaliser on: taps at chain[chain_idx].eq, symbol instants FX_EQ_DELAY later
     uint32_t chain_idx;     // the frame's slot in the chain table
-    uint32_t vb_off, vb_nblk;   // batch Viterbi path: first work item / number of trellis blocks of this frame
+    uint32_t vb_off;        // batch Viterbi path: first work item of this frame ...
+    uint16_t vb_nblk;       // ... its number of trellis blocks (<= 4097: 8 x 65539 + 6 steps, blocks of >= 128) ...
+    uint16_t vb_clean;      // ... 1: fx_vbpre_kernel found the coded bits a terminated codeword and wrote the message itself:
+                            //    no trellis runs for the frame (0 from fx_plan_kernel, every block)
 };
+static_assert(sizeof(FxPayJob) == 128, "FxPayJob: two 64-byte lines");
 
 // batch Viterbi: trellis steps of warm-up a block runs before its own region (survivor paths merge within a few
 // constraint lengths; whether they did is verified, see fx_vbpost_kernel)

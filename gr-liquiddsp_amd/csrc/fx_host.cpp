@@ -61,8 +61,8 @@ extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStre
                                      uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
                                      FxBlockHdr *hdr_host, uint32_t *plan_ws);
 extern "C" unsigned fx_plan_ws_words(void);
-extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
-                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T);
+extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
+                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on);
 extern "C" hipError_t fx_launch_vbitems(unsigned first_item, unsigned n_items, hipStream_t st, const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap,
                                         const FxBlockHdr *hdr, uint8_t *bufA, const uint8_t *bufB, unsigned long long *dwv, uint8_t *vec_arena, uint32_t *vb_st, uint32_t dbg, int packed,
                                         int with_fix);
@@ -220,6 +220,7 @@ struct fxrx_ctx_s {
     uint64_t plain_hint = 0, batch_hint = 0, vb_items_hint = 0, vb_steps_hint = 0, vb_want_hint = 0;   // likewise: frames of the wave-per-frame / batch decoders, trellis blocks, trellis steps
     bool first_block = true;             // nothing collected yet: grids cover their lists' capacity
     bool batch_viterbi = true;           // FXRX_BATCH_VITERBI=0: every frame through the wave-per-frame decoder
+    bool vb_clean = true;                // FXRX_VB_CLEAN=0: no codeword check in fx_vbpre_kernel, every batch-path frame runs the trellis
     // The repair round within the chain costs two launches per block -- and launches are what the pipeline is short of (DESIGN.md
     // section 6) --, so it is only enqueued while blocks keep needing it: for the next 16 blocks after one that did.
     // FXRX_INCHAIN_REPAIR=0: never, 1: while needed (default), 2: always.
@@ -388,6 +389,7 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_TAPER")) c->taper = std::min(0.95f, (float)std::atof(e));
     if (const char *e = std::getenv("FXRX_CHAIN_SLOW")) c->chain_slow = std::atoi(e) != 0;
     if (const char *e = std::getenv("FXRX_BATCH_VITERBI")) c->batch_viterbi = std::atoi(e) != 0;
+    if (const char *e = std::getenv("FXRX_VB_CLEAN")) c->vb_clean = std::atoi(e) != 0;
     if (const char *e = std::getenv("FXRX_INCHAIN_REPAIR")) c->inchain_repair = std::min(2, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_DEBUG_STOP_AFTER")) c->debug_stop_after = std::atoi(e);
     if (const char *e = std::getenv("FXRX_DEBUG_WALK_TWICE")) c->debug_walk_twice = std::atoi(e);
@@ -766,7 +768,7 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
             // (two work items per lane once the items fill the chip or other blocks do; one per lane for a lone small block)
             const int vb_packed = (c->depth > 1 || c->vb_items_hint > 64ull * 4ull * (uint64_t)c->n_cus * 3ull / 2ull) ? 1 : 0;
             sl.vb_items_launched = c->first_block ? sl.vb_cap : (unsigned)std::min<uint64_t>(sl.vb_cap, c->vb_items_hint + c->vb_items_hint / 2 + 1024);
-            HIP_OK(fx_launch_vbpre(0, sl.vb_pre_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables));
+            HIP_OK(fx_launch_vbpre(0, sl.vb_pre_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0));
             HIP_OK(fx_launch_vbitems(0, sl.vb_items_launched, st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p,
                                      sl.d_vb_st.p, c->vb_debug, vb_packed, (c->first_block || c->vbfix_hint || c->vb_debug) ? 1 : 0));
             HIP_OK(fx_launch_vbfinish(0, sl.vb_pre_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
@@ -1015,7 +1017,7 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
                                 sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
     if (more_batch) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
         HIP_OK(hipMemsetAsync(&hdr_pay->n_vb_fallback, 0, sizeof(uint32_t), sl.st));
-        HIP_OK(fx_launch_vbpre(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables));
+        HIP_OK(fx_launch_vbpre(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0));
         HIP_OK(fx_launch_vbitems(0, h.n_vb_items, sl.st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, c->vb_debug, 1, 1));
         HIP_OK(fx_launch_vbfinish(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
                                   sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p));
@@ -1124,6 +1126,7 @@ static int collect_block(fxrx_ctx_s *c)
     const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR;
     sl.out.resize(h.n_frames);
     uint64_t vb_rep = 0;                       // trellis blocks the batch Viterbi path had to run again (hand-over check failed)
+    uint64_t vb_clean = 0;                     // frames it decoded by the codeword check alone
     for (uint32_t i = 0; i < h.n_frames; i++) {
         const FxOutRec &r = sl.h_recs.p[i];
         fxrx_frame &f = sl.out[i].f; std::memset(&f, 0, sizeof f);
@@ -1137,7 +1140,7 @@ static int collect_block(fxrx_ctx_s *c)
             f.mod_scheme = r.ms; f.mod_bps = r.bps; f.check = r.check; f.fec0 = r.fec0; f.fec1 = r.fec1;
             f.payload_len = r.pay_len; f.num_framesyms = r.nsym;
             f.payload = sl.h_out.p + r.out_off; f.payload_valid = (int)r.payload_valid;
-            vb_rep += r.status >> 8;
+            vb_rep += r.status >> 8; vb_clean += r.status & FX_REC_VB_CLEAN;
             f.evm_sum = r.evm_sum; f.evm_db = 10.0f * log10f(r.evm_sum / (float)(r.nsym ? r.nsym : 1));
             f.framesyms = c->cfg.want_framesyms ? (const fx_complex *)(sl.h_framesyms.p + r.sym_off) : nullptr;
             if (c->cfg.soft_decision && c->cfg.want_framesyms) {
@@ -1176,6 +1179,7 @@ static int collect_block(fxrx_ctx_s *c)
     t.payload_symbols = h.sym_total; t.verify_hops = h.verify_hops + sl.kept_vhops; t.verify_failures = h.verify_failures + sl.kept_vfail;
     t.host_submit_ms = sl.host_submit_ms; t.host_walkwait_ms = 0.0; t.walk_mode = sl.any_late ? 1 : 0; t.replays = c->replays + c->repairs_host;
     t.vb_blocks = h.n_vb_items; t.vb_repairs = vb_rep; t.late_decodes = c->late_decodes; t.vb_fallbacks = h.n_vb_fallback;
+    t.vb_clean = vb_clean;
     sl.busy = false; c->last = &sl;
     c->tail = (c->tail + 1) % nslots; c->inflight--;
     return (int)sl.out.size();

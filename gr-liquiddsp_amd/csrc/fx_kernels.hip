@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "fx_device.h"
+#include "fx_vbclean.h"
 
 // 8 waves: the 49 CFO-sweep transforms of a hop take 7 rounds instead of 13.  The 512-sample window is still
 // handled by the first 256 threads (HALF); reductions keep the 4-wave tree order of the canonical arithmetic.
@@ -2046,7 +2047,7 @@ void fx_plan_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t det
             j.nsym = f.valid ? fp->pay_sym_len : 0u; j.sym_off = sym_off;
             j.pay_len = fp->pay_len; j.check = fp->check; j.fec0 = fp->fec0; j.fec1 = fp->fec1; j.k = f.k; j.l0 = f.l0; j.l1 = f.l1;
             j.byte_off = byte_off; j.dw_off = dw_off; j.out_off = out_off; j.pad_ = f.valid ? 1u : 0u;
-            j.eq = eq; j.chain_idx = (uint32_t)(fp - chain); j.vb_off = 0; j.vb_nblk = f.vnb;
+            j.eq = eq; j.chain_idx = (uint32_t)(fp - chain); j.vb_off = 0; j.vb_nblk = (uint16_t)f.vnb; j.vb_clean = 0;
             pjobs[g] = j;
             // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
             union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
@@ -3505,7 +3506,10 @@ __device__ __forceinline__ void vb2_forward(int p, uint32_t blk, const VbHalf &A
 }
 
 // ---- forward pass: one lane per (frame, trellis block) work item; the items of a wave share their puncturing code ----
-// vb_items: [0, cap) the frame of every item slot (0xFFFFFFFF: padding of a code class's last wave), [cap, 2 cap) its block
+// vb_items: [0, cap) the frame of every item slot (0xFFFFFFFF: padding of a code class's last wave), [cap, 2 cap) its block.
+// The items of a frame fx_vbpre_kernel has decoded itself (FxPayJob.vb_clean) are off like padding: the trellis kernels
+// neither read nor write their status words, vector records or decision words (all stale), and a wave without a live item
+// leaves at once.
 struct VbItem { uint32_t g, b, t_reg, t1, Tn, nblk; bool on; };
 __device__ __forceinline__ VbItem vb_item(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, uint32_t slot, uint32_t blk)
 {
@@ -3514,6 +3518,7 @@ __device__ __forceinline__ VbItem vb_item(const FxPayJob *jobs, const uint32_t *
     it.on = item != 0xFFFFFFFFu;
     it.g = it.on ? item : 0u; it.b = it.on ? vb_items[item_cap + slot] : 0u;
     const FxPayJob &job = jobs[it.g];
+    it.on = it.on && job.vb_clean == 0u;
     it.Tn = 8u * job.k + 6u; it.nblk = job.vb_nblk;
     it.t_reg = it.b * blk; it.t1 = min(it.Tn, it.t_reg + blk);
     return it;
@@ -3732,9 +3737,38 @@ __device__ __forceinline__ void vb_pack_bytes(const uint8_t *hs, unsigned bps, u
         dst[j] = (uint8_t)v;
     }
 }
+// coded-bit word w (8 bytes, big-endian) of a packet de-interleaved in LDS
+__device__ __forceinline__ uint64_t vb_lds_word(const uint8_t *X, uint32_t w)
+{
+    const uint2 v = reinterpret_cast<const uint2 *>(X)[w];
+    return ((uint64_t)__builtin_bswap32(v.x) << 32) | __builtin_bswap32(v.y);
+}
+// Rate 1/2 frames whose coded bits, as received, are exactly the encoding of a message with a zero tail: that message is what
+// the Viterbi decoder outputs (every other path into any state of it costs d_free = 10 or more), so it is written to A here
+// -- bit 7 of byte j is step 8 j, as the traceback leaves it -- and the frame is marked clean: the trellis kernels skip it and
+// fx_vbfinish_kernel goes straight to its tail (fx_vbclean.h: the code's feed-forward inverse, the re-encoding, the
+// comparison).  A lane per 32-step word, the words before it re-read from LDS for the carries.
+__device__ __forceinline__ void vb_clean_check(FxPayJob *jobs, uint32_t jf, uint32_t k, const uint8_t *X, uint8_t *A, int lane)
+{
+    const uint32_t Tn = 8u * k + 6u, nw = (Tn + 31u) / 32u;
+    bool ok = true;
+    for (uint32_t w = lane; w < nw; w += DEC_THREADS) {
+        uint32_t u;
+        ok = ok && vbc_check_word(w >= 2u ? vb_lds_word(X, w - 2u) : 0ull, w >= 1u ? vb_lds_word(X, w - 1u) : 0ull, vb_lds_word(X, w), w, Tn, u) == 0u;
+    }
+    const bool clean = !__any(!ok);
+    if (clean) {                                                           // (a second pass: A is written for clean frames only)
+        for (uint32_t w = lane; 4u * w < k; w += DEC_THREADS) {
+            uint32_t u;
+            (void)vbc_check_word(w >= 2u ? vb_lds_word(X, w - 2u) : 0ull, w >= 1u ? vb_lds_word(X, w - 1u) : 0ull, vb_lds_word(X, w), w, Tn, u);
+            reinterpret_cast<uint32_t *>(A)[w] = __builtin_bswap32(u);   // (byte_off is a multiple of 16; bytes up to k + 3 are the frame's)
+        }
+    }
+    if (lane == 0) jobs[jf].vb_clean = clean ? 1u : 0u;
+}
 extern "C" __global__ __launch_bounds__(DEC_THREADS)
-void fx_vbpre_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB,
-                     const FxTables *T)
+void fx_vbpre_kernel(FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB,
+                     const FxTables *T, uint32_t clean_on)
 {
     __shared__ __attribute__((aligned(16))) uint8_t X[VBPRE_LDS];
     const uint32_t njobs = hdr->n_dec_batch;
@@ -3770,6 +3804,8 @@ void fx_vbpre_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBloc
         __builtin_amdgcn_wave_barrier();
         const uint32_t n16 = (job.l0 + 8u + 15u) / 16u;
         for (uint32_t j = lane; j < n16; j += DEC_THREADS) reinterpret_cast<uint4 *>(B)[j] = reinterpret_cast<const uint4 *>(X)[j];
+        // (the check reads up to 8 bytes past the coded bits: zeroed above; packets on the global-memory branch below keep the trellis)
+        if (clean_on && conv_p(job.fec0) == 1) vb_clean_check(jobs, jf, __builtin_amdgcn_readfirstlane(job.k), X, A, lane);
         return;
     }
     vb_pack_bytes(hs, job.bps, job.l1, A, lane);
@@ -3795,9 +3831,11 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
     const uint32_t jf = job_idx[ji];
     FxPayJob job = jobs[jf];
     job.k = __builtin_amdgcn_readfirstlane(job.k); job.pay_len = __builtin_amdgcn_readfirstlane(job.pay_len);
-    job.check = __builtin_amdgcn_readfirstlane(job.check); job.vb_nblk = __builtin_amdgcn_readfirstlane(job.vb_nblk);
-    job.vb_off = __builtin_amdgcn_readfirstlane(job.vb_off);
+    job.check = __builtin_amdgcn_readfirstlane(job.check); job.vb_nblk = (uint16_t)__builtin_amdgcn_readfirstlane(job.vb_nblk);
+    job.vb_off = __builtin_amdgcn_readfirstlane(job.vb_off); job.vb_clean = (uint16_t)__builtin_amdgcn_readfirstlane(job.vb_clean);
     uint8_t *A = bufA + job.byte_off, *B = bufB + job.byte_off;
+    // a frame fx_vbpre_kernel decoded itself: its message is in A, and its trellis records are stale (no trellis ran)
+    if (job.vb_clean) { dec_tail(job, jf, A, lane, out, recs, FX_REC_VB_CLEAN); return; }
     const uint32_t Tn = 8u * job.k + 6u, at = job.vb_off, nblk = job.vb_nblk;
     bool bad = false, mism = false; uint32_t rep = 0;
     for (uint32_t base = 0; base < nblk; base += 64) {
@@ -3827,11 +3865,11 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
     dec_tail(job, jf, A, lane, out, recs, rep << 8);
 }
 
-extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
-                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T)
+extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
+                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on)
 {
     if (n_waves == 0) return hipSuccess;
-    hipLaunchKernelGGL(fx_vbpre_kernel, dim3(n_waves), dim3(DEC_THREADS), 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, T);
+    hipLaunchKernelGGL(fx_vbpre_kernel, dim3(n_waves), dim3(DEC_THREADS), 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, T, clean_on ? 1u : 0u);
     return hipGetLastError();
 }
 // forward pass, [hand-over check,] traceback: the lane-per-work-item kernels, over the same item slots
