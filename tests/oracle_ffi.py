@@ -29,6 +29,10 @@ def build(force=False):
     return _LIB_PATH
 
 
+class C32(C.Structure):                        # fxr_c32
+    _fields_ = [("re", C.c_float), ("im", C.c_float)]
+
+
 class Stats(C.Structure):
     _fields_ = [("evm", C.c_float), ("rssi", C.c_float), ("cfo", C.c_float),
                 ("framesyms", C.c_void_p), ("num_framesyms", C.c_uint),
@@ -108,7 +112,7 @@ def lib():
         L.fxr_sync_set_equalizer.argtypes = [C.c_void_p, C.c_int]
         L.fxr_sync_set_soft.argtypes = [C.c_void_p, C.c_int]
         L.fxr_sync_last_soft.restype = C.c_void_p; L.fxr_sync_last_soft.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
-        L.fxr_modem_demod_soft.argtypes = [C.c_int, C.c_uint64, C.c_uint, C.c_void_p]
+        L.fxr_modem_demod_soft.argtypes = [C.c_int, C32, C.c_uint, C.c_void_p]       # (fxr_c32 by value: an SSE-class argument)
         L.fxr_eq_init_taps.argtypes = [C.c_void_p]
         L.fxr_sync_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_uint]
         L.fxr_sync_execute_chunked.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint]
