@@ -30,6 +30,7 @@ struct FxTables {
     uint8_t  h128dec[4096];
     uint32_t golenc[4096], golerr[4096];   // Golay(24,12): codeword of a 12-bit word, error pattern of a syndrome
     uint8_t  rsexp[512], rslog[256];       // GF(2^8)/0x11d for Reed-Solomon RS(255,223)
+    uint8_t  h84enc[16];                   // Hamming(8,4) codewords (soft header decoding)
 };
 
 #define FX_DEV __device__ __forceinline__

@@ -45,14 +45,15 @@
 #include "fx_device.h"
 #include "fx_codec.hpp"
 
-extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, unsigned njobs, hipStream_t st, const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results,
+extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, int sh, unsigned njobs, hipStream_t st, const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results,
                                      FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, const FxTables *T, int ext, uint32_t n_jobs_total,
                                      const uint32_t *n_list, uint32_t list_cap);
 extern "C" hipError_t fx_launch_seekverify(unsigned grid, hipStream_t st, const FxVerifyRun *runs, uint32_t run_cap, const FxWalkJob *jobs, FxWalkResult *results,
                                            FxFrame *frames, FxBlockHdr *hdr, const FxTables *T, uint32_t phase);
-extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total,
+extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, int sh, unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total,
                                       FxWalkResult *results, FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap,
                                       FxBlockHdr *hdr, uint32_t force_slow, const FxTables *T);
+extern "C" hipError_t fx_launch_hdrdec(int soft, unsigned n, hipStream_t st, const uint8_t *in, uint8_t *out, int32_t *valid, const FxTables *T);
 extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, const FxWalkResult *results,
                                           const FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxBlockHdr *hdr, uint32_t force_repair,
                                           FxWalkJob *jobs_rw, uint32_t *req_list, uint32_t *stat, uint32_t pass);
@@ -249,7 +250,7 @@ struct fxrx_ctx_s {
 
 namespace {
 
-int upload_tables(fxrx_ctx_s *c)
+std::unique_ptr<FxTables> make_tables()
 {
     const fx::HostTables &H = fx::host_tables();
     const fx::BlockCodes &B = fx::block_codes();
@@ -280,11 +281,17 @@ int upload_tables(fxrx_ctx_s *c)
     }
     for (size_t i = 0; i < H.perm54.size(); i++) t->perm54[i] = (uint16_t)H.perm54[i];
     for (size_t i = 0; i < H.perm27.size(); i++) t->perm27[i] = (uint16_t)H.perm27[i];
-    std::memcpy(t->h84dec, B.h84_dec, 256); std::memcpy(t->sdcol, B.sd_col, 64);
+    std::memcpy(t->h84dec, B.h84_dec, 256); std::memcpy(t->h84enc, B.h84_enc, 16); std::memcpy(t->sdcol, B.sd_col, 64);
     std::memcpy(t->sd22col, B.sd22_col, 16); std::memcpy(t->sd39col, B.sd39_col, 32);
     std::memcpy(t->h74dec, B.h74_dec, 128); std::memcpy(t->h128dec, B.h128_dec, 4096);
     std::memcpy(t->golenc, B.gol_enc, sizeof B.gol_enc); std::memcpy(t->golerr, B.gol_err, sizeof B.gol_err);
     std::memcpy(t->rsexp, B.rs_exp, 512); std::memcpy(t->rslog, B.rs_log, 256);
+    return t;
+}
+
+int upload_tables(fxrx_ctx_s *c)
+{
+    std::unique_ptr<FxTables> t = make_tables();
     HIP_OK(hipMalloc((void **)&c->d_tables, sizeof(FxTables)));
     HIP_OK(hipMemcpy(c->d_tables, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
     return 0;
@@ -374,6 +381,7 @@ void fxrx_destroy(fxrx_ctx *c)
 fxrx_ctx *fxrx_create(const fxrx_config *cfg)
 {
     if (!cfg || cfg->n_streams == 0) { set_err("fxrx_create: bad config"); return nullptr; }
+    if (cfg->mode == FXRX_MODE_DETECTOR && cfg->soft_header) { set_err("fxrx_create: soft_header needs flex_rx mode (FXRX_ERR_ARG)"); return nullptr; }
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || cfg->device >= nd) {
         set_err("fxrx_create: no usable HIP device (this library has no CPU path)"); return nullptr;
@@ -634,9 +642,9 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl)
     const int tl = c->timing_level >= 0 ? c->timing_level : (c->depth > 1 ? 0 : 2);      // stage events: see fxrx_set_timing
     sl.timing_level = tl;
     for (int rep = 0; rep < c->debug_walk_twice; rep++)
-        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
+        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[0], st));
-    HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
+    HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
     // the true walkers of continuing streams read the state the previous block's chain kernel leaves.  What the speculative
     // walkers skipped is verified before that wait -- it does not depend on the state --, so that the chain of dependencies
     // from one block's chain kernel to the next one's is just: true walkers, their few verification runs, chain kernel
@@ -659,7 +667,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl)
         cst = c->st_chain;
         HIP_OK(hipStreamWaitEvent(cst, sl.ev[9], 0));
         if (c->prev_chain) HIP_OK(hipStreamWaitEvent(cst, c->prev_chain, 0));
-        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, (unsigned)late.size(), cst, d_jobs, d_list + early.size(), sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
+        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)late.size(), cst, d_jobs, d_list + early.size(), sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
     }
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[1], cst));
     if (verify)
@@ -690,7 +698,7 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
     const uint32_t chain_slots = sl.chain_cap, list_cap = chain_slots + 64 * FX_PLL_CLASSES;
     FxBlockHdr *hdr = sl.d_hdr.p, *hdr_pay = sl.d_hdr.p + 1;
     if (chain_mode == kChainFull)
-        HIP_OK(fx_launch_chain(mode, c->cfg.equalizer ? 1 : 0, NS, st, d_streams, d_jobs, (uint32_t)sl.NJ, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, sl.d_runs.p, sl.run_cap,
+        HIP_OK(fx_launch_chain(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, NS, st, d_streams, d_jobs, (uint32_t)sl.NJ, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, sl.d_runs.p, sl.run_cap,
                                hdr, c->chain_slow ? 1u : 0u, c->d_tables));
     else if (chain_mode == kChainFast) {
         // stitch; one repair round within the chain for what only takes a walk from a hand-off state (a hand-off target missing
@@ -706,7 +714,7 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
             HIP_OK(fx_launch_chainfast(NS, cs, d_streams, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, hdr, c->chain_slow ? 1u : 0u, nullptr, nullptr, nullptr, 0u));
         else {
             HIP_OK(fx_launch_chainfast(NS, cs, d_streams, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, hdr, 0u, d_jobs_rw, sl.d_req.p, sl.d_cstat.p, 1u));
-            HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, (unsigned)std::min<size_t>(2 * sl.NJ, 64), cs, d_jobs, sl.d_req.p, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, hdr,
+            HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)std::min<size_t>(2 * sl.NJ, 64), cs, d_jobs, sl.d_req.p, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, hdr,
                                   c->d_tables, 1, (uint32_t)sl.NJ, &hdr->n_repair_req, req_cap));
             HIP_OK(fx_launch_chainfast(NS, cs, d_streams, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, hdr, 0u, nullptr, nullptr, sl.d_cstat.p, 2u));
         }
@@ -895,7 +903,7 @@ static int repair_rounds(fxrx_ctx_s *c, Slot &sl)
             for (uint32_t r : req) if ((r & 0x80000000u) && (r & 0x7fffffffu) < sl.NJ) c->st[hj[r & 0x7fffffffu].stream].noskip_left = 32;
         }
         HIP_OK(hipMemsetAsync(hdr, 0, sizeof(FxBlockHdr), st));
-        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, hh.n_repair_req, st, d_jobs, sl.d_req.p, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, hdr, c->d_tables, 1, (uint32_t)sl.NJ, nullptr, 0u));
+        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, hh.n_repair_req, st, d_jobs, sl.d_req.p, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, hdr, c->d_tables, 1, (uint32_t)sl.NJ, nullptr, 0u));
         HIP_OK(hipMemcpyAsync(&hh, hdr, sizeof hh, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         sl.kept_hops += hh.hops; sl.kept_cheap += hh.hops_cheap; sl.kept_repairs += hh.walk_jobs_run ? hh.walk_jobs_run : 0;
@@ -1090,6 +1098,35 @@ int fxrx_debug_fail(fxrx_ctx *c, unsigned int submits, unsigned int collects)
     if (!c) return FXRX_ERR_ARG;
     c->debug_fail_submit = submits; c->debug_fail_collect = collects;
     return 0;
+}
+
+int fxrx_debug_header_decode(int soft, const uint8_t *in, unsigned int n, uint8_t *out20, int *valid)
+{
+    if (!in || !out20 || !valid) return FXRX_ERR_ARG;
+    if (n == 0) return 0;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_err("fxrx_debug_header_decode: no usable HIP device"); return FXRX_ERR_NODEVICE; }
+    const size_t in_bytes = (size_t)n * (soft ? 8 * FX_HDR_ENC : FX_HDR_ENC);
+    std::unique_ptr<FxTables> t = make_tables();
+    FxTables *d_t = nullptr; uint8_t *d_in = nullptr, *d_out = nullptr; int32_t *d_valid = nullptr;
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void **)&d_t, sizeof(FxTables)));
+        HIP_OK(hipMalloc((void **)&d_in, in_bytes));
+        HIP_OK(hipMalloc((void **)&d_out, (size_t)n * FX_HDR_DEC));
+        HIP_OK(hipMalloc((void **)&d_valid, (size_t)n * sizeof(int32_t)));
+        HIP_OK(hipMemcpy(d_t, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
+        HIP_OK(fx_launch_hdrdec(soft ? 1 : 0, n, nullptr, d_in, d_out, d_valid, d_t));
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipMemcpy(out20, d_out, (size_t)n * FX_HDR_DEC, hipMemcpyDeviceToHost));
+        std::vector<int32_t> v(n);
+        HIP_OK(hipMemcpy(v.data(), d_valid, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (unsigned i = 0; i < n; i++) valid[i] = v[i];
+        return 0;
+    };
+    const int rc = run();
+    for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out, (void *)d_valid }) if (p) (void)hipFree(p);
+    return rc;
 }
 
 static int collect_block(fxrx_ctx_s *c)

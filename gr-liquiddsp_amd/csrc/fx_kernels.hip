@@ -57,7 +57,12 @@ template <int WW> struct WalkLdsT {
     uint32_t cand[WW];
     uint8_t hs[FX_HDR_MOD];
     uint8_t b0[64], b1[64];
+    // soft header (fxrx_config.soft_header): the 432 soft values of the coded bits and their de-interleaved copy, in m2 past
+    // the 32 entries of the pilot DFT (m2 is scratch by the time the header is decoded)
+    __device__ __forceinline__ uint8_t *hsoft() { return reinterpret_cast<uint8_t *>(m2 + 32); }
 };
+#define FX_HDR_SOFT_STRIDE 448
+static_assert(32 * sizeof(float) + FX_HDR_SOFT_STRIDE + 8 * FX_HDR_ENC <= FX_NFFT * sizeof(float), "soft header values must fit in m2");
 
 // what one detector hop needs, and nothing else: the seek verifier's workgroups (30 KB) leave LDS for the single-wave
 // PLL workgroups of the blocks in flight -- with the walker's 53-KB layout three verifier workgroups fill a CU's LDS
@@ -216,23 +221,81 @@ template <class LDS> __device__ __forceinline__ bool seek_sweep(LDS &L, float x2
     return (peak > threshold) && (bidx < FX_NFFT - FX_S_LEN);
 }
 
+// soft value of one bit, 0 = surely 0 ... 255 = surely 1 (fx_softdemod_kernel's rule; the soft header front uses it too)
+__device__ __forceinline__ uint8_t soft_byte(float d0, float d1, float gamma16)
+{
+    float t = rintf(fmaf(d0 - d1, gamma16, 127.0f));
+    t = fminf(fmaxf(t, 0.0f), 255.0f);
+    return (uint8_t)t;
+}
+__device__ __forceinline__ void soft_axis(float v, unsigned nb, float al, float gamma16, uint8_t *soft)
+{
+    const unsigned L = 1u << nb;
+    float d0[3] = { 1e30f, 1e30f, 1e30f }, d1[3] = { 1e30f, 1e30f, 1e30f };
+    for (unsigned i = 0; i < L; i++) {
+        const float dx = v - (2.0f * (float)i - (float)(L - 1)) * al, d = dx * dx;
+        const unsigned g = gray_enc(i);
+#pragma unroll
+        for (unsigned b = 0; b < 3; b++) if (b < nb) { if ((g >> (nb - 1 - b)) & 1u) d1[b] = fminf(d1[b], d); else d0[b] = fminf(d0[b], d); }
+    }
+#pragma unroll
+    for (unsigned b = 0; b < 3; b++) if (b < nb) soft[b] = soft_byte(d0[b], d1[b], gamma16);
+}
+
 // header: 54 received bytes (L.b0) -> 20 header bytes (L.b1[0..19]) + CRC verdict (L.u[1]).
 // Called by the whole workgroup; every stage is spread over threads (a one-thread version of this cost more
-// than the rest of the header span together).
-template <class LDS> __device__ __forceinline__ void decode_header_bytes(LDS &L, const FxTables *T, int tid)
+// than the rest of the header span together).  Two fronts turn the channel's bits into the 27 Hamming(8,4)-decoded
+// bytes in L.b0 (hard: header_front_hard, soft: header_front_soft); header_back does the rest for both.
+__device__ __forceinline__ uint8_t gather_bits(const uint8_t *src, const uint16_t *perm, int j)
+{
+    unsigned v = 0;
+#pragma unroll
+    for (int b = 0; b < 8; b++) { const unsigned s_ = perm[8 * j + b]; v = (v << 1) | ((src[s_ >> 3] >> (7 - (s_ & 7))) & 1u); }
+    return (uint8_t)v;
+}
+template <class LDS> __device__ __forceinline__ void header_front_hard(LDS &L, const FxTables *T, int tid)
 {
     uint8_t *b0 = L.b0, *b1 = L.b1;
-    auto gather_byte = [&](const uint8_t *src, const uint16_t *perm, int j) -> uint8_t {
-        unsigned v = 0;
-#pragma unroll
-        for (int b = 0; b < 8; b++) { const unsigned s_ = perm[8 * j + b]; v = (v << 1) | ((src[s_ >> 3] >> (7 - (s_ & 7))) & 1u); }
-        return (uint8_t)v;
-    };
-    if (tid < FX_HDR_ENC) b1[tid] = gather_byte(b0, T->perm54, tid);                       // de-interleave (54)
+    if (tid < FX_HDR_ENC) b1[tid] = gather_bits(b0, T->perm54, tid);                       // de-interleave (54)
     __syncthreads();
     if (tid < FX_HDR_E0) b0[tid] = (uint8_t)((T->h84dec[b1[2 * tid]] << 4) | T->h84dec[b1[2 * tid + 1]]);   // Hamming(8,4)
     __syncthreads();
-    if (tid < FX_HDR_E0) b1[tid] = gather_byte(b0, T->perm27, tid);                        // de-interleave (27)
+}
+// soft front (fxrx_config.soft_header): L.hsoft() holds the 432 soft values of the header's coded bits in channel order,
+// 0 = surely 0 ... 255 = surely 1.  De-interleave them as bits, then maximum-likelihood Hamming(8,4) per word: the message d
+// that minimises sum_b (bit b of h84enc[d] ? 255 - s_b : s_b), ties to the smallest d (the hard table's rule; on soft values
+// 0 / 255 alone the cost is 255 x the Hamming distance, so this is exactly the hard decoder).  The cost is taken as
+// sum_b s_b + sum_{b set} (255 - 2 s_b); the first term is the same for every d.
+template <class LDS> __device__ __forceinline__ void header_front_soft(LDS &L, const FxTables *T, int tid)
+{
+    constexpr int NT = 64 * LDS::WAVES;
+    const uint8_t *s0 = L.hsoft();
+    uint8_t *s1 = L.hsoft() + FX_HDR_SOFT_STRIDE;
+    for (int i = tid; i < 8 * FX_HDR_ENC; i += NT) s1[i] = s0[T->perm54[i]];                // de-interleave (432 soft values)
+    __syncthreads();
+    if (tid < 64) {                                                                          // wave 0: lane w decodes word w
+        const uint8_t *sw = s1 + 8 * min(tid, FX_HDR_ENC - 1);
+        int t[8];
+#pragma unroll
+        for (int b = 0; b < 8; b++) t[b] = 255 - 2 * (int)sw[b];
+        int best = 0x7fffffff; unsigned dec = 0;
+#pragma unroll 4
+        for (unsigned d = 0; d < 16; d++) {
+            const unsigned c = T->h84enc[d];
+            int cost = 0;
+#pragma unroll
+            for (int b = 0; b < 8; b++) cost += ((c >> (7 - b)) & 1u) ? t[b] : 0;
+            if (cost < best) { best = cost; dec = d; }
+        }
+        const unsigned lo = (unsigned)__shfl_xor((int)dec, 1, 64);                          // the odd word's nibble
+        if (tid < FX_HDR_ENC && !(tid & 1)) L.b0[tid >> 1] = (uint8_t)((dec << 4) | lo);
+    }
+    __syncthreads();
+}
+template <class LDS> __device__ __forceinline__ void header_back(LDS &L, const FxTables *T, int tid)
+{
+    uint8_t *b0 = L.b0, *b1 = L.b1;
+    if (tid < FX_HDR_E0) b1[tid] = gather_bits(b0, T->perm27, tid);                         // de-interleave (27)
     __syncthreads();
     if (tid < 192) {                                                                       // SECDED(72,64): 3 blocks x 64 bits
         const int blk = tid >> 6, j = tid & 63;
@@ -268,6 +331,18 @@ template <class LDS> __device__ __forceinline__ void decode_header_bytes(LDS &L,
         L.u[1] = key == rx;
     }
     __syncthreads();
+}
+
+template <class LDS> __device__ __forceinline__ void decode_header_bytes(LDS &L, const FxTables *T, int tid)
+{
+    header_front_hard(L, T, tid);
+    header_back(L, T, tid);
+}
+// the same from the 432 soft values in L.hsoft()
+template <class LDS> __device__ __forceinline__ void decode_header_soft(LDS &L, const FxTables *T, int tid)
+{
+    header_front_soft(L, T, tid);
+    header_back(L, T, tid);
 }
 
 // ===================================================================== detector-only walker (frame_detector_cc): a wave per hop
@@ -674,7 +749,8 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
 // EXT (walks of the repair rounds, fx_host.cpp): a hand-off target that the list of the segment it falls in does not hold
 // would only be the next round's repair -- the walker looks it up itself and, if it is not there, carries on through that
 // segment as well (a few times at most, and while its frame table has room).
-template <int MODE, int WW, bool EQ, bool EXT = false>
+// SH (fxrx_config.soft_header): the header is decoded from soft values (header_front_soft) instead of hard QPSK decisions.
+template <int MODE, int WW, bool EQ, bool EXT = false, bool SH = false>
 __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_index, FxWalkResult *result, FxFrame *frames, FxVerifyRun *runs,
                                          uint32_t run_cap, FxBlockHdr *hdr, const FxTables *T_in, WalkLdsT<WW> &L,
                                          const float2 (&twA)[7], const float2 (&twB)[7],
@@ -1199,17 +1275,31 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         }
         const uint32_t pph = rad2u32(pphi);
         const float pg = 1.0f / pgain;
-        if (tid < FX_HDR_SYM && (tid % FX_PILOT_SPACING) != 0) {
-            float2 y = derot(L.hdr[tid], pph + pdl * (uint32_t)tid, sc);
-            y.x *= pg; y.y *= pg;
-            const int nn = tid - 1 - tid / FX_PILOT_SPACING;           // data index (pilots removed)
-            L.hs[nn] = (uint8_t)((y.x > 0.0f ? 0u : 1u) | (y.y > 0.0f ? 0u : 2u));
+        if constexpr (SH) {
+            // soft header: the payload demapper's QPSK rule (fx_softdemod_kernel), MSB (y.y) then LSB (y.x) of data symbol nn
+            if (tid < FX_HDR_SYM && (tid % FX_PILOT_SPACING) != 0) {
+                float2 y = derot(L.hdr[tid], pph + pdl * (uint32_t)tid, sc);
+                y.x *= pg; y.y *= pg;
+                const int nn = tid - 1 - tid / FX_PILOT_SPACING;
+                constexpr float gamma16 = 1.2f * 4.0f * 16.0f;
+                soft_axis(-y.y, 1, 0.70710678118654752f, gamma16, L.hsoft() + 2 * nn);
+                soft_axis(-y.x, 1, 0.70710678118654752f, gamma16, L.hsoft() + 2 * nn + 1);
+            }
+            __syncthreads();
+            decode_header_soft(L, T, tid);
+        } else {
+            if (tid < FX_HDR_SYM && (tid % FX_PILOT_SPACING) != 0) {
+                float2 y = derot(L.hdr[tid], pph + pdl * (uint32_t)tid, sc);
+                y.x *= pg; y.y *= pg;
+                const int nn = tid - 1 - tid / FX_PILOT_SPACING;           // data index (pilots removed)
+                L.hs[nn] = (uint8_t)((y.x > 0.0f ? 0u : 1u) | (y.y > 0.0f ? 0u : 2u));
+            }
+            __syncthreads();
+            if (tid < FX_HDR_ENC)
+                L.b0[tid] = (uint8_t)((L.hs[4 * tid] << 6) | (L.hs[4 * tid + 1] << 4) | (L.hs[4 * tid + 2] << 2) | L.hs[4 * tid + 3]);
+            __syncthreads();
+            decode_header_bytes(L, T, tid);
         }
-        __syncthreads();
-        if (tid < FX_HDR_ENC)
-            L.b0[tid] = (uint8_t)((L.hs[4 * tid] << 6) | (L.hs[4 * tid + 1] << 4) | (L.hs[4 * tid + 2] << 2) | L.hs[4 * tid + 3]);
-        __syncthreads();
-        decode_header_bytes(L, T, tid);
         if (tid == 0) {
             const uint8_t *hd = L.b1;
             int ok = (int)L.u[1];
@@ -1294,13 +1384,13 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
 // the walker of a mode and its LDS layout: the detector-only mode has its own (detect_run, a wave per hop)
 template <int MODE, int WW> struct WalkLdsSel { typedef WalkLdsT<WW> type; };
 template <int WW> struct WalkLdsSel<FX_MODE_DETECT, WW> { typedef DetLdsT<WW> type; };
-template <int MODE, int WW, bool EQ, bool EXT = false>
+template <int MODE, int WW, bool EQ, bool EXT = false, bool SH = false>
 __device__ __forceinline__ void walk_any(const FxWalkJob &job, uint32_t job_index, FxWalkResult *result, FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap,
                                          FxBlockHdr *hdr, const FxTables *T, typename WalkLdsSel<MODE, WW>::type &L, const float2 (&twA)[7], const float2 (&twB)[7],
                                          const FxWalkJob *all_jobs = nullptr, const FxWalkResult *all_results = nullptr, uint32_t n_jobs_total = 0)
 {
     if constexpr (MODE == FX_MODE_DETECT) detect_run<WW, EXT>(job, job_index, result, frames, hdr, T, L, twA, twB, all_jobs, all_results, n_jobs_total);
-    else walk_run<MODE, WW, EQ, EXT>(job, job_index, result, frames, runs, run_cap, hdr, T, L, twA, twB, all_jobs, all_results, n_jobs_total);
+    else walk_run<MODE, WW, EQ, EXT, SH>(job, job_index, result, frames, runs, run_cap, hdr, T, L, twA, twB, all_jobs, all_results, n_jobs_total);
 }
 
 template <int MODE, int WW, bool EQ, bool EXT = false>
@@ -1335,17 +1425,59 @@ void fx_walk_kernel(const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResul
     const FxWalkJob job = jobs[ji];
     walk_any<MODE, WW, EQ, EXT>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
 }
+// the soft-header walker (fxrx_config.soft_header; flex_rx only): a kernel of its own, so that the default instances keep their
+// names and their code (the same prologue as fx_walk_kernel's; shared through a function, the detector's repair instance compiled
+// differently)
+template <int WW, bool EQ, bool EXT = false>
+__global__ __launch_bounds__(64 * WW, FX_FLEX_OCC) FX_WALK_VGPR_ATTR
+void fx_walk_sh_kernel(const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results, FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap,
+                       FxBlockHdr *hdr, const FxTables *T, uint32_t n_jobs_total, const uint32_t *n_list, uint32_t list_cap)
+{
+    __shared__ WalkLdsT<WW> L;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if constexpr (EXT) {
+        // (the repair round enqueued with the block, as in fx_walk_kernel)
+        if (n_list && blockIdx.x >= min(*n_list, list_cap)) return;
+    }
+    float2 twA[7], twB[7];
+#pragma unroll
+    for (int r = 1; r < 8; r++) { twA[r - 1] = T->tw[lane * r]; twB[r - 1] = T->tw[8 * (lane & 7) * r]; }
+    for (int i = tid; i < FX_NFFT; i += 64 * WW) L.S[i] = T->S[i];
+    if constexpr (EXT) {
+        if (n_list) {
+            const uint32_t nreq = min(*n_list, list_cap);
+            for (uint32_t i = blockIdx.x; i < nreq; i += gridDim.x) {
+                const uint32_t ji = job_list[i] & 0x7fffffffu;
+                const FxWalkJob job = jobs[ji];
+                walk_any<FX_MODE_FLEXRX, WW, EQ, EXT, true>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
+                __syncthreads();
+            }
+            return;
+        }
+    }
+    const uint32_t ji = job_list[blockIdx.x] & 0x7fffffffu;
+    const FxWalkJob job = jobs[ji];
+    walk_any<FX_MODE_FLEXRX, WW, EQ, EXT, true>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
+}
+
 
 // (the equaliser stage is a compile-time variant of the flex_rx walker: the default instance carries none of its code)
 // ext: the walks of a repair round (they may carry on into the segments behind theirs); n_list (ext only): the number of queued
-// segments is read from there on the device and `njobs` workgroups stride over them (list_cap bounds the count)
-extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, unsigned njobs, hipStream_t st, const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results,
+// segments is read from there on the device and `njobs` workgroups stride over them (list_cap bounds the count); sh: soft header
+extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, int sh, unsigned njobs, hipStream_t st, const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results,
                                      FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, const FxTables *T, int ext, uint32_t n_jobs_total,
                                      const uint32_t *n_list, uint32_t list_cap)
 {
     if (njobs == 0) return hipSuccess;
 #define FX_WALK_LAUNCH(M, W, E, X) hipLaunchKernelGGL((fx_walk_kernel<M, W, E, X>), dim3(njobs), dim3(64 * W), 0, st, jobs, job_list, results, frames, runs, run_cap, hdr, T, n_jobs_total, n_list, list_cap)
     if (mode == FX_MODE_DETECT) { if (ext) FX_WALK_LAUNCH(FX_MODE_DETECT, FX_DETECT_WAVES, false, true); else FX_WALK_LAUNCH(FX_MODE_DETECT, FX_DETECT_WAVES, false, false); }
+    else if (sh) {
+#define FX_WALK_SH_LAUNCH(E, X) hipLaunchKernelGGL((fx_walk_sh_kernel<FX_FLEX_WAVES, E, X>), dim3(njobs), dim3(64 * FX_FLEX_WAVES), 0, st, jobs, job_list, results, frames, runs, run_cap, hdr, T, n_jobs_total, n_list, list_cap)
+        if (ext) { if (eq) FX_WALK_SH_LAUNCH(true, true); else FX_WALK_SH_LAUNCH(false, true); }
+        else if (eq) FX_WALK_SH_LAUNCH(true, false);
+        else FX_WALK_SH_LAUNCH(false, false);
+#undef FX_WALK_SH_LAUNCH
+    }
     else if (ext) { if (eq) FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, true, true); else FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, false, true); }
     else if (eq) FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, true, false);
     else FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, false, false);
@@ -1722,15 +1854,13 @@ extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, con
 }
 
 // The full-size chain kernel: same fast path, and behind it the general, sequential one that can walk.
-template <int MODE, int WW, bool EQ>
-__global__ __launch_bounds__(64 * WW, 1)
-void fx_chain_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total, FxWalkResult *results, FxFrame *frames,
-                     FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, uint32_t force_slow,
-                     const FxTables *T)
+// SH: the repair walks decode headers like the segments' walkers did (fx_walk_sh_kernel), or speculation would not be exact.
+template <int MODE, int WW, bool EQ, bool SH>
+__device__ __forceinline__ void chain_kernel_body(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total, FxWalkResult *results,
+                                                  FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap,
+                                                  FxBlockHdr *hdr, uint32_t force_slow, const FxTables *T, typename WalkLdsSel<MODE, WW>::type &L, ChainLds &C)
 {
     constexpr int NT = 64 * WW;
-    __shared__ typename WalkLdsSel<MODE, WW>::type L;
-    __shared__ ChainLds C;
     const uint32_t s = blockIdx.x;
     const FxStreamDesc sd = streams[s];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1764,7 +1894,7 @@ void fx_chain_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_
                 j.start = wst; j.floor = wfl; j.fresh = wfr ? 1u : 0u; j.prelock = 0; j.no_skip = 1; j.state_in = nullptr;
                 j.frame_base = sd.repair_base; j.max_frames = sd.repair_cap;
                 __syncthreads();
-                walk_any<MODE, WW, EQ>(j, wj, rep_res, frames, runs, run_cap, hdr, T, L, twA, twB);
+                walk_any<MODE, WW, EQ, false, SH>(j, wj, rep_res, frames, runs, run_cap, hdr, T, L, twA, twB);
                 wg_sync_global();
                 if (tid == 0) atomicAdd(&hdr->repairs, 1u);
                 Rp = rep_res; F = frames + sd.repair_base; m = 0; need_walk = false;
@@ -1828,12 +1958,40 @@ void fx_chain_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_
     chain_finish<NT>(sd, s, st_in, cnt, fin_pos, fin_floor, fin_fresh, chain_count, hdr);
 }
 
-extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total,
+template <int MODE, int WW, bool EQ>
+__global__ __launch_bounds__(64 * WW, 1)
+void fx_chain_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total, FxWalkResult *results, FxFrame *frames,
+                     FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, uint32_t force_slow,
+                     const FxTables *T)
+{
+    __shared__ typename WalkLdsSel<MODE, WW>::type L;
+    __shared__ ChainLds C;
+    chain_kernel_body<MODE, WW, EQ, false>(streams, jobs, n_jobs_total, results, frames, chain, chain_count, runs, run_cap, hdr, force_slow, T, L, C);
+}
+// the soft-header chain kernel (flex_rx only)
+template <int WW, bool EQ>
+__global__ __launch_bounds__(64 * WW, 1)
+void fx_chain_sh_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total, FxWalkResult *results, FxFrame *frames,
+                        FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, uint32_t force_slow,
+                        const FxTables *T)
+{
+    __shared__ WalkLdsT<WW> L;
+    __shared__ ChainLds C;
+    chain_kernel_body<FX_MODE_FLEXRX, WW, EQ, true>(streams, jobs, n_jobs_total, results, frames, chain, chain_count, runs, run_cap, hdr, force_slow, T, L, C);
+}
+
+extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, int sh, unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total,
                                       FxWalkResult *results, FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap,
                                       FxBlockHdr *hdr, uint32_t force_slow, const FxTables *T)
 {
     if (mode == FX_MODE_DETECT)
         hipLaunchKernelGGL((fx_chain_kernel<FX_MODE_DETECT, FX_DETECT_WAVES, false>), dim3(nstreams), dim3(64 * FX_DETECT_WAVES), 0, st, streams, jobs, n_jobs_total, results,
+                           frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
+    else if (sh && eq)
+        hipLaunchKernelGGL((fx_chain_sh_kernel<FX_FLEX_WAVES, true>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
+                           frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
+    else if (sh)
+        hipLaunchKernelGGL((fx_chain_sh_kernel<FX_FLEX_WAVES, false>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
                            frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
     else if (eq)
         hipLaunchKernelGGL((fx_chain_kernel<FX_MODE_FLEXRX, FX_FLEX_WAVES, true>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
@@ -1841,6 +1999,33 @@ extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, unsigned nstreams, 
     else
         hipLaunchKernelGGL((fx_chain_kernel<FX_MODE_FLEXRX, FX_FLEX_WAVES, false>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
                            frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
+    return hipGetLastError();
+}
+
+// fxrx_debug_header_decode: the walker's header decoder (decode_header_bytes / decode_header_soft, same LDS layout) on
+// caller-supplied input, one workgroup per header.  SOFT: 432 soft values per header in channel order, else the 54 hard bytes.
+template <bool SOFT>
+__global__ __launch_bounds__(64 * FX_FLEX_WAVES)
+void fx_hdrdec_kernel(const uint8_t *in, uint32_t n, uint8_t *out, int32_t *valid, const FxTables *T)
+{
+    __shared__ WalkLdsT<FX_FLEX_WAVES> L;
+    const int tid = threadIdx.x;
+    for (uint32_t h = blockIdx.x; h < n; h += gridDim.x) {
+        if constexpr (SOFT) { for (int i = tid; i < 8 * FX_HDR_ENC; i += 64 * FX_FLEX_WAVES) L.hsoft()[i] = in[(size_t)h * (8 * FX_HDR_ENC) + i]; }
+        else if (tid < FX_HDR_ENC) L.b0[tid] = in[(size_t)h * FX_HDR_ENC + tid];
+        __syncthreads();
+        if constexpr (SOFT) decode_header_soft(L, T, tid); else decode_header_bytes(L, T, tid);
+        if (tid < FX_HDR_DEC) out[(size_t)h * FX_HDR_DEC + tid] = L.b1[tid];
+        if (tid == 0) valid[h] = (int32_t)L.u[1];
+        __syncthreads();
+    }
+}
+extern "C" hipError_t fx_launch_hdrdec(int soft, unsigned n, hipStream_t st, const uint8_t *in, uint8_t *out, int32_t *valid, const FxTables *T)
+{
+    if (n == 0) return hipSuccess;
+    const unsigned grid = std::min(n, 65536u);
+    if (soft) hipLaunchKernelGGL((fx_hdrdec_kernel<true>), dim3(grid), dim3(64 * FX_FLEX_WAVES), 0, st, in, n, out, valid, T);
+    else hipLaunchKernelGGL((fx_hdrdec_kernel<false>), dim3(grid), dim3(64 * FX_FLEX_WAVES), 0, st, in, n, out, valid, T);
     return hipGetLastError();
 }
 
@@ -3948,26 +4133,6 @@ extern "C" hipError_t fx_launch_symcopy(unsigned grid, hipStream_t st, const FxB
 // packet byte).  soft = clamp(rint(127 + 16 gamma (d0 - d1))), gamma = 1.2 M, d0 / d1 = squared distance to the nearest point
 // whose label has a 0 / a 1 at that bit: exhaustive over the M phases for PSK, per axis for ASK / QAM; differential PSK: the
 // hard symbol's bits as 0 / 255.  Work items are the matched filter's (frame, 1024 symbols).
-__device__ __forceinline__ uint8_t soft_byte(float d0, float d1, float gamma16)
-{
-    float t = rintf(fmaf(d0 - d1, gamma16, 127.0f));
-    t = fminf(fmaxf(t, 0.0f), 255.0f);
-    return (uint8_t)t;
-}
-__device__ __forceinline__ void soft_axis(float v, unsigned nb, float al, float gamma16, uint8_t *soft)
-{
-    const unsigned L = 1u << nb;
-    float d0[3] = { 1e30f, 1e30f, 1e30f }, d1[3] = { 1e30f, 1e30f, 1e30f };
-    for (unsigned i = 0; i < L; i++) {
-        const float dx = v - (2.0f * (float)i - (float)(L - 1)) * al, d = dx * dx;
-        const unsigned g = gray_enc(i);
-#pragma unroll
-        for (unsigned b = 0; b < 3; b++) if (b < nb) { if ((g >> (nb - 1 - b)) & 1u) d1[b] = fminf(d1[b], d); else d0[b] = fminf(d0[b], d); }
-    }
-#pragma unroll
-    for (unsigned b = 0; b < 3; b++) if (b < nb) soft[b] = soft_byte(d0[b], d1[b], gamma16);
-}
-
 extern "C" __global__ __launch_bounds__(256)
 void fx_softdemod_kernel(const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr, const float2 *framesyms,
                          const uint8_t *hard, uint8_t *soft_arena, const FxTables *T)

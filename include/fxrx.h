@@ -148,6 +148,12 @@ typedef struct {
     int          soft_decision;  /* 1: decode the payload from per-bit soft values (liquid: flexframesync_decode_payload_soft, which the
                                     reference never calls): soft-input Viterbi for the convolutional stage(s) nearest the channel.
                                     With want_framesyms the soft values themselves come back too (fxrx_frame.soft_bits).  0: hard */
+    int          soft_header;    /* 1: decode the 20-byte frame header from per-bit soft values (liquid: flexframesync_decode_header_soft, which
+                                    the reference never calls): the header's QPSK symbols, after pilot phase / frequency / gain correction,
+                                    give two soft values each under the payload demapper's rule above, and the Hamming(8,4) stage next to the
+                                    channel picks the maximum-likelihood codeword of every 8 soft values; SECDED(72,64) and CRC-32 follow as
+                                    before.  The soft rule is this project's, not pinned to liquid's demapper.  Flex_rx mode only
+                                    (fxrx_create fails with FXRX_ERR_ARG in detector mode).  0 (default): hard decisions */
 } fxrx_config;
 
 typedef struct {
@@ -212,6 +218,11 @@ unsigned int fxrx_inflight(const fxrx_ctx *c);
 /* tests: make the next `submits` calls of fxrx_submit / `collects` calls of fxrx_collect fail (FXRX_ERR_STATE) after they have
  * done their bookkeeping, to exercise the paths above */
 int fxrx_debug_fail(fxrx_ctx *c, unsigned int submits, unsigned int collects);
+/* tests: run the walker's header decoder on the GPU over n headers given in host memory.  soft != 0: `in` holds 432 soft values per
+ * header (0 = surely 0 ... 255 = surely 1) in channel order, before the header's first de-interleaver; soft == 0: the 54 received bytes.
+ * Writes 20 decoded bytes per header to out20 and the CRC-32 verdict (1 / 0) to valid[i].  Synchronous, on the current HIP device;
+ * returns 0 or FXRX_ERR_* */
+int fxrx_debug_header_decode(int soft, const uint8_t *in, unsigned int n, uint8_t *out20, int *valid);
 /* diagnostic builds (-DFX_STAMPS) only: shader-clock deltas of the decode phases of payload job i */
 int fxrx_debug_stamps(const fxrx_ctx *c, unsigned int i, uint32_t out[8]);
 int fxrx_debug_chain_stamps(const fxrx_ctx *c, uint32_t out[8]);  /* chain kernel phase clocks (stream 0) of the last collected block */

@@ -48,4 +48,17 @@ typedef enum {
     LIQUID_MODEM_QAM16 = 27, LIQUID_MODEM_QAM32 = 28, LIQUID_MODEM_QAM64 = 29, LIQUID_MODEM_QPSK = 40
 } modulation_scheme;
 
+/* decoder options of flexframesync [RECALLED liquid 1.3.x: flexframesync_decode_header_soft / flexframesync_decode_payload_soft,
+ * soft-decision demodulation and decoding of the header / the payload].  The reference calls neither.  Here both re-create the
+ * context underneath (its state is reset) and return 0, or -1 if that failed, in which case the previous setting stays in force.
+ * The soft rule is this project's (include/fxrx.h: fxrx_config.soft_header / soft_decision), not pinned to liquid's demapper. */
+#ifdef __cplusplus
+extern "C" {
+#endif
+int flexframesync_decode_header_soft(flexframesync q, int soft);
+int flexframesync_decode_payload_soft(flexframesync q, int soft);
+#ifdef __cplusplus
+}
+#endif
+
 #endif
