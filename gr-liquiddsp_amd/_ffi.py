@@ -43,7 +43,7 @@ class TxChannel(C.Structure):               # fxtx_channel
 class Config(C.Structure):                  # fxrx_config
     _fields_ = [("device", C.c_int), ("mode", C.c_int), ("n_streams", C.c_uint), ("threshold", C.c_float),
                 ("segment_len", C.c_uint), ("want_framesyms", C.c_int), ("equalizer", C.c_int), ("soft_decision", C.c_int),
-                ("soft_header", C.c_int)]
+                ("soft_header", C.c_int), ("soft_block", C.c_int)]
 
 
 class Frame(C.Structure):                   # fxrx_frame
@@ -86,7 +86,7 @@ EXPORTS = [
     "fxrx_outer_from_index", "fxrx_outer_to_index",
     "fxtx_create", "fxtx_destroy", "fxtx_frame_len", "fxtx_generate",
     "fxtx_apply_channel", "fxrx_set_timing", "fxrx_debug_block_times", "fxrx_ready", "fxrx_inflight", "fxrx_debug_fail", "fxrx_pinned_alloc", "fxrx_pinned_free", "fxrx_sync_context",
-    "fxrx_debug_header_decode",
+    "fxrx_debug_header_decode", "fxrx_debug_block_decode", "fxrx_sync_set_soft_block",
 ]
 
 
@@ -173,6 +173,8 @@ def lib():
     L.fxrx_debug_fail.restype = C.c_int; L.fxrx_debug_fail.argtypes = [C.c_void_p, C.c_uint, C.c_uint]
     L.fxrx_debug_header_decode.restype = C.c_int
     L.fxrx_debug_header_decode.argtypes = [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_int)]
+    L.fxrx_debug_block_decode.restype = C.c_int
+    L.fxrx_debug_block_decode.argtypes = [C.c_uint, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
     L.fxrx_pinned_alloc.restype = C.c_void_p; L.fxrx_pinned_alloc.argtypes = [C.c_size_t]
     L.fxrx_pinned_free.restype = None; L.fxrx_pinned_free.argtypes = [C.c_void_p]
     L.fxrx_sync_context.restype = C.c_void_p; L.fxrx_sync_context.argtypes = [C.c_void_p]
@@ -205,6 +207,7 @@ def lib():
     L.fxrx_sync_set_threshold.argtypes = [C.c_void_p, C.c_float]; L.fxrx_sync_set_threshold.restype = None
     L.fxrx_sync_set_equalizer.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_equalizer.restype = None
     L.fxrx_sync_set_soft.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft.restype = None
+    L.fxrx_sync_set_soft_block.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_block.restype = C.c_int
     L.flexframesync_decode_header_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_header_soft.restype = C.c_int
     L.flexframesync_decode_payload_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_payload_soft.restype = C.c_int
     L.fxrx_sync_pending.argtypes = [C.c_void_p]; L.fxrx_sync_pending.restype = C.c_uint

@@ -31,6 +31,8 @@ struct FxTables {
     uint32_t golenc[4096], golerr[4096];   // Golay(24,12): codeword of a 12-bit word, error pattern of a syndrome
     uint8_t  rsexp[512], rslog[256];       // GF(2^8)/0x11d for Reed-Solomon RS(255,223)
     uint8_t  h84enc[16];                   // Hamming(8,4) codewords (soft header decoding)
+    uint32_t h74enc[16], h128enc[256];     // Hamming(7,4) / (12,8) codewords (soft block decoding)
+    uint8_t  sdinv[3][256];                // SECDED (22,16) / (39,32) / (72,64): syndrome -> data column index + 1, 0 = none
 };
 
 #define FX_DEV __device__ __forceinline__

@@ -62,7 +62,7 @@ constexpr unsigned kSyncPollEvery = 1u << 15;       // samples between two looks
 // (every few thousand samples) finds the oldest one done; their frames wait in `pending` and leave one per call.
 struct fxrx_sync_s {
     framesync_callback cb = nullptr; void *ud = nullptr;
-    fxrx_ctx *ctx = nullptr; float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0;
+    fxrx_ctx *ctx = nullptr; float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0, soft_block = 0;
     unsigned block = kSyncBlockDefault, depth = kSyncDepthDefault;
     std::vector<fx_complex *> bufs; unsigned cur = 0; size_t fill = 0;     // ring of depth + 1 pinned input buffers of `block` samples
     std::deque<HeldFrame> pending; HeldFrame current;
@@ -135,7 +135,8 @@ struct fxrx_sync_s {
 static fxrx_ctx *sync_make_ctx(const fxrx_sync_s *q)
 {
     fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_FLEX_RX; cfg.n_streams = 1; cfg.want_framesyms = 1;
-    if (q) { cfg.threshold = q->threshold; cfg.equalizer = q->equalizer; cfg.soft_decision = q->soft; cfg.soft_header = q->soft_header; }
+    if (q) { cfg.threshold = q->threshold; cfg.equalizer = q->equalizer; cfg.soft_decision = q->soft; cfg.soft_header = q->soft_header;
+            cfg.soft_block = q->soft && q->soft_block; }
     if (const char *d = std::getenv("FXRX_DEVICE")) cfg.device = std::atoi(d);
     fxrx_ctx *ctx = fxrx_create(&cfg);
     if (ctx && fxrx_set_depth(ctx, q ? q->depth : kSyncDepthDefault) != 0) { fxrx_destroy(ctx); return nullptr; }
@@ -220,6 +221,7 @@ static int sync_set_option(flexframesync q, int fxrx_sync_s::*field, int on, con
 void fxrx_sync_set_threshold(flexframesync q, float t) { if (!q) return; q->threshold = t; sync_recreate(q, "fxrx_sync_set_threshold"); }
 void fxrx_sync_set_equalizer(flexframesync q, int on) { if (!q) return; q->equalizer = on ? 1 : 0; sync_recreate(q, "fxrx_sync_set_equalizer"); }
 void fxrx_sync_set_soft(flexframesync q, int on) { if (!q) return; q->soft = on ? 1 : 0; sync_recreate(q, "fxrx_sync_set_soft"); }
+int fxrx_sync_set_soft_block(flexframesync q, int on) { return sync_set_option(q, &fxrx_sync_s::soft_block, on, "fxrx_sync_set_soft_block"); }
 // [RECALLED liquid 1.3.x] flexframesync_decode_header_soft / flexframesync_decode_payload_soft (include/liquid/liquid.h)
 int flexframesync_decode_header_soft(flexframesync q, int soft) { return sync_set_option(q, &fxrx_sync_s::soft_header, soft, "flexframesync_decode_header_soft"); }
 int flexframesync_decode_payload_soft(flexframesync q, int soft) { return sync_set_option(q, &fxrx_sync_s::soft, soft, "flexframesync_decode_payload_soft"); }

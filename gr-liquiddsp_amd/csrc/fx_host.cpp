@@ -54,6 +54,7 @@ extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, int sh, unsigned ns
                                       FxWalkResult *results, FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap,
                                       FxBlockHdr *hdr, uint32_t force_slow, const FxTables *T);
 extern "C" hipError_t fx_launch_hdrdec(int soft, unsigned n, hipStream_t st, const uint8_t *in, uint8_t *out, int32_t *valid, const FxTables *T);
+extern "C" hipError_t fx_launch_blkdec(int soft, unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T);
 extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, const FxWalkResult *results,
                                           const FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxBlockHdr *hdr, uint32_t force_repair,
                                           FxWalkJob *jobs_rw, uint32_t *req_list, uint32_t *stat, uint32_t pass);
@@ -286,6 +287,13 @@ std::unique_ptr<FxTables> make_tables()
     std::memcpy(t->h74dec, B.h74_dec, 128); std::memcpy(t->h128dec, B.h128_dec, 4096);
     std::memcpy(t->golenc, B.gol_enc, sizeof B.gol_enc); std::memcpy(t->golerr, B.gol_err, sizeof B.gol_err);
     std::memcpy(t->rsexp, B.rs_exp, 512); std::memcpy(t->rslog, B.rs_log, 256);
+    for (int d = 0; d < 16; d++) t->h74enc[d] = B.h74_enc[d];
+    for (int d = 0; d < 256; d++) t->h128enc[d] = B.h128_enc[d];
+    {   // SECDED: syndrome -> data column + 1 (the columns are distinct and of weight 3 or 5)
+        const uint8_t *cols[3] = { B.sd22_col, B.sd39_col, B.sd_col };
+        const unsigned ncol[3] = { 16, 32, 64 };
+        for (int c = 0; c < 3; c++) for (unsigned j = 0; j < ncol[c]; j++) t->sdinv[c][cols[c][j]] = (uint8_t)(j + 1);
+    }
     return t;
 }
 
@@ -382,6 +390,9 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
 {
     if (!cfg || cfg->n_streams == 0) { set_err("fxrx_create: bad config"); return nullptr; }
     if (cfg->mode == FXRX_MODE_DETECTOR && cfg->soft_header) { set_err("fxrx_create: soft_header needs flex_rx mode (FXRX_ERR_ARG)"); return nullptr; }
+    if (cfg->soft_block && (cfg->mode == FXRX_MODE_DETECTOR || !cfg->soft_decision)) {
+        set_err("fxrx_create: soft_block needs soft_decision and flex_rx mode (FXRX_ERR_ARG)"); return nullptr;
+    }
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || cfg->device >= nd) {
         set_err("fxrx_create: no usable HIP device (this library has no CPU path)"); return nullptr;
@@ -752,7 +763,7 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         // decode: one wave per frame.  The lean instance has no loop (it would double its registers): its grid covers what
         // the last block held plus a margin, and a second, usually empty launch covers the rest of the list's capacity in
         // big workgroups (few of them).  The Reed-Solomon instance strides.
-        const int soft = c->cfg.soft_decision ? 1 : 0;
+        const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? 2 : 1) : 0;     // (fx_launch_paydec)
         if (soft) {
             // per-bit soft values from the carrier-recovered symbols (data parallel, off the PLL's recurrence); the decoder
             // de-interleaves them in place, so a caller that wants to see them gets a copy first
@@ -1012,7 +1023,7 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     if (!more_plain && !more_rs && !more_batch && !more_fb) return 0;
     const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
     FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
-    const int soft = c->cfg.soft_decision ? 1 : 0;
+    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? 2 : 1) : 0;     // (fx_launch_paydec)
     FxPayResult *pres = nullptr;
 #ifdef FX_STAMPS
     pres = sl.d_pres.p;
@@ -1126,6 +1137,33 @@ int fxrx_debug_header_decode(int soft, const uint8_t *in, unsigned int n, uint8_
     };
     const int rc = run();
     for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out, (void *)d_valid }) if (p) (void)hipFree(p);
+    return rc;
+}
+
+int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out)
+{
+    const bool block = fec == FX_FEC_HAMMING74 || fec == FX_FEC_HAMMING84 || fec == FX_FEC_HAMMING128 || fec == FX_FEC_GOLAY2412 ||
+                       fec == FX_FEC_SECDED2216 || fec == FX_FEC_SECDED3932 || fec == FX_FEC_SECDED7264;
+    if (!block || !in || !out || n == 0 || n > 65535) { set_err("fxrx_debug_block_decode: bad argument"); return FXRX_ERR_ARG; }
+    if (count == 0) return 0;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_err("fxrx_debug_block_decode: no usable HIP device"); return FXRX_ERR_NODEVICE; }
+    const size_t el = fx::fec_enc_len(fec, n), in_bytes = (size_t)count * el * (soft ? 8 : 1), out_bytes = (size_t)count * n;
+    std::unique_ptr<FxTables> t = make_tables();
+    FxTables *d_t = nullptr; uint8_t *d_in = nullptr, *d_out = nullptr;
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void **)&d_t, sizeof(FxTables)));
+        HIP_OK(hipMalloc((void **)&d_in, in_bytes));
+        HIP_OK(hipMalloc((void **)&d_out, out_bytes));
+        HIP_OK(hipMemcpy(d_t, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
+        HIP_OK(fx_launch_blkdec(soft ? 1 : 0, fec, n, count, nullptr, d_in, d_out, d_t));
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out }) if (p) (void)hipFree(p);
     return rc;
 }
 

@@ -2870,6 +2870,241 @@ __device__ __forceinline__ void block_fec_decode(unsigned fs, uint32_t n, const 
     }
 }
 
+// ===================================================================== payload: soft-input block decoders (fxrx_config.soft_block)
+// The rules are this project's, not liquid's fec_decode_soft.  Soft values: one byte per coded bit, 0 = surely 0
+// ... 255 = surely 1, de-interleaved, in codeword bit order.  Inside a decoder a codeword is a "position mask": bit b = codeword
+// bit b (b = 0 first on the wire).  The cost of codeword c is sum_b |s_b - 255 c_b|: one v_sad_u8 per four positions against
+// c's bytes of 0 / 255.
+//   Hamming(7,4), (8,4), (12,8): exhaustive maximum likelihood, ties to the smallest message.  The message loop is wave-uniform,
+//     so codewords and their byte masks are scalar work and a candidate costs a few VALU instructions.
+//   Golay(24,12), SECDED: Chase-4 -- the hard decoder on the hard word with every pattern of the four least reliable positions
+//     flipped (syndromes are linear: one XOR of columns per pattern); the cheapest re-encoded success wins, ties to the smallest
+//     pattern; no success at all: the hard decoder's result on the hard word.
+
+// four position bits -> their four bytes of 0 / 255 (byte i = bit i)
+__device__ __forceinline__ uint32_t sb_expand4(uint32_t nib)
+{
+    const uint32_t m = __umul24(nib, 0x00204081u) & 0x01010101u;
+    return (m << 8) - m;
+}
+// the hard decisions (value > 127) of four soft values -> four position bits
+__device__ __forceinline__ uint32_t sb_hard4(uint32_t w) { return (((w >> 7) & 0x01010101u) * 0x10204080u) >> 28; }
+
+// cost of the codeword with position mask pm (32 positions a word) against W words of soft values
+template <int W>
+__device__ __forceinline__ uint32_t sb_cost(const uint32_t (&sw)[W], const uint32_t (&pm)[(W + 7) / 8])
+{
+    uint32_t c = 0;
+#pragma unroll
+    for (int i = 0; i < W; i++) c = __builtin_amdgcn_sad_u8(sw[i], sb_expand4((pm[i >> 3] >> (4 * (i & 7))) & 15u), c);
+    return c;
+}
+
+// the first nvalid of W words of soft values at p (4-byte aligned); the rest 0
+template <int W>
+__device__ __forceinline__ void sb_load(const uint8_t *p, uint32_t nvalid, uint32_t (&sw)[W])
+{
+#pragma unroll
+    for (int i = 0; i < W; i++) sw[i] = (uint32_t)i < nvalid ? reinterpret_cast<const uint32_t *>(p)[i] : 0u;
+}
+
+// hard position mask of the soft values
+template <int W>
+__device__ __forceinline__ void sb_hard(const uint32_t (&sw)[W], uint32_t (&pm)[(W + 7) / 8])
+{
+#pragma unroll
+    for (int i = 0; i < (W + 7) / 8; i++) pm[i] = 0;
+#pragma unroll
+    for (int i = 0; i < W; i++) pm[i >> 3] |= sb_hard4(sw[i]) << (4 * (i & 7));
+}
+
+// Chase test positions: the four transmitted positions (b < nvalid) with the smallest (|2 s_b - 255|, b)
+template <int W>
+__device__ __forceinline__ void sb_least4(const uint32_t (&sw)[W], uint32_t nvalid, uint32_t (&t)[4])
+{
+    uint32_t k0 = ~0u, k1 = ~0u, k2 = ~0u, k3 = ~0u;
+#pragma unroll
+    for (int b = 0; b < 4 * W; b++) {
+        const uint32_t s = (sw[b >> 2] >> (8 * (b & 3))) & 255u;
+        const uint32_t rho = s > 127u ? 2u * s - 255u : 255u - 2u * s;
+        uint32_t x = (uint32_t)b < nvalid ? (rho << 7) | (uint32_t)b : ~0u, a;
+        a = min(k0, x); x = max(k0, x); k0 = a;
+        a = min(k1, x); x = max(k1, x); k1 = a;
+        a = min(k2, x); x = max(k2, x); k2 = a;
+        k3 = min(k3, x);
+    }
+    t[0] = k0 & 127u; t[1] = k1 & 127u; t[2] = k2 & 127u; t[3] = k3 & 127u;
+}
+
+// position mask with position t set (t < 32 M)
+template <int M>
+__device__ __forceinline__ void sb_flip(uint32_t (&pm)[M], uint32_t t)
+{
+#pragma unroll
+    for (int i = 0; i < M; i++) pm[i] ^= (t >> 5) == (uint32_t)i ? 1u << (t & 31u) : 0u;
+}
+
+// exhaustive ML over the 2^K codewords enc[d] of N bits (MSB first); ties to the smallest d
+template <int K, int N, class E>
+__device__ __forceinline__ unsigned sb_ml(const uint32_t (&sw)[(N + 3) / 4], const E *enc)
+{
+    uint32_t best = ~0u;
+    for (uint32_t d = 0; d < (1u << K); d++) {
+        const uint32_t pm[1] = { __builtin_bitreverse32((uint32_t)enc[d]) >> (32 - N) };
+        best = min(best, (sb_cost<(N + 3) / 4>(sw, pm) << K) | d);
+    }
+    return best & ((1u << K) - 1u);
+}
+
+// Golay(24,12), Chase-4, one codeword (24 soft values) -> its 12 data bits
+__device__ __forceinline__ unsigned sb_golay(const uint32_t (&sw)[6], const FxTables *T)
+{
+    uint32_t pm[1], t[4], tr[4], tc[4];
+    sb_hard<6>(sw, pm);
+    sb_least4<6>(sw, 24u, t);
+    const uint32_t r = __builtin_bitreverse32(pm[0]) >> 8;                     // received word, MSB first (position b = bit 23 - b)
+    const uint32_t syn = (T->golenc[r >> 12] ^ r) & 0xfffu;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t q = 23u - t[j];
+        tr[j] = 1u << q;
+        tc[j] = q >= 12u ? T->golenc[1u << (q - 12u)] & 0xfffu : tr[j];     // the syndrome of that one bit
+    }
+    uint32_t best = ~0u, bd = r >> 12;
+#pragma unroll
+    for (int p = 0; p < 16; p++) {
+        uint32_t s = syn, rp = r;
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (p & (1 << j)) { s ^= tc[j]; rp ^= tr[j]; }
+        const uint32_t e = T->golerr[s];
+        if (e != 0xFFFFFFFFu) {
+            // e has syndrome s, so rp ^ e is the codeword of its data: the re-encoding of the hard decoder's output
+            const uint32_t c = rp ^ e, cm[1] = { __builtin_bitreverse32(c) >> 8 };
+            const uint32_t key = (sb_cost<6>(sw, cm) << 4) | (uint32_t)p;
+            if (key < best) { best = key; bd = c >> 12; }
+        }
+    }
+    return bd & 0xfffu;
+}
+
+// SECDED with ND data bytes per block, Chase-4, one block: its soft values at S (parity byte's 8, then the data bits), nb data
+// bytes transmitted; `inv`: syndrome -> data column index + 1 (0: none).  Writes the nb data bytes to dec.
+template <int ND>
+__device__ __forceinline__ void sb_secded_block(const uint8_t *S, uint32_t nb, const uint8_t *col, const uint8_t *inv, uint8_t *dec)
+{
+    constexpr int W = 2 + 2 * ND, M = (W + 7) / 8;
+    const uint32_t nvalid = 8u + 8u * nb;
+    uint32_t sw[W], y[M], t[4], tm[4][M], tc[4];
+    sb_load<W>(S, nvalid / 4u, sw);
+    sb_hard<W>(sw, y);
+    sb_least4<W>(sw, nvalid, t);
+    uint32_t syn = __builtin_bitreverse32(y[0]) >> 24;                         // received parity byte (position p = bit 7 - p)
+#pragma unroll
+    for (int j = 0; j < 8 * ND; j++) if ((y[(8 + j) >> 5] >> ((8 + j) & 31)) & 1u) syn ^= col[j];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+#pragma unroll
+        for (int i = 0; i < M; i++) tm[j][i] = 0;
+        sb_flip<M>(tm[j], t[j]);
+        tc[j] = t[j] < 8u ? 0x80u >> t[j] : (uint32_t)col[t[j] - 8u];
+    }
+    uint32_t best = ~0u, bc[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) bc[i] = y[i];
+#pragma unroll
+    for (int p = 0; p < 16; p++) {
+        uint32_t s = syn, c[M];
+#pragma unroll
+        for (int i = 0; i < M; i++) c[i] = y[i];
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (p & (1 << j)) {
+            s ^= tc[j];
+#pragma unroll
+            for (int i = 0; i < M; i++) c[i] ^= tm[j][i];
+        }
+        // success: syndrome 0, of weight 1 (a parity bit), or a data column.  The candidate is the re-encoded output: a data bit
+        // flipped if its column is transmitted, else the parity byte re-computed (received parity ^ syndrome)
+        const uint32_t iv = inv[s];
+        const bool ok = s == 0u || __popc(s) == 1u || iv != 0u;
+        if (ok) {
+            if (iv != 0u && iv - 1u < 8u * nb) sb_flip<M>(c, 8u + iv - 1u);
+            else c[0] ^= __builtin_bitreverse32(s) >> 24;
+            const uint32_t key = (sb_cost<W>(sw, c) << 4) | (uint32_t)p;
+            if (key < best) {
+                best = key;
+#pragma unroll
+                for (int i = 0; i < M; i++) bc[i] = c[i];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < ND; j++)
+        if ((uint32_t)j < nb) dec[j] = (uint8_t)(__builtin_bitreverse32((bc[(8 + 8 * j) >> 5] >> ((8 + 8 * j) & 31)) & 255u) >> 24);
+}
+
+template <int ND>
+__device__ __forceinline__ void sb_secded(const uint8_t *col, const uint8_t *inv, uint32_t n, const uint8_t *S, uint8_t *dec, int lane)
+{
+    const uint32_t nblk = (n + ND - 1) / ND;
+    for (uint32_t blk = lane; blk < nblk; blk += DEC_THREADS)
+        sb_secded_block<ND>(S + 8 * (ND + 1) * (size_t)blk, min((uint32_t)ND, n - ND * blk), col, inv, dec + ND * (size_t)blk);
+}
+
+// the block codes with a soft-input decoder (not Reed-Solomon)
+__device__ __forceinline__ bool sb_code(unsigned fs)
+{
+    return fs == FX_FEC_HAMMING74 || fs == FX_FEC_HAMMING84 || fs == FX_FEC_HAMMING128 || fs == FX_FEC_GOLAY2412 ||
+           fs == FX_FEC_SECDED2216 || fs == FX_FEC_SECDED3932 || fs == FX_FEC_SECDED7264;
+}
+
+// soft-input counterpart of block_fec_decode: S, the soft values of fec_enc_len(fs, n) coded bytes (8-byte aligned) -> n bytes
+__device__ __forceinline__ void block_fec_decode_soft(unsigned fs, uint32_t n, const uint8_t *S, uint8_t *dec, const FxTables *T, int lane)
+{
+    if (fs == FX_FEC_HAMMING84) {
+        for (uint32_t j = lane; j < n; j += DEC_THREADS) {
+            uint32_t a[2], b[2];
+            sb_load<2>(S + 16 * (size_t)j, 2u, a); sb_load<2>(S + 16 * (size_t)j + 8, 2u, b);
+            dec[j] = (uint8_t)((sb_ml<4, 8>(a, T->h84enc) << 4) | sb_ml<4, 8>(b, T->h84enc));
+        }
+    } else if (fs == FX_FEC_HAMMING74) {
+        // two 7-bit codewords per output byte: positions 14 j .. 14 j + 13, not word aligned
+        for (uint32_t j = lane; j < n; j += DEC_THREADS) {
+            const uint8_t *p = S + 14 * (size_t)j;
+            uint32_t a[2] = { 0, 0 }, b[2] = { 0, 0 };
+#pragma unroll
+            for (int i = 0; i < 7; i++) { a[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3)); b[i >> 2] |= (uint32_t)p[7 + i] << (8 * (i & 3)); }
+            dec[j] = (uint8_t)((sb_ml<4, 7>(a, T->h74enc) << 4) | sb_ml<4, 7>(b, T->h74enc));
+        }
+    } else if (fs == FX_FEC_HAMMING128) {
+        for (uint32_t j = lane; j < n; j += DEC_THREADS) {
+            uint32_t a[3];
+            sb_load<3>(S + 12 * (size_t)j, 3u, a);
+            dec[j] = (uint8_t)sb_ml<8, 12>(a, T->h128enc);
+        }
+    } else if (fs == FX_FEC_GOLAY2412) {
+        // two codewords per three output bytes; a codeword past the coded ones (odd count) only feeds bytes past n
+        const uint32_t ncw = (8 * n + 11) / 12, ngrp = (n + 2) / 3;
+        for (uint32_t g = lane; g < ngrp; g += DEC_THREADS) {
+            uint32_t acc = 0;
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const uint32_t j = 2 * g + c;
+                unsigned d = 0;
+                if (j < ncw) { uint32_t a[6]; sb_load<6>(S + 24 * (size_t)j, 6u, a); d = sb_golay(a, T); }
+                acc = (acc << 12) | d;
+            }
+#pragma unroll
+            for (int b = 0; b < 3; b++) if (3 * g + b < n) dec[3 * g + b] = (uint8_t)(acc >> (8 * (2 - b)));
+        }
+    } else if (fs == FX_FEC_SECDED7264) {
+        sb_secded<8>(T->sdcol, T->sdinv[2], n, S, dec, lane);
+    } else if (fs == FX_FEC_SECDED3932) {
+        sb_secded<4>(T->sd39col, T->sdinv[1], n, S, dec, lane);
+    } else if (fs == FX_FEC_SECDED2216) {
+        sb_secded<2>(T->sd22col, T->sdinv[0], n, S, dec, lane);
+    }
+}
+
 // K=7 (0x6d, 0x4f) hard-decision Viterbi, one lane per state, exchange-free of LDS.
 //
 // A shift-register trellis is a perfect shuffle: state p feeds rotl(p,1) (input bit = p's old MSB) and
@@ -3229,7 +3464,8 @@ __device__ __forceinline__ void deinterleave_staged(uint8_t *buf, uint32_t n, ui
     __threadfence_block(); __builtin_amdgcn_wave_barrier();
 }
 
-template <bool WITH_RS, bool SOFT>
+// SB (fxrx_config.soft_block): a block code (not Reed-Solomon) in a stage that decodes from soft values uses its soft-input decoder
+template <bool WITH_RS, bool SOFT, bool SB = false>
 __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob *jobs, const uint32_t *job_idx, const uint8_t *hard, uint8_t *bufA,
                                           uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res,
                                           const FxTables *T, uint8_t *X)
@@ -3254,6 +3490,7 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
         bool still_soft = false;
         if (pc1) viterbi27<2>(pc1, job.l0, S, B, dw_arena + job.dw_off, A, lane, nullptr);
         else if (job.fec1 == FX_FEC_NONE) still_soft = true;
+        else if (SB && sb_code(job.fec1)) block_fec_decode_soft(job.fec1, job.l0, S, B, T, lane);
         else {
             soft_to_hard_wave(S, A, job.l1, lane);
             __threadfence_block(); __builtin_amdgcn_wave_barrier();
@@ -3265,6 +3502,7 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
             deinterleave_soft_wave(S, job.l0, lane);
             FX_STAMP(3);
             if (pc0) viterbi27<2>(pc0, job.k, S, A, dw_arena + job.dw_off, B, lane, res ? &res[jf].stamp[6] : nullptr);
+            else if (SB && sb_code(job.fec0)) block_fec_decode_soft(job.fec0, job.k, S, A, T, lane);
             else {
                 soft_to_hard_wave(S, B, job.l0, lane);
                 __threadfence_block(); __builtin_amdgcn_wave_barrier();
@@ -3338,6 +3576,30 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
     }
 }
 
+// the soft-block variant (fxrx_config.soft_block): fx_paydec_kernel<WITH_RS, true> with soft-input block decoders, in kernels of
+// its own so that the default instances keep their code
+template <bool WITH_RS>
+__global__ __launch_bounds__(WITH_RS ? DEC_THREADS : DEC_THREADS * DEC_MAX_WAVES)
+void fx_paydec_sb_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA,
+                         uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T,
+                         FxBlockHdr *fallback_host)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t Xs[WITH_RS ? 16 : DEC_LDS];
+    uint8_t *X = (!WITH_RS && blockDim.x == 64) ? Xs : nullptr;
+    const uint32_t njobs = WITH_RS ? hdr->n_dec_rs : (fallback_host ? hdr->n_vb_fallback : hdr->n_dec_plain);
+    const uint32_t wpg = blockDim.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const uint32_t ji0 = __builtin_amdgcn_readfirstlane(first_wave + blockIdx.x * wpg + (threadIdx.x >> 6));
+    if (ji0 >= njobs) return;
+    __builtin_amdgcn_s_setprio(2);
+    if constexpr (WITH_RS) {
+        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, true, true>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
+    } else {
+        dec_frame<false, true, true>(ji0, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
+    }
+}
+
+// soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input block decoders (fx_paydec_sb_kernel)
 extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host)
@@ -3346,9 +3608,33 @@ extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wav
     const unsigned w = with_rs ? 1u : (waves_per_wg < 1u ? 1u : (waves_per_wg > DEC_MAX_WAVES ? DEC_MAX_WAVES : waves_per_wg));
     const dim3 grid((grid_waves + w - 1) / w), block(DEC_THREADS * w);
 #define FX_DEC_LAUNCH(RS, SF) hipLaunchKernelGGL((fx_paydec_kernel<RS, SF>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
-    if (with_rs) { if (soft) FX_DEC_LAUNCH(true, true); else FX_DEC_LAUNCH(true, false); }
+#define FX_DEC_SB_LAUNCH(RS) hipLaunchKernelGGL((fx_paydec_sb_kernel<RS>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
+    if (soft == 2) { if (with_rs) FX_DEC_SB_LAUNCH(true); else FX_DEC_SB_LAUNCH(false); }
+    else if (with_rs) { if (soft) FX_DEC_LAUNCH(true, true); else FX_DEC_LAUNCH(true, false); }
     else { if (soft) FX_DEC_LAUNCH(false, true); else FX_DEC_LAUNCH(false, false); }
+#undef FX_DEC_SB_LAUNCH
 #undef FX_DEC_LAUNCH
+    return hipGetLastError();
+}
+
+// tests (fxrx_debug_block_decode): the decode kernel's block decoders on `count` crafted packets of n message bytes, one wave
+// per packet.  SOFT: 8 fec_enc_len(fs, n) soft values per packet (codeword bit order), else the fec_enc_len(fs, n) coded bytes.
+template <bool SOFT>
+__global__ __launch_bounds__(DEC_THREADS)
+void fx_blkdec_kernel(unsigned fs, uint32_t n, uint32_t count, const uint8_t *in, uint8_t *out, const FxTables *T)
+{
+    const uint32_t p = blockIdx.x;
+    if (p >= count) return;
+    const size_t el = fec_enc_len(fs, n);
+    if constexpr (SOFT) block_fec_decode_soft(fs, n, in + 8 * el * p, out + (size_t)n * p, T, threadIdx.x);
+    else block_fec_decode<false>(fs, n, in + el * p, out + (size_t)n * p, T, threadIdx.x);
+}
+
+extern "C" hipError_t fx_launch_blkdec(int soft, unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T)
+{
+    if (count == 0) return hipSuccess;
+    if (soft) hipLaunchKernelGGL(fx_blkdec_kernel<true>, dim3(count), dim3(DEC_THREADS), 0, st, fs, n, count, in, out, T);
+    else hipLaunchKernelGGL(fx_blkdec_kernel<false>, dim3(count), dim3(DEC_THREADS), 0, st, fs, n, count, in, out, T);
     return hipGetLastError();
 }
 

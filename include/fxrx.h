@@ -80,6 +80,9 @@ void fxrx_sync_set_block(flexframesync q, unsigned int samples);
 void fxrx_sync_set_threshold(flexframesync q, float threshold);
 void fxrx_sync_set_equalizer(flexframesync q, int on);   /* re-creates the context like fxrx_sync_set_threshold */
 void fxrx_sync_set_soft(flexframesync q, int on);        /* likewise: soft-decision payload decoding */
+/* soft-input block decoders (fxrx_config.soft_block), in force while soft payload decoding is on.  Re-creates the context; returns 0,
+ * or -1 if that failed, in which case the previous setting stays */
+int  fxrx_sync_set_soft_block(flexframesync q, int on);
 unsigned int fxrx_sync_pending(flexframesync q);     /* completed frames not yet delivered */
 /* the liquid signatures return void: when a block fails on the GPU its samples (and those of the blocks in flight with it) are
  * dropped -- never fed twice --, the synchroniser restarts freshly reset behind the gap, the text stays in fxrx_last_error(),
@@ -154,6 +157,13 @@ typedef struct {
                                     channel picks the maximum-likelihood codeword of every 8 soft values; SECDED(72,64) and CRC-32 follow as
                                     before.  The soft rule is this project's, not pinned to liquid's demapper.  Flex_rx mode only
                                     (fxrx_create fails with FXRX_ERR_ARG in detector mode).  0 (default): hard decisions */
+    int          soft_block;     /* 1: a block code (Hamming, Golay, SECDED; not Reed-Solomon) in a stage that decodes from soft values -- fec1,
+                                    or fec0 when fec1 is none -- decodes from them too, instead of from their hard decisions: Hamming(7,4) /
+                                    (8,4) / (12,8) by exhaustive maximum likelihood (least cost sum_b (c_b ? 255 - s_b : s_b), ties to the
+                                    smallest message), Golay(24,12) and SECDED by Chase-4 over the hard decoder (the four least reliable
+                                    positions flipped in all 16 patterns, the cheapest re-encoded success, ties to the smallest pattern).
+                                    These rules are this project's, not pinned to liquid's fec_decode_soft.  Needs soft_decision = 1 and
+                                    flex_rx mode (fxrx_create fails with FXRX_ERR_ARG otherwise).  0 (default): hard decisions there */
 } fxrx_config;
 
 typedef struct {
@@ -223,6 +233,11 @@ int fxrx_debug_fail(fxrx_ctx *c, unsigned int submits, unsigned int collects);
  * Writes 20 decoded bytes per header to out20 and the CRC-32 verdict (1 / 0) to valid[i].  Synchronous, on the current HIP device;
  * returns 0 or FXRX_ERR_* */
 int fxrx_debug_header_decode(int soft, const uint8_t *in, unsigned int n, uint8_t *out20, int *valid);
+/* tests: run the payload decoder's block decoder for `fec` (Hamming, Golay or SECDED), soft-input (soft != 0) or hard, on the GPU over
+ * `count` packets of n message bytes given in host memory.  soft != 0: `in` holds 8 fec_enc_len(fec, n) soft values per packet in codeword
+ * bit order (after the stage's de-interleaver); soft == 0: the fec_enc_len(fec, n) coded bytes.  Writes n bytes per packet to out.
+ * Synchronous, on the current HIP device; returns 0 or FXRX_ERR_* */
+int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out);
 /* diagnostic builds (-DFX_STAMPS) only: shader-clock deltas of the decode phases of payload job i */
 int fxrx_debug_stamps(const fxrx_ctx *c, unsigned int i, uint32_t out[8]);
 int fxrx_debug_chain_stamps(const fxrx_ctx *c, uint32_t out[8]);  /* chain kernel phase clocks (stream 0) of the last collected block */
