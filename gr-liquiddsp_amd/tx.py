@@ -104,7 +104,8 @@ def synth_streams_device(n_streams, n_samples, first_stream_id=0, props=None, pa
     """n_streams DISTINCT synthetic IQ streams of n_samples each, generated on the GPU (fxtx_generate + fxtx_channel) straight
     into one device tensor of shape (n_streams, n_samples), complex64 -- the SURVEY 8(d) workload without the host ever
     holding a stream: frames back to back with `gap` zero samples, per-stream payload bytes MT19937(0x5EED + id), per-stream
-    channel draws MT19937(0xC0FFEE + id): CFO ~ U(-0.05, 0.05) rad/sample, phase ~ U(-pi, pi), delay ~ U(-0.5, 0.5) sample,
+    channel draws MT19937(0xC0FFEE + id): CFO ~ U(-0.05, 0.05) rad/sample, phase ~ U(-pi, pi), delay ~ U(-0.5, 0.5) sample
+    (the pulse's dt, liquid's firdes convention: an advance -- the receiver reports tau ~ -delay),
     AWGN at Es/N0 = snr_db from the device's counter-based generator (seed = id).  props(stream_id) -> dict with any of
     mod, fec0, fec1, check, payload_len, snr_db (per-stream frame properties: the mod/FEC sweep of BASELINE config 5).
     Returns (tensor, injected) with injected[s] = [(start sample, payload bytes), ...]."""
@@ -147,7 +148,8 @@ def synth_stream(n_samples, stream_id=0, mod=2, fec0=11, fec1=1, check=CRC_24, p
     """One synthetic IQ stream of exactly n_samples samples.
 
     Payload bytes: MT19937(0x5EED + stream_id); channel draws: MT19937(0xC0FFEE + stream_id):
-    CFO ~ U(-0.05, 0.05) rad/sample, phase ~ U(-pi, pi), delay ~ U(-0.5, 0.5) sample, AWGN with
+    CFO ~ U(-0.05, 0.05) rad/sample, phase ~ U(-pi, pi), delay ~ U(-0.5, 0.5) sample (the pulse's dt, liquid's
+    firdes convention: an advance -- the frame arrives `delay` samples early, the receiver reports tau ~ -delay), AWGN with
     sigma^2 = 10^(-snr/10) per complex sample (unit-power signal), as in BASELINE.md section 3.
     Returns (iq complex64, list of (start_index, payload bytes) of frames that fit entirely)."""
     prng = np.random.RandomState((0x5EED + stream_id) & 0x7FFFFFFF)

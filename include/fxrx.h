@@ -128,7 +128,9 @@ int          flexframegen_assemble(flexframegen q, const unsigned char *header, 
                                    unsigned int payload_len);
 unsigned int flexframegen_getframelen(flexframegen q);
 int          flexframegen_write_samples(flexframegen q, fx_complex *buffer, unsigned int buffer_len);
-/* extension: design the pulse with a fractional-sample delay (channel emulation in tests/bench) */
+/* extension: design the pulse with a fractional-sample offset dt (channel emulation in tests/bench).  liquid's firdes
+ * convention, tap i at t = i - (n-1)/2 + dt: dt is an ADVANCE -- the frame arrives dt samples early, the receiver's
+ * start + tau comes out dt lower (tau ~ -dt; tests/test_ref_detect.py pins the sign). */
 void         fxrx_gen_set_delay(flexframegen q, float dt);
 
 /* ------------------------------------------------------------------------------------------
@@ -300,7 +302,7 @@ typedef struct {
     const unsigned char *header;        /* 14 user bytes, or NULL for zeros */
     const unsigned char *payload;       /* payload_len bytes (host memory) */
     unsigned int        payload_len;    /* 0 .. 65535 */
-    float               dt;             /* fractional-sample delay the pulse is designed with (0 = none) */
+    float               dt;             /* fractional-sample offset the pulse is designed with (0 = none): an advance, tau ~ -dt */
     unsigned long long  out_offset;     /* first sample of the frame in the output buffer */
 } fxtx_frame;
 fxtx_ctx    *fxtx_create(int device);                        /* NULL + fxrx_last_error() without a usable GPU */
