@@ -87,7 +87,10 @@ EXPORTS = [
     "fxtx_create", "fxtx_destroy", "fxtx_frame_len", "fxtx_generate",
     "fxtx_apply_channel", "fxrx_set_timing", "fxrx_debug_block_times", "fxrx_ready", "fxrx_inflight", "fxrx_debug_fail", "fxrx_pinned_alloc", "fxrx_pinned_free", "fxrx_sync_context",
     "fxrx_debug_header_decode", "fxrx_debug_block_decode", "fxrx_sync_set_soft_block",
+    "fxrx_iq_sample_bytes", "fxrx_set_iq_scale", "fxrx_submit_fmt", "fxrx_process_fmt", "fxrx_iq_convert_host", "fxtx_quantize",
 ]
+
+IQ_FC32, IQ_SC16, IQ_SC8 = 0, 1, 2          # FXRX_IQ_*
 
 
 class DropinStats(C.Structure):            # dropin_stats of csrc/blocks/dropin_feed.cpp
@@ -165,6 +168,13 @@ def lib():
     L.fxrx_submit.restype = C.c_int
     L.fxrx_submit.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_int]
     L.fxrx_collect.restype = C.c_int; L.fxrx_collect.argtypes = [C.c_void_p]
+    for f in (L.fxrx_submit_fmt, L.fxrx_process_fmt):
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_int, C.c_int]
+    L.fxrx_iq_sample_bytes.restype = C.c_uint; L.fxrx_iq_sample_bytes.argtypes = [C.c_int]
+    L.fxrx_set_iq_scale.restype = C.c_int; L.fxrx_set_iq_scale.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    L.fxrx_iq_convert_host.restype = C.c_int; L.fxrx_iq_convert_host.argtypes = [C.c_int, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.fxtx_quantize.restype = C.c_int
+    L.fxtx_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_int, C.c_float, C.POINTER(C.c_ulonglong)]
     L.fxrx_set_depth.restype = C.c_int; L.fxrx_set_depth.argtypes = [C.c_void_p, C.c_uint]
     L.fxrx_set_timing.restype = C.c_int; L.fxrx_set_timing.argtypes = [C.c_void_p, C.c_int]
     L.fxrx_debug_block_times.restype = C.c_int; L.fxrx_debug_block_times.argtypes = [C.c_void_p, C.POINTER(C.c_double * 4)]

@@ -80,6 +80,7 @@ extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wav
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host);
 extern "C" hipError_t fx_launch_symcopy(unsigned grid, hipStream_t st, const FxBlockHdr *hdr, const float2 *sym, float2 *host);
 extern "C" hipError_t fx_launch_upload(hipStream_t st, const void *src, void *dst, size_t bytes, unsigned n_cus);
+extern "C" hipError_t fx_launch_ingest(hipStream_t st, int fmt, const void *src, float2 *dst, size_t n, float scale, unsigned n_cus);   // fx_ingest.hip
 extern "C" hipError_t fx_launch_copy_u32(hipStream_t st, const uint32_t *src, uint32_t *dst);
 extern "C" hipError_t fx_launch_softdemod(unsigned grid, hipStream_t st, const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr,
                                           const float2 *framesyms, const uint8_t *hard, uint8_t *soft_arena, const FxTables *T);
@@ -127,16 +128,18 @@ template <class T> struct PinBuf {
 };
 
 constexpr size_t kUploadKernelMax = 64u << 20;      // host blocks up to this size are uploaded by fx_upload_kernel when their memory is page-locked
-// is p page-locked host memory the device can read, and at which address?
-static bool pinned_device_ptr(const void *p, const void **dev)
+// is p page-locked host memory the device can read, and at which address?  (align_mask: float IQ is fetched in 8-byte pieces;
+// integer IQ may sit at any multiple of its sample size: 0)
+static bool pinned_device_ptr(const void *p, const void **dev, uintptr_t align_mask = 7u)
 {
-    if (!p || (reinterpret_cast<uintptr_t>(p) & 7u)) return false;
+    if (!p || (reinterpret_cast<uintptr_t>(p) & align_mask)) return false;
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }     // (pageable memory: not an error here)
     if (a.type != hipMemoryTypeHost || !a.devicePointer) return false;
     *dev = a.devicePointer;
     return true;
 }
+inline unsigned iq_sample_bytes(int fmt) { return fmt == FXRX_IQ_FC32 ? 8u : fmt == FXRX_IQ_SC16 ? 4u : fmt == FXRX_IQ_SC8 ? 2u : 0u; }
 constexpr unsigned kMaxDepth = 32;
 constexpr unsigned kStateRing = kMaxDepth + 3;      // FxStreamState records per stream: one per block in flight and then some
 constexpr uint32_t kFallbackWaves = 32;             // in-chain launch for frames the batch Viterbi path hands back (normally none)
@@ -150,6 +153,9 @@ struct StreamState {
     int64_t carry_bound = 0;                // upper bound of the tail the next block will find (sizes its arenas)
     unsigned noskip_left = 0;               // blocks this stream is still walked with the exact detector on every hop (a skipped hop fired recently; survives a reset)
 };
+
+// integer IQ of one stream, to be converted into the slot's float staging buffer in front of the block's chain
+struct IngestJob { unsigned stream = 0; const void *dev_src = nullptr; const void *host_src = nullptr; uint64_t n = 0; };
 
 // what a block needs to know about a stream at submit time (kept for a replay)
 struct StreamSnap { int64_t tot0 = 0; bool fresh_start = true; int64_t carry_bound = 0; bool noskip = false; };
@@ -167,7 +173,9 @@ struct Slot {
     uint64_t seq = 0;                        // block number since context creation
     // the input, as submitted (kept for a replay)
     std::vector<const float2 *> x; std::vector<uint64_t> n; std::vector<StreamSnap> snap;
-    std::vector<DevBuf<float2>> d_in;        // staging of host inputs
+    std::vector<DevBuf<float2>> d_in;        // staging of host inputs (and of integer inputs, host or device, after their conversion)
+    std::vector<DevBuf<uint8_t>> d_raw;      // integer IQ that reaches the device through the copy engines (pageable memory, very large blocks)
+    std::vector<IngestJob> ingest; int ingest_fmt = FXRX_IQ_FC32; float ingest_scale = 0.0f;   // conversions enqueue_block still has to launch
     // descriptor arena, one upload: [FxWalkJob x NJ | job lists | FxStreamDesc x NS]
     PinBuf<uint8_t> hp_desc; DevBuf<uint8_t> d_desc;
     size_t NJ = 0, n_early = 0, n_late = 0, o_list = 0, o_streams = 0;
@@ -247,6 +255,11 @@ struct fxrx_ctx_s {
     unsigned noskip_left = 0;            // blocks still to be walked with the exact detector on every hop (after a verification failure)
     unsigned debug_fail_submit = 0, debug_fail_collect = 0;   // tests (fxrx_debug_fail): the next n submits / collects report a failure
     uint64_t discarded = 0;              // blocks dropped by a failing fxrx_collect (see discard_inflight)
+    // FXRX_INGEST_KERNEL_MAX: integer IQ in page-locked memory up to this many raw bytes per stream and block is read over the bus by
+    // fx_ingest_kernel itself (no copy call on the host thread); above it copy engine + device pass.  Measured:
+    // the two routes are equal within the spread up to 1 MB raw, and the kernel read is slower from 2 MB on.
+    size_t ingest_kernel_max = 1u << 20;
+    float iq_scale[3] = { 1.0f, 1.0f / 32768.0f, 1.0f / 128.0f };   // fxrx_set_iq_scale, indexed by FXRX_IQ_*
 };
 
 namespace {
@@ -416,6 +429,7 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_WALK_PER_CU")) c->walk_per_cu = (uint32_t)std::min(8, std::max(1, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_VERIFY_PER_CU")) c->verify_per_cu = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_MF_PER_CU")) c->mf_per_cu = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
+    if (const char *e = std::getenv("FXRX_INGEST_KERNEL_MAX")) c->ingest_kernel_max = (size_t)std::max<long long>(0, std::atoll(e));
     if (const char *e = std::getenv("FXRX_PLAN_GRID")) c->plan_grid = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_VB_DEBUG")) c->vb_debug = (uint32_t)std::atoi(e);
     // (a block is at least as long as the warm-up of the next one: 128 steps)
@@ -649,6 +663,17 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl)
 
     const double tp2 = g_prof_on ? prof_now() : 0.0;
     // ---- 3. the chain, front part: walkers and seek verification ----
+    // (integer IQ first: raw copy where the source is not readable from the device, then fx_ingest_kernel into the staging buffer
+    // the descriptors point at.  Launched here, behind every check and reservation of the block; a replay finds the list empty.)
+    if (!sl.ingest.empty()) {
+        std::vector<IngestJob> todo; todo.swap(sl.ingest);
+        const size_t bytes = iq_sample_bytes(sl.ingest_fmt);
+        for (const IngestJob &j : todo) {
+            const void *src = j.dev_src;
+            if (!src) { HIP_OK(hipMemcpyAsync(sl.d_raw[j.stream].p, j.host_src, j.n * bytes, hipMemcpyHostToDevice, st)); src = sl.d_raw[j.stream].p; }
+            HIP_OK(fx_launch_ingest(st, sl.ingest_fmt, src, sl.d_in[j.stream].p, (size_t)j.n, sl.ingest_scale, (unsigned)c->n_cus));
+        }
+    }
     HIP_OK(fx_launch_upload(st, sl.hp_desc.p, sl.d_desc.p, desc_bytes, (unsigned)c->n_cus));     // (descriptors: our own page-locked buffer)
     const int tl = c->timing_level >= 0 ? c->timing_level : (c->depth > 1 ? 0 : 2);      // stage events: see fxrx_set_timing
     sl.timing_level = tl;
@@ -813,15 +838,50 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
     return 0;
 }
 
-int fxrx_submit(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device)
+// Integer IQ of a block: everything that can fail for a reason the caller can mend -- format, alignment, the staging buffers of
+// ALL streams -- before the context is touched or anything is enqueued.  Leaves the list of conversions in the slot.
+static int prepare_ingest(fxrx_ctx_s *c, Slot &sl, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt)
+{
+    const unsigned NS = c->cfg.n_streams;
+    const size_t bytes = iq_sample_bytes(fmt);
+    sl.ingest.clear();
+    for (unsigned s = 0; s < NS; s++)
+        if (n_samples[s] && (!iq[s] || (reinterpret_cast<uintptr_t>(iq[s]) & (bytes - 1)))) {
+            set_err("fxrx_submit_fmt: integer IQ must be aligned to its sample size (sc16: 4 bytes, sc8: 2 bytes)"); return FXRX_ERR_ARG;
+        }
+    if (sl.d_in.size() < NS) sl.d_in.resize(NS);
+    if (sl.d_raw.size() < NS) sl.d_raw.resize(NS);
+    std::vector<IngestJob> jobs;
+    for (unsigned s = 0; s < NS; s++) {
+        const uint64_t nn = n_samples[s];
+        if (sl.d_in[s].reserve(nn + 1)) return FXRX_ERR_HIP;
+        if (!nn) continue;
+        IngestJob j; j.stream = s; j.n = nn;
+        // a device buffer is read in place; a small page-locked block (ingest_kernel_max) is read over the bus by the kernel itself;
+        // everything else goes through the copy engines into the raw staging buffer first, which measured faster from 2 MB raw on
+        if (on_device) j.dev_src = iq[s];
+        else if (!(nn * bytes <= c->ingest_kernel_max && pinned_device_ptr(iq[s], &j.dev_src, 0u))) {
+            j.dev_src = nullptr; j.host_src = iq[s];
+            if (sl.d_raw[s].reserve(nn * bytes + 16)) return FXRX_ERR_HIP;
+        }
+        jobs.push_back(j);
+    }
+    sl.ingest.swap(jobs); sl.ingest_fmt = fmt; sl.ingest_scale = c->iq_scale[fmt];
+    return 0;
+}
+
+static int submit_block(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt)
 {
     if (!c || !iq || !n_samples) { set_err("fxrx_submit: null argument"); return FXRX_ERR_ARG; }
+    if (iq_sample_bytes(fmt) == 0) { set_err("fxrx_submit_fmt: unknown IQ format"); return FXRX_ERR_ARG; }
     if (c->inflight >= c->depth) { set_err("fxrx_submit: pipeline full, call fxrx_collect first"); return FXRX_ERR_STATE; }
     HIP_OK(hipSetDevice(c->cfg.device));
     const auto t_enter = std::chrono::steady_clock::now();
     const unsigned NS = c->cfg.n_streams;
     const unsigned nslots = c->depth + 1;
     Slot &sl = *c->slots[c->head];
+    sl.ingest.clear();
+    if (fmt != FXRX_IQ_FC32) { const int r = prepare_ingest(c, sl, iq, n_samples, on_device, fmt); if (r) return r; }
     sl.out.clear(); sl.timing = fxrx_timing{};
     sl.kept_hops = sl.kept_cheap = sl.kept_vhops = sl.kept_vfail = sl.kept_repairs = 0;
     const unsigned noskip_before = c->noskip_left;
@@ -839,7 +899,8 @@ int fxrx_submit(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, i
         StreamState &S = c->st[s];
         const uint64_t nn = n_samples[s];
         total_new += nn;
-        if (on_device) sl.x[s] = (const float2 *)iq[s];
+        if (fmt != FXRX_IQ_FC32) sl.x[s] = sl.d_in[s].p;            // (prepare_ingest: converted into the staging buffer by the block's first kernels)
+        else if (on_device) sl.x[s] = (const float2 *)iq[s];
         else {
             if (sl.d_in[s].reserve(nn + 1)) return FXRX_ERR_HIP;
             if (nn) {
@@ -870,6 +931,29 @@ int fxrx_submit(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, i
     sl.busy = true;
     c->head = (c->head + 1) % nslots; c->inflight++;
     sl.host_submit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
+    return 0;
+}
+
+int fxrx_submit(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device) { return submit_block(c, iq, n_samples, on_device, FXRX_IQ_FC32); }
+int fxrx_submit_fmt(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt) { return submit_block(c, iq, n_samples, on_device, fmt); }
+
+unsigned int fxrx_iq_sample_bytes(int fmt) { return iq_sample_bytes(fmt); }
+
+int fxrx_set_iq_scale(fxrx_ctx *c, int fmt, float scale)
+{
+    if (!c || (fmt != FXRX_IQ_SC16 && fmt != FXRX_IQ_SC8) || !std::isfinite(scale) || !(scale > 0.0f)) { set_err("fxrx_set_iq_scale: bad argument"); return FXRX_ERR_ARG; }
+    c->iq_scale[fmt] = scale;
+    return 0;
+}
+
+// the definition of an integer sample: one exact conversion, one binary32 multiply (this file is compiled with -ffp-contract=off)
+int fxrx_iq_convert_host(int fmt, float scale, const void *in, uint64_t n_samples, float *out_re_im)
+{
+    if (iq_sample_bytes(fmt) == 0 || (n_samples && (!in || !out_re_im))) { set_err("fxrx_iq_convert_host: bad argument"); return FXRX_ERR_ARG; }
+    const uint64_t nc = 2 * n_samples;
+    if (fmt == FXRX_IQ_FC32) { if (nc) std::memcpy(out_re_im, in, nc * sizeof(float)); }
+    else if (fmt == FXRX_IQ_SC16) { const int16_t *q = static_cast<const int16_t *>(in); for (uint64_t i = 0; i < nc; i++) out_re_im[i] = (float)q[i] * scale; }
+    else { const int8_t *q = static_cast<const int8_t *>(in); for (uint64_t i = 0; i < nc; i++) out_re_im[i] = (float)q[i] * scale; }
     return 0;
 }
 
@@ -1260,14 +1344,15 @@ static int collect_block(fxrx_ctx_s *c)
     return (int)sl.out.size();
 }
 
-int fxrx_process(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device)
+int fxrx_process_fmt(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt)
 {
     if (!c) return FXRX_ERR_ARG;
     while (c->inflight) { int r = fxrx_collect(c); if (r < 0) return r; }      // drain anything a caller left in flight
-    int r = fxrx_submit(c, iq, n_samples, on_device);
+    int r = submit_block(c, iq, n_samples, on_device, fmt);
     if (r < 0) return r;
     return fxrx_collect(c);
 }
+int fxrx_process(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device) { return fxrx_process_fmt(c, iq, n_samples, on_device, FXRX_IQ_FC32); }
 
 // diagnostic builds (-DFX_STAMPS): walker phase clocks of the last collected block, summed over its walk jobs / of the slowest job
 static int walk_stamps(const fxrx_ctx *c, uint64_t sum[4], uint64_t maxjob[8])

@@ -26,6 +26,8 @@ extern "C" hipError_t fx_launch_txgen(unsigned ntiles, hipStream_t st, const FxT
 extern "C" hipError_t fx_launch_txenc(unsigned njobs, hipStream_t st, const FxTxEncJob *jobs, const uint8_t *pay, const uint32_t *perm_arena,
                                       uint8_t *bufA, uint8_t *bufB, uint8_t *pay_idx, const FxTxTables *T);
 extern "C" hipError_t fx_launch_channel(hipStream_t st, float2 *x, unsigned n_streams, unsigned long long n_per_stream, const FxChannel *chs, const FxTxTables *T);
+extern "C" hipError_t fx_launch_quantize(hipStream_t st, int fmt, const float2 *in, void *out, size_t n, float inv_scale, unsigned long long *saturated,
+                                         unsigned n_cus);          // fx_ingest.hip
 extern "C" void fxrx_set_error(const char *msg);       // fx_host.cpp: thread-local message behind fxrx_last_error()
 
 namespace {
@@ -42,6 +44,7 @@ struct fxtx_ctx_s {
     Dev<FxTxTables> d_tab; Dev<uint8_t> d_idx; Dev<FxTxJob> d_jobs; Dev<uint32_t> d_tiles;
     // packet encoder on the GPU: payload bytes, scratch, interleaver gather tables (one per coded length, append-only)
     Dev<uint8_t> d_pay, d_bufA, d_bufB; Dev<FxTxEncJob> d_ejobs; Dev<uint32_t> d_perm; Dev<FxChannel> d_chan;
+    Dev<unsigned long long> d_sat; int n_cus = 256;      // fxtx_quantize: count of clamped components
     std::map<uint32_t, uint32_t> perm_off; std::vector<uint32_t> perm_host; size_t perm_uploaded = 0;
     bool host_encode_only = false;       // FXTX_HOST_ENCODE=1: every frame's packet encoding on the host
 };
@@ -59,6 +62,7 @@ fxtx_ctx *fxtx_create(int device)
     const fx::HostTables &H = fx::host_tables();
     const fx::BlockCodes &B = fx::block_codes();
     if (const char *e = std::getenv("FXTX_HOST_ENCODE")) c->host_encode_only = std::atoi(e) != 0;
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cus = prop.multiProcessorCount; }
     std::unique_ptr<FxTxTables> t(new FxTxTables);
     std::memset(t.get(), 0, sizeof(FxTxTables));
     for (int i = 0; i < 1024; i++) t->sc[i] = make_float2(H.sc[i].re, H.sc[i].im);
@@ -223,6 +227,27 @@ int fxtx_apply_channel(fxtx_ctx *c, void *iq_device, unsigned int n_streams, uns
     ok = ok && fx_launch_channel(c->stream, (float2 *)iq_device, n_streams, n_per_stream, c->d_chan.p, c->d_tab.p) == hipSuccess;
     ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
     if (!ok) { fxrx_set_error(std::string("fxtx_apply_channel: ").append(hipGetErrorString(hipGetLastError())).c_str()); return FXRX_ERR_HIP; }
+    return 0;
+}
+
+// Float IQ -> integer IQ (fx_quantize_kernel): q = saturate(rintf(x * inv_scale)) per component, NaN -> 0.  Synchronous.
+int fxtx_quantize(fxtx_ctx *c, const void *iq_f32_device, void *out_device, unsigned long long n_samples, int fmt, float inv_scale,
+                  unsigned long long *saturated)
+{
+    const size_t bytes = fmt == FXRX_IQ_SC16 ? 4u : fmt == FXRX_IQ_SC8 ? 2u : 0u;
+    if (!c || bytes == 0 || (n_samples && (!iq_f32_device || !out_device))) { fxrx_set_error("fxtx_quantize: bad argument"); return FXRX_ERR_ARG; }
+    const uintptr_t a = reinterpret_cast<uintptr_t>(iq_f32_device), b = reinterpret_cast<uintptr_t>(out_device);
+    if (n_samples && ((a & 7u) || (b & (bytes - 1)))) { fxrx_set_error("fxtx_quantize: misaligned pointer"); return FXRX_ERR_ARG; }
+    if (n_samples && a < b + n_samples * bytes && b < a + n_samples * 8ull) { fxrx_set_error("fxtx_quantize: input and output overlap"); return FXRX_ERR_ARG; }
+    if (hipSetDevice(c->device) != hipSuccess) { fxrx_set_error("hipSetDevice failed"); return FXRX_ERR_HIP; }
+    unsigned long long sat = 0;
+    bool ok = c->d_sat.reserve(1);
+    ok = ok && hipMemsetAsync(c->d_sat.p, 0, sizeof(unsigned long long), c->stream) == hipSuccess;
+    ok = ok && fx_launch_quantize(c->stream, fmt, static_cast<const float2 *>(iq_f32_device), out_device, (size_t)n_samples, inv_scale, c->d_sat.p, (unsigned)c->n_cus) == hipSuccess;
+    ok = ok && hipMemcpyAsync(&sat, c->d_sat.p, sizeof sat, hipMemcpyDeviceToHost, c->stream) == hipSuccess;
+    ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+    if (!ok) { fxrx_set_error(std::string("fxtx_quantize: ").append(hipGetErrorString(hipGetLastError())).c_str()); return FXRX_ERR_HIP; }
+    if (saturated) *saturated = sat;
     return 0;
 }
 

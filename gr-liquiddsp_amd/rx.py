@@ -9,6 +9,7 @@ import numpy as np
 from . import _ffi
 
 MODE_FLEX_RX, MODE_DETECTOR = 0, 1
+IQ_FC32, IQ_SC16, IQ_SC8 = _ffi.IQ_FC32, _ffi.IQ_SC16, _ffi.IQ_SC8
 
 
 class RxError(RuntimeError):
@@ -32,6 +33,49 @@ def _frame_to_dict(f, copy_syms):
     return d
 
 
+def _int_iq_format(s):
+    """FXRX_IQ_SC16 / FXRX_IQ_SC8 for an (n, 2) array or tensor of dtype int16 / int8 (SDR-native IQ), else None."""
+    if len(getattr(s, "shape", ())) != 2 or s.shape[1] != 2:
+        return None
+    name = str(s.dtype).replace("torch.", "")
+    return {"int16": IQ_SC16, "int8": IQ_SC8}.get(name)
+
+
+def iq_convert(q, fmt=None, scale=None):
+    """Integer IQ of shape (n, 2) -> complex64 on the host by the library's definition (fxrx_iq_convert_host):
+    re = float(i_re) * scale, im = float(i_im) * scale; scale defaults to 1/32768 (int16) / 1/128 (int8)."""
+    q = np.ascontiguousarray(q)
+    fmt = _int_iq_format(q) if fmt is None else fmt
+    if fmt not in (IQ_SC16, IQ_SC8):
+        raise ValueError("iq_convert: expected an (n, 2) int16 or int8 array")
+    scale = (1.0 / 32768.0 if fmt == IQ_SC16 else 1.0 / 128.0) if scale is None else scale
+    out = np.empty(len(q), np.complex64)
+    if _ffi.lib().fxrx_iq_convert_host(fmt, C.c_float(scale), q.ctypes.data, len(q), out.ctypes.data) != 0:
+        raise RxError("fxrx_iq_convert_host failed: %s" % _ffi.lib().fxrx_last_error().decode())
+    return out
+
+
+def marshal_streams(streams):
+    """What process() / submit() hand to the C ABI for a list of streams: (keep-alive objects, addresses, sample counts,
+    on_device, FXRX_IQ_* format).  (n, 2) int16 / int8 arrays (host) or tensors (device) select sc16 / sc8 -- all streams of a
+    block share the format --; everything else goes the float way: complex64 arrays or tensors."""
+    on_device = hasattr(streams[0], "data_ptr")
+    fmt = _int_iq_format(streams[0])
+    if fmt is not None:
+        if any(_int_iq_format(s) != fmt or hasattr(s, "data_ptr") != on_device for s in streams):
+            raise ValueError("all streams of a block must share one IQ format")
+        if on_device:
+            keep = [s.contiguous() for s in streams]
+            return keep, [s.data_ptr() for s in keep], [s.shape[0] for s in keep], True, fmt
+        keep = [np.ascontiguousarray(s) for s in streams]
+        return keep, [s.ctypes.data for s in keep], [len(s) for s in keep], False, fmt
+    if on_device:
+        keep = [s.contiguous() for s in streams]
+        return keep, [s.data_ptr() for s in keep], [s.numel() for s in keep], True, IQ_FC32
+    keep = [np.ascontiguousarray(s, dtype=np.complex64) for s in streams]
+    return keep, [s.ctypes.data for s in keep], [len(s) for s in keep], False, IQ_FC32
+
+
 class RxContext:
     """fxrx_ctx wrapper.  Raises RxError when the library or a HIP device is missing (no fallback)."""
 
@@ -45,6 +89,7 @@ class RxContext:
             raise RxError("fxrx_create failed: %s" % self.L.fxrx_last_error().decode())
         self.n_streams, self.mode, self.want_framesyms = n_streams, mode, want_framesyms
         self._keep = None
+        self._inflight_keep = []
 
     def close(self):
         if getattr(self, "h", None):
@@ -56,15 +101,23 @@ class RxContext:
     def reset(self):
         self.L.fxrx_reset(self.h)
 
-    def process_raw(self, ptrs, counts, on_device):
-        """ptrs/counts: one address and sample count per stream.  Returns number of results."""
+    def process_raw(self, ptrs, counts, on_device, fmt=0):
+        """ptrs/counts: one address and sample count per stream; fmt: FXRX_IQ_* of the samples.  Returns number of results."""
         n = self.n_streams
         a = (C.c_void_p * n)(*ptrs)
         c = (C.c_uint64 * n)(*counts)
-        r = self.L.fxrx_process(self.h, a, c, 1 if on_device else 0)
+        if fmt == IQ_FC32:
+            r = self.L.fxrx_process(self.h, a, c, 1 if on_device else 0)
+        else:
+            r = self.L.fxrx_process_fmt(self.h, a, c, 1 if on_device else 0, int(fmt))
         if r < 0:
             raise RxError("fxrx_process failed (%d): %s" % (r, self.L.fxrx_last_error().decode()))
         return r
+
+    def set_iq_scale(self, fmt, scale):
+        """Scale of an integer IQ format (default 1/32768 for sc16, 1/128 for sc8), from the next submit on."""
+        if self.L.fxrx_set_iq_scale(self.h, int(fmt), C.c_float(scale)) != 0:
+            raise RxError("fxrx_set_iq_scale: %s" % self.L.fxrx_last_error().decode())
 
     def set_depth(self, depth):
         """Allow up to `depth` blocks in flight (submit/collect pipelining over three HIP streams)."""
@@ -76,11 +129,14 @@ class RxContext:
         if self.L.fxrx_set_timing(self.h, int(level)) != 0:
             raise RxError("fxrx_set_timing: bad level")
 
-    def submit_raw(self, ptrs, counts, on_device):
+    def submit_raw(self, ptrs, counts, on_device, fmt=0):
         n = self.n_streams
         a = (C.c_void_p * n)(*ptrs)
         c = (C.c_uint64 * n)(*counts)
-        r = self.L.fxrx_submit(self.h, a, c, 1 if on_device else 0)
+        if fmt == IQ_FC32:
+            r = self.L.fxrx_submit(self.h, a, c, 1 if on_device else 0)
+        else:
+            r = self.L.fxrx_submit_fmt(self.h, a, c, 1 if on_device else 0, int(fmt))
         if r < 0:
             raise RxError("fxrx_submit failed (%d): %s" % (r, self.L.fxrx_last_error().decode()))
 
@@ -91,22 +147,34 @@ class RxContext:
         return r
 
     def process(self, streams):
-        """streams: list (len n_streams) of numpy complex64 arrays (host) or torch complex64 CUDA tensors."""
+        """streams: list (len n_streams) of numpy complex64 arrays (host) or torch complex64 CUDA tensors -- or, for SDR-native
+        integer IQ, of (n, 2) int16 / int8 numpy arrays (host) or torch tensors (device): sc16 / sc8, converted on the device."""
         if len(streams) != self.n_streams:
             raise ValueError("expected %d streams" % self.n_streams)
-        on_device = hasattr(streams[0], "data_ptr")
+        keep, ptrs, counts, on_device, fmt = marshal_streams(streams)
         if on_device:
-            keep = [s.contiguous() for s in streams]
-            ptrs = [s.data_ptr() for s in keep]
-            counts = [s.numel() for s in keep]
             import torch
             torch.cuda.synchronize()        # inputs produced on torch's stream must be complete
-        else:
-            keep = [np.ascontiguousarray(s, dtype=np.complex64) for s in streams]
-            ptrs = [s.ctypes.data for s in keep]
-            counts = [len(s) for s in keep]
         self._keep = keep
-        return self.results(self.process_raw(ptrs, counts, on_device))
+        return self.results(self.process_raw(ptrs, counts, on_device, fmt))
+
+    def submit(self, streams):
+        """Pipelined form of process(): enqueue one block (same inputs as process()); collect() returns the oldest block's
+        results.  The inputs of up to `depth` blocks in flight are kept alive here."""
+        if len(streams) != self.n_streams:
+            raise ValueError("expected %d streams" % self.n_streams)
+        keep, ptrs, counts, on_device, fmt = marshal_streams(streams)
+        if on_device:
+            import torch
+            torch.cuda.synchronize()
+        self.submit_raw(ptrs, counts, on_device, fmt)
+        self._inflight_keep.append(keep)
+
+    def collect(self):
+        n = self.collect_raw()
+        if self._inflight_keep:
+            self._keep = self._inflight_keep.pop(0)
+        return self.results(n)
 
     def results(self, n):
         out = []

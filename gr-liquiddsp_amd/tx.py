@@ -91,12 +91,38 @@ class TxContext:
         if r != 0:
             raise RuntimeError("fxtx_apply_channel: " + self.L.fxrx_last_error().decode())
 
+    def quantize(self, iq, fmt, inv_scale):
+        """Device complex64 tensor -> (n, 2) int16 (fmt 1, sc16) / int8 (fmt 2, sc8) device tensor by fxtx_quantize:
+        q = saturate(rint(x * inv_scale)) per component.  Returns (tensor, number of clamped components)."""
+        import torch
+        if fmt not in (_ffi.IQ_SC16, _ffi.IQ_SC8):
+            raise ValueError("quantize: fmt must be IQ_SC16 or IQ_SC8")
+        iq = iq.contiguous()
+        out = torch.empty((iq.numel(), 2), dtype=torch.int16 if fmt == _ffi.IQ_SC16 else torch.int8, device=iq.device)
+        torch.cuda.synchronize(iq.device)
+        sat = C.c_ulonglong(0)
+        r = self.L.fxtx_quantize(self.h, C.c_void_p(iq.data_ptr()), C.c_void_p(out.data_ptr()), iq.numel(), int(fmt), C.c_float(inv_scale), C.byref(sat))
+        if r != 0:
+            raise RuntimeError("fxtx_quantize: " + self.L.fxrx_last_error().decode())
+        return out, int(sat.value)
+
     def close(self):
         if getattr(self, "h", None):
             self.L.fxtx_destroy(self.h)
             self.h = None
 
     __del__ = close
+
+
+def quantize(iq, fmt, inv_scale, tx=None):
+    """quantize(device_tensor, fmt, inv_scale) -> (tensor, saturated): TxContext.quantize on a context of the tensor's device."""
+    own = tx is None
+    tx = TxContext(iq.device.index or 0) if own else tx
+    try:
+        return tx.quantize(iq, fmt, inv_scale)
+    finally:
+        if own:
+            tx.close()
 
 
 def synth_streams_device(n_streams, n_samples, first_stream_id=0, props=None, payload_len=1024, gap=256, snr_db=20.0, device=0, tx=None,

@@ -224,6 +224,29 @@ int fxrx_collect(fxrx_ctx *c);
  * stood.  A failing fxrx_collect drops every block in flight (their samples are never searched) and restarts all streams
  * from a freshly reset synchroniser with the next block submitted; sample positions keep counting.  Either way the context
  * stays usable -- unless the HIP runtime itself reports errors, which every later call will report again. */
+/* Integer IQ (SDR-native samples).  A block may be handed over as interleaved 16-bit (sc16) or 8-bit (sc8) signed integer
+ * (re, im) pairs instead of float32; the conversion happens on the device, inside the block's upload: host memory crosses the
+ * bus raw, at 4 / 2 bytes a sample (asynchronously when it is page-locked), into a staging buffer of the block and is converted
+ * behind the copy; a device buffer is read in place; a small page-locked block (up to FXRX_INGEST_KERNEL_MAX raw bytes per
+ * stream, an environment variable, default 1 MiB) is read over the bus by the conversion kernel itself, which saves the host the
+ * copy call.  Measured: up to 1 MB raw the two routes are equally fast, from 2 MB on the copy is faster.
+ * Definition of a sample: re = (float)i_re * scale, im = (float)i_im * scale -- one exact
+ * int -> float conversion and one IEEE binary32 multiply, no contraction -- which is what fxrx_iq_convert_host computes: results
+ * for integer input are identical, field for field and bit for bit, to fxrx_submit on the float array that function produces.
+ * The format is a property of a block, not of the context: the blocks of a continuing stream may change format; all streams of
+ * one block share it.  sc16 samples must be 4-byte aligned, sc8 samples 2-byte aligned (FXRX_ERR_ARG otherwise); any such
+ * alignment and any n_samples work.  fxrx_submit(c, ...) is fxrx_submit_fmt(c, ..., FXRX_IQ_FC32).  Failure semantics as for
+ * fxrx_submit; with an integer format every argument check and reservation is done before anything is enqueued. */
+enum { FXRX_IQ_FC32 = 0, FXRX_IQ_SC16 = 1, FXRX_IQ_SC8 = 2 };
+unsigned int fxrx_iq_sample_bytes(int fmt);                 /* 8, 4, 2; 0 for an unknown fmt (no GPU needed) */
+/* scale of an integer format: default 1/32768 (sc16), 1/128 (sc8).  Must be finite and > 0; applies from the next submit on.
+ * FXRX_IQ_FC32 or an unknown format: FXRX_ERR_ARG */
+int fxrx_set_iq_scale(fxrx_ctx *c, int fmt, float scale);
+int fxrx_submit_fmt(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt);
+int fxrx_process_fmt(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt);
+/* the definition of the conversion, on the host (no GPU needed): n_samples integer pairs at `in` -> 2 n_samples floats at
+ * out_re_im.  FXRX_IQ_FC32 copies.  Returns 0, or FXRX_ERR_ARG for an unknown format or a NULL pointer */
+int fxrx_iq_convert_host(int fmt, float scale, const void *in, uint64_t n_samples, float *out_re_im);
 /* 1: the oldest block in flight has finished (fxrx_collect will not wait), 0: not yet / nothing in flight, < 0: FXRX_ERR_* */
 int fxrx_ready(const fxrx_ctx *c);
 unsigned int fxrx_inflight(const fxrx_ctx *c);
@@ -321,6 +344,14 @@ int          fxtx_generate(fxtx_ctx *c, const fxtx_frame *frames, unsigned int n
 typedef struct { float cfo, phase, gain, sigma; unsigned long long seed; } fxtx_channel;
 int          fxtx_apply_channel(fxtx_ctx *c, void *iq_device, unsigned int n_streams, unsigned long long n_per_stream,
                           const fxtx_channel *ch);
+
+/* Float IQ -> integer IQ on the device (the inverse of the receive side's conversion, for signal sources and tools):
+ * q = saturate(rintf(x * inv_scale)) per component (round half to even; NaN -> 0), to int16 (FXRX_IQ_SC16) or int8 (FXRX_IQ_SC8)
+ * pairs; *saturated (may be NULL) = number of components that were clamped -- what tells a user the gain is wrong.  Synchronous.
+ * in / out are device pointers on the context's device (8-byte / sample-size aligned); they may not overlap.
+ * Returns 0 or FXRX_ERR_*. */
+int          fxtx_quantize(fxtx_ctx *c, const void *iq_f32_device, void *out_device, unsigned long long n_samples,
+                           int fmt, float inv_scale, unsigned long long *saturated);
 
 #ifdef __cplusplus
 }
