@@ -196,6 +196,8 @@ struct FxBlockHdr {                      // device memory, zeroed at submit; mir
     uint32_t hops, hops_cheap, repairs, verify_hops, verify_failures, walk_jobs_run;
     uint32_t vb_ticket;                  // host mirror only: fx_vbfinish_kernel handed frames back to the wave-per-frame decoder (n_vb_fallback on the device says how many)
     uint32_t done;                       // host mirror only: written last
+    uint32_t vb_dirty;                   // host mirror only: fx_vbpre_kernel (early tail) met a frame that needs the trellis kernels; zero from the plan stage
+    uint32_t pad_;
     uint32_t stamp[8];
 };
 

@@ -11,7 +11,7 @@
 //   true walkers of continuing streams  -- fx_walk_kernel; their start state is read from device memory
 //   seek verification (phase 1)         -- the remaining runs
 //   chain                               -- fx_chainfast_kernel: stitch / resume state / carried tail, per stream
-//   plan                                -- fx_plan_kernel + fx_planlists_kernel: payload jobs, work lists, host result records
+//   plan                                -- fx_planfused_kernel (or fx_plan_kernel + fx_planlists_kernel): payload jobs, work lists, host result records
 //   payload MF -> PLL -> packet decode  -- results land in pinned host memory
 //
 // Slow paths, all at fxrx_collect (repair_and_replay, finish_decode): repair rounds (segments walked again in parallel:
@@ -61,16 +61,17 @@ extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, con
 extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
                                      const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap,
                                      uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
-                                     FxBlockHdr *hdr_host, uint32_t *plan_ws);
+                                     FxBlockHdr *hdr_host, uint32_t *plan_ws, int fused);
 extern "C" unsigned fx_plan_ws_words(void);
 extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
-                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on);
+                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on, int early_tail, uint8_t *out, FxOutRec *recs,
+                                      FxBlockHdr *hdr_host);
 extern "C" hipError_t fx_launch_vbitems(unsigned first_item, unsigned n_items, hipStream_t st, const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap,
                                         const FxBlockHdr *hdr, uint8_t *bufA, const uint8_t *bufB, unsigned long long *dwv, uint8_t *vec_arena, uint32_t *vb_st, uint32_t dbg, int packed,
                                         int with_fix);
 extern "C" hipError_t fx_launch_vbfinish(unsigned first_wave, unsigned n_waves, hipStream_t st, const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHdr *hdr,
                                          uint8_t *bufA, uint8_t *bufB, unsigned long long *dwv, const uint8_t *vec_arena, const uint32_t *vb_st, uint32_t *fb_list, uint32_t list_cap,
-                                         uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host);
+                                         uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host, int early_tail);
 extern "C" hipError_t fx_launch_paymf(unsigned grid, int eq, hipStream_t st, const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr,
                                       const FxFrame *chain, float2 *sym_raw, const FxTables *T);
 extern "C" hipError_t fx_launch_paypll(unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs, const uint32_t *pll_list, const FxBlockHdr *hdr,
@@ -142,6 +143,7 @@ static bool pinned_device_ptr(const void *p, const void **dev, uintptr_t align_m
 inline unsigned iq_sample_bytes(int fmt) { return fmt == FXRX_IQ_FC32 ? 8u : fmt == FXRX_IQ_SC16 ? 4u : fmt == FXRX_IQ_SC8 ? 2u : 0u; }
 constexpr unsigned kMaxDepth = 32;
 constexpr unsigned kStateRing = kMaxDepth + 3;      // FxStreamState records per stream: one per block in flight and then some
+constexpr unsigned kTrellisHold = 8;                // blocks that keep the trellis kernels in their chain after a collected block with frames that were not clean
 constexpr uint32_t kFallbackWaves = 32;             // in-chain launch for frames the batch Viterbi path hands back (normally none)
 constexpr uint32_t kRepairCap = 256;                // frame-table slots per stream for walks done by the chain kernel
 
@@ -190,6 +192,8 @@ struct Slot {
     DevBuf<unsigned long long> d_vb_dw;      // its decision words, step-major within the 64 work items of a wave
     DevBuf<uint32_t> d_vb_st;                // traceback states and flags per work item
     uint32_t vb_cap = 0, vb_blk = 0, vb_pre_launched = 0, vb_items_launched = 0, fb_launched = 0;
+    uint32_t vb_fin_launched = 0;            // waves of fx_vbfinish_kernel launched with the chain (0: the trellis kernels were left out)
+    bool vb_early = false;                   // clean frames finish in fx_vbpre_kernel (fxrx_ctx_s.vb_early_tail and the codeword check on)
     uint64_t vb_dw_words = 0, vb_slots_alloc = 128;
     DevBuf<FxPayJob> d_pjobs; DevBuf<FxPayResult> d_pres;
     uint32_t run_cap = 0, chain_cap = 0, mf_cap = 0, frame_slots = 0;
@@ -235,6 +239,12 @@ struct fxrx_ctx_s {
     // section 6) --, so it is only enqueued while blocks keep needing it: for the next 16 blocks after one that did.
     // FXRX_INCHAIN_REPAIR=0: never, 1: while needed (default), 2: always.
     int inchain_repair = 1; unsigned inchain_left = 0;
+    bool plan_fused = true;              // FXRX_PLAN_FUSED=0: the plan stage is two launches even when one workgroup plans the block
+    // FXRX_VB_EARLY_TAIL=0: the tail of clean frames runs in fx_vbfinish_kernel and the trellis kernels are launched with every block.
+    // Otherwise fx_vbpre_kernel finishes clean frames, and the trellis kernels (forward pass, hand-over check, traceback, back part,
+    // fallback decoder: up to five launches a block) join the chain only while frames that need them keep turning up: for the next
+    // kTrellisHold blocks after a collected block that held one.  A block that meets one without them is completed when it is collected.
+    bool vb_early_tail = true; unsigned trellis_left = 0;
     int timing_level = -1;               // stage events per block: -1 auto (all stages one block at a time, none with blocks in flight) | 0 none | 1 the PLL only | 2 all stages
     hipEvent_t ref_event = nullptr; double ref_host_ms = 0.0;   // fxrx_debug_block_times: a common origin of GPU and host clocks
     int debug_walk_twice = 0;            // FXRX_DEBUG_WALK_TWICE: the speculative walkers are launched twice, the stage time is the second launch's (cold-start experiment)
@@ -423,6 +433,8 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_BATCH_VITERBI")) c->batch_viterbi = std::atoi(e) != 0;
     if (const char *e = std::getenv("FXRX_VB_CLEAN")) c->vb_clean = std::atoi(e) != 0;
     if (const char *e = std::getenv("FXRX_INCHAIN_REPAIR")) c->inchain_repair = std::min(2, std::max(0, std::atoi(e)));
+    if (const char *e = std::getenv("FXRX_PLAN_FUSED")) c->plan_fused = std::atoi(e) != 0;
+    if (const char *e = std::getenv("FXRX_VB_EARLY_TAIL")) c->vb_early_tail = std::atoi(e) != 0;
     if (const char *e = std::getenv("FXRX_DEBUG_STOP_AFTER")) c->debug_stop_after = std::atoi(e);
     if (const char *e = std::getenv("FXRX_DEBUG_WALK_TWICE")) c->debug_walk_twice = std::atoi(e);
     if (const char *e = std::getenv("FXRX_TIMING")) c->timing_level = std::min(2, std::max(0, std::atoi(e)));
@@ -762,7 +774,7 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
     // (the plan kernels' workgroups take contiguous ranges of the chain's frames: about 2048 each, from the last block's count)
     HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->frames_hint / 2048 + 1), d_streams, NS, detect ? 1u : 0u, c->cfg.equalizer ? 1u : 0u, sl.vb_blk, sl.d_chain.p,
                           sl.d_chain_count.p, sl.d_stream_base.p, sl.d_pjobs.p, sl.h_recs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.mf_cap, sl.d_pll_list.p, sl.d_dec_list.p, list_cap,
-                          sl.d_vb_items.p, sl.vb_cap, hdr, hdr_pay, sl.h_hdr.p, sl.d_plan_ws.p));
+                          sl.d_vb_items.p, sl.vb_cap, hdr, hdr_pay, sl.h_hdr.p, sl.d_plan_ws.p, c->plan_fused ? 1 : 0));
     const int tl = sl.timing_level;
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[4], st));
     if (c->debug_stop_after == 4) { c->carry_reader[b % 3] = nullptr; HIP_OK(hipEventRecord(sl.ev[8], st)); return 0; }
@@ -811,19 +823,26 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
             sl.vb_pre_launched = c->first_block ? chain_slots : (unsigned)std::min<uint64_t>(chain_slots, c->batch_hint + c->batch_hint / 2 + 64);
             // (two work items per lane once the items fill the chip or other blocks do; one per lane for a lone small block)
             const int vb_packed = (c->depth > 1 || c->vb_items_hint > 64ull * 4ull * (uint64_t)c->n_cus * 3ull / 2ull) ? 1 : 0;
-            sl.vb_items_launched = c->first_block ? sl.vb_cap : (unsigned)std::min<uint64_t>(sl.vb_cap, c->vb_items_hint + c->vb_items_hint / 2 + 1024);
-            HIP_OK(fx_launch_vbpre(0, sl.vb_pre_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0));
+            // (the trellis kernels: always without the early tail; with it, while the traffic has frames for them)
+            sl.vb_early = c->vb_early_tail && c->vb_clean;
+            const bool trellis = !sl.vb_early || c->first_block || c->vb_debug || c->trellis_left > 0;
+            if (c->trellis_left) c->trellis_left--;
+            sl.vb_items_launched = !trellis ? 0u : c->first_block ? sl.vb_cap : (unsigned)std::min<uint64_t>(sl.vb_cap, c->vb_items_hint + c->vb_items_hint / 2 + 1024);
+            sl.vb_fin_launched = trellis ? sl.vb_pre_launched : 0u;
+            HIP_OK(fx_launch_vbpre(0, sl.vb_pre_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0,
+                                   sl.vb_early ? 1 : 0, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p));
             HIP_OK(fx_launch_vbitems(0, sl.vb_items_launched, st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p,
                                      sl.d_vb_st.p, c->vb_debug, vb_packed, (c->first_block || c->vbfix_hint || c->vb_debug) ? 1 : 0));
-            HIP_OK(fx_launch_vbfinish(0, sl.vb_pre_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
-                                      sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p));
+            HIP_OK(fx_launch_vbfinish(0, sl.vb_fin_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
+                                      sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0));
             // frames whose hand-overs could not be verified (a block that ran again and ended differently): the wave-per-frame decoder,
             // launched with the chain only while such frames keep turning up (the count reaches the host either way; what a launch
             // did not cover is decoded when the block is collected)
-            sl.fb_launched = (c->first_block || c->fb_hint || c->vb_debug) ? (uint32_t)std::min<uint64_t>(chain_slots, std::max<uint64_t>(kFallbackWaves, c->fb_hint + c->fb_hint / 2 + 16)) : 0u;
+            sl.fb_launched = trellis && (c->first_block || c->fb_hint || c->vb_debug) ? (uint32_t)std::min<uint64_t>(chain_slots, std::max<uint64_t>(kFallbackWaves, c->fb_hint + c->fb_hint / 2 + 16)) : 0u;
             HIP_OK(fx_launch_paydec(0, 0, 0, sl.fb_launched, 1u, st, sl.d_pjobs.p, sl.d_dec_list.p + 3 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
                                     sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, sl.h_hdr.p));
-        } else sl.vb_pre_launched = sl.vb_items_launched = sl.fb_launched = 0;
+        } else { sl.vb_pre_launched = sl.vb_items_launched = sl.vb_fin_launched = sl.fb_launched = 0; sl.vb_early = false; }
+        sl.timing.trellis_launched = sl.vb_fin_launched ? 1 : 0;
         if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[7], st));
         // (a copy kernel: it knows how many symbols the block really holds)
         if (c->cfg.want_framesyms)
@@ -1102,9 +1121,13 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     }
     const FxBlockHdr &h = *sl.h_hdr.p;
     const bool more_plain = h.n_dec_plain > sl.dec_launched, more_rs = h.n_dec_rs > 0 && sl.rs_launched == 0;   // (the Reed-Solomon instance strides: any launch covers all)
-    const bool more_batch = h.n_dec_batch > sl.vb_pre_launched || h.n_vb_items > sl.vb_items_launched;
+    const bool no_trellis = sl.vb_blk && sl.vb_fin_launched == 0;              // (left out of the chain: see fxrx_ctx_s.vb_early_tail)
+    const bool more_batch = h.n_dec_batch > sl.vb_pre_launched || (!no_trellis && h.n_vb_items > sl.vb_items_launched);
+    // fx_vbpre_kernel met a frame that is not clean and the trellis kernels were not launched: they run now, over all items (clean
+    // frames' items are off, their waves of the back part leave at once); fx_vbpre_kernel itself is done and is not needed again
+    const bool late_trellis = no_trellis && !more_batch && *(volatile const uint32_t *)&sl.h_hdr.p->vb_dirty != 0u;
     const bool more_fb = sl.vb_blk && h.n_vb_fallback > sl.fb_launched;
-    if (!more_plain && !more_rs && !more_batch && !more_fb) return 0;
+    if (!more_plain && !more_rs && !more_batch && !more_fb && !late_trellis) return 0;
     const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
     FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
     const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? 2 : 1) : 0;     // (fx_launch_paydec)
@@ -1118,15 +1141,17 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     if (more_rs)
         HIP_OK(fx_launch_paydec(1, soft, 0, h.n_dec_rs, 1u, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
                                 sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
-    if (more_batch) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
+    if (more_batch || late_trellis) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
         HIP_OK(hipMemsetAsync(&hdr_pay->n_vb_fallback, 0, sizeof(uint32_t), sl.st));
-        HIP_OK(fx_launch_vbpre(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0));
+        if (more_batch)
+            HIP_OK(fx_launch_vbpre(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0,
+                                   sl.vb_early ? 1 : 0, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p));
         HIP_OK(fx_launch_vbitems(0, h.n_vb_items, sl.st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, c->vb_debug, 1, 1));
         HIP_OK(fx_launch_vbfinish(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
-                                  sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p));
+                                  sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0));
         HIP_OK(fx_launch_paydec(0, 0, 0, kFallbackWaves, 1u, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 3 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
                                 sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, sl.h_hdr.p));
-        sl.vb_pre_launched = h.n_dec_batch; sl.vb_items_launched = h.n_vb_items; sl.fb_launched = kFallbackWaves;
+        sl.vb_pre_launched = sl.vb_fin_launched = h.n_dec_batch; sl.vb_items_launched = h.n_vb_items; sl.fb_launched = kFallbackWaves;
         HIP_OK(hipStreamSynchronize(sl.st));
         { uint32_t nfb = 0; HIP_OK(hipMemcpy(&nfb, &hdr_pay->n_vb_fallback, sizeof nfb, hipMemcpyDeviceToHost)); sl.h_hdr.p->n_vb_fallback = nfb; sl.h_hdr.p->vb_ticket = 0; }
     }
@@ -1318,6 +1343,7 @@ static int collect_block(fxrx_ctx_s *c)
             S.carry_bound = std::min<int64_t>(S.carry_bound, std::min<int64_t>(S.carry_cap, hs[s].carry_len + (S.total - end_total)));
     }
     c->frames_hint = h.n_frames; c->plain_hint = h.n_dec_plain; c->batch_hint = h.n_dec_batch; c->vb_items_hint = h.n_vb_items;
+    if (sl.vb_early && h.n_dec_batch > vb_clean) c->trellis_left = kTrellisHold;     // frames that were not clean: the trellis kernels stay in the chain for a while
     c->fb_hint = h.n_vb_fallback; c->vbfix_hint = h.n_vb_fallback + vb_rep; c->mf_items_hint = h.n_mfblk; c->vb_want_hint = h.vb_want; c->vb_steps_hint = (uint64_t)h.vb_want * (h.vb_blk ? h.vb_blk : 1u); c->first_block = false;
     c->rs_hint = h.n_dec_rs ? h.n_dec_rs : c->rs_hint - std::min<uint64_t>(c->rs_hint, std::max<uint64_t>(1, c->rs_hint / 8));   // (fades out, to zero, over a few dozen blocks without such frames)
     if (h.verify_hops) c->verify_per = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, ((uint64_t)h.verify_hops + 4ull * c->n_cus - 1) / (4ull * c->n_cus)));

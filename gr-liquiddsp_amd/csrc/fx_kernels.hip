@@ -2169,13 +2169,16 @@ __device__ __forceinline__ uint32_t plan_stream_bases(const uint32_t *chain_coun
     return run;
 }
 
-extern "C" __global__ __launch_bounds__(PLAN_THREADS)
-void fx_plan_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain, const uint32_t *chain_count,
-                    uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap, uint32_t vb_cap, uint32_t *pw)
+// What the list pass needs of a frame's job, kept in LDS by the one-workgroup kernel for the first PLAN_KEEP chunks (2048 frames:
+// what one workgroup is given) instead of being read back from pjobs: x = vb_nblk | valid << 16, y = ms, z = fec0, w = fec1 (32 KB of LDS, in one workgroup).
+#define PLAN_KEEP 8
+
+// the body of fx_plan_kernel (keep: nullptr, or PLAN_KEEP * PLAN_THREADS LDS slots that receive those fields of the range's first frames)
+__device__ __forceinline__ void plan_jobs_body(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
+                                               const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0,
+                                               uint32_t mf_cap, uint32_t vb_cap, uint32_t *pw, uint32_t (*ws)[PLAN_NV], uint32_t *base_s, uint4 *keep)
 {
     // vb_blk: trellis steps per block of the batch Viterbi path (0: path off, e.g. soft decisions)
-    __shared__ uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
-    __shared__ uint32_t base_s[PLAN_NV];
     const int tid = threadIdx.x;
     const uint32_t N = plan_stream_bases(chain_count, nstreams, stream_base, ws);
     uint32_t g0, g1; plan_range(N, g0, g1);
@@ -2234,6 +2237,7 @@ void fx_plan_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t det
             j.byte_off = byte_off; j.dw_off = dw_off; j.out_off = out_off; j.pad_ = f.valid ? 1u : 0u;
             j.eq = eq; j.chain_idx = (uint32_t)(fp - chain); j.vb_off = 0; j.vb_nblk = (uint16_t)f.vnb; j.vb_clean = 0;
             pjobs[g] = j;
+            if (keep && c0 - g0 < PLAN_KEEP * PLAN_THREADS) keep[c0 - g0 + tid] = make_uint4((uint32_t)j.vb_nblk | (f.valid ? 0x10000u : 0u), j.ms, j.fec0, j.fec1);
             // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
             union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
             u.r.start = sd.abs_base + fp->start; u.r.stream = f.sidx; u.r.offset = fp->offset;
@@ -2266,18 +2270,30 @@ void fx_plan_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t det
 }
 
 extern "C" __global__ __launch_bounds__(PLAN_THREADS)
-void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_base, FxPayJob *pjobs, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
-                         uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw)
+void fx_plan_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain, const uint32_t *chain_count,
+                    uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap, uint32_t vb_cap, uint32_t *pw)
 {
-    __shared__ uint32_t cls_base[FX_PLL_CLASSES + 1], vbc_base[8], last;
+    __shared__ uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
+    __shared__ uint32_t base_s[PLAN_NV];
+    plan_jobs_body(streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0, mf_cap, vb_cap, pw, ws, base_s, nullptr);
+}
+
+struct PlanListsShared { FxBlockHdr h; uint32_t cls_base[FX_PLL_CLASSES + 1], vbc_base[8], last; };
+// the body of fx_planlists_kernel (keep: nullptr, or what plan_jobs_body left there in the same workgroup).  The counts were added up with
+// device-scope atomics; they are read the same way, so that the one-workgroup kernel sees them without a kernel boundary in between.
+__device__ __forceinline__ void plan_lists_body(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_base, FxPayJob *pjobs, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
+                                                uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw,
+                                                PlanListsShared &sh, const uint4 *keep)
+{
+    uint32_t (&cls_base)[FX_PLL_CLASSES + 1] = sh.cls_base; uint32_t (&vbc_base)[8] = sh.vbc_base; uint32_t &last = sh.last;
     const int tid = threadIdx.x;
-    const uint32_t N = stream_base[nstreams];
+    const uint32_t N = __hip_atomic_load(&stream_base[nstreams], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tid == 0) {
         uint32_t b = 0;
-        for (int c = 0; c < FX_PLL_CLASSES; c++) { cls_base[c] = b; b += (pw[PW_CLS_CNT + c] + 63u) & ~63u; }   // whole waves
+        for (int c = 0; c < FX_PLL_CLASSES; c++) { cls_base[c] = b; b += (__hip_atomic_load(&pw[PW_CLS_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 63u) & ~63u; }   // whole waves
         cls_base[FX_PLL_CLASSES] = b;
         uint32_t vb = 0;
-        for (int c = 0; c < 7; c++) { vbc_base[c] = vb; vb += (pw[PW_VBC_CNT + c] + 127u) & ~127u; }            // whole forward-pass waves: 128 slots
+        for (int c = 0; c < 7; c++) { vbc_base[c] = vb; vb += (__hip_atomic_load(&pw[PW_VBC_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 127u) & ~127u; }            // whole forward-pass waves: 128 slots
         vbc_base[7] = vb;
     }
     __syncthreads();
@@ -2286,7 +2302,10 @@ void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_ba
         const uint32_t g = c0 + tid;
         const bool live = g < g1;
         uint32_t ms = 0, fec0 = 0, fec1 = 0, vnb = 0; bool val = false;
-        if (live) { const FxPayJob &j = pjobs[g]; val = j.pad_ != 0; ms = j.ms; fec0 = j.fec0; fec1 = j.fec1; vnb = j.vb_nblk; }
+        if (live && keep && c0 - g0 < PLAN_KEEP * PLAN_THREADS) {
+            const uint4 kp = keep[c0 - g0 + tid];
+            val = (kp.x >> 16) != 0; vnb = kp.x & 0xffffu; ms = kp.y; fec0 = kp.z; fec1 = kp.w;
+        } else if (live) { const FxPayJob &j = pjobs[g]; val = j.pad_ != 0; ms = j.ms; fec0 = j.fec0; fec1 = j.fec1; vnb = j.vb_nblk; }
         const unsigned c = pll_class(ms);
         const uint32_t pp = cls_base[c] + wave_agg_add(pw + PW_CLS_FILL, c, 1u, val);
         if (val && pp < list_cap) pll_list[pp] = g;
@@ -2303,9 +2322,9 @@ void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_ba
     }
     if (blockIdx.x == 0) {                                                      // padding slots of every class
         for (int c = 0; c < FX_PLL_CLASSES; c++)
-            for (uint32_t i = cls_base[c] + pw[PW_CLS_CNT + c] + tid; i < cls_base[c + 1] && i < list_cap; i += PLAN_THREADS) pll_list[i] = 0xFFFFFFFFu;
+            for (uint32_t i = cls_base[c] + __hip_atomic_load(&pw[PW_CLS_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + tid; i < cls_base[c + 1] && i < list_cap; i += PLAN_THREADS) pll_list[i] = 0xFFFFFFFFu;
         for (int c = 0; c < 7; c++)
-            for (uint32_t i = vbc_base[c] + pw[PW_VBC_CNT + c] + tid; i < vbc_base[c + 1] && i < vb_cap; i += PLAN_THREADS) vb_items[i] = 0xFFFFFFFFu;
+            for (uint32_t i = vbc_base[c] + __hip_atomic_load(&pw[PW_VBC_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + tid; i < vbc_base[c + 1] && i < vb_cap; i += PLAN_THREADS) vb_items[i] = 0xFFFFFFFFu;
     }
     // the workgroup that finishes last: block header for the payload kernels and for the host; counters, workspace and the
     // walk-phase header are zeroed for the slot's next block
@@ -2314,18 +2333,25 @@ void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_ba
     __syncthreads();
     if (!last) return;
     __threadfence();
+    // (the header is put together in LDS -- a local struct indexed per class would live in scratch memory -- and goes out to both
+    // copies a word per thread)
     if (tid == 0) {
-        const volatile uint32_t *tot = pw + PW_INC + 8 * (gridDim.x - 1);
-        FxBlockHdr h = *hdr;
+        const volatile uint32_t *tot = pw + PW_INC + 8 * (gridDim.x - 1), *cnt = pw;
+        FxBlockHdr &h = sh.h;
+        h = *hdr;
         h.n_frames = N; h.n_pjobs = tot[5]; h.n_mfblk = min(tot[4], mf_cap);
-        h.n_dec_plain = pw[PW_DEC_CNT + 0]; h.n_dec_rs = pw[PW_DEC_CNT + 1]; h.n_dec_batch = pw[PW_DEC_CNT + 2];
+        h.n_dec_plain = cnt[PW_DEC_CNT + 0]; h.n_dec_rs = cnt[PW_DEC_CNT + 1]; h.n_dec_batch = cnt[PW_DEC_CNT + 2];
         h.n_vb_items = min(vbc_base[7], vb_cap); h.vb_blk = vb_blk; h.vb_want = tot[6] + 7u * 128u; h.n_vb_fallback = 0;
-        for (int c = 0; c < FX_PLL_CLASSES; c++) { h.pll_cnt[c] = pw[PW_CLS_CNT + c]; h.pll_base[c] = cls_base[c]; }
+        for (int c = 0; c < FX_PLL_CLASSES; c++) { h.pll_cnt[c] = cnt[PW_CLS_CNT + c]; h.pll_base[c] = cls_base[c]; }
         h.pll_base[FX_PLL_CLASSES] = cls_base[FX_PLL_CLASSES];
         h.sym_total = tot[0]; h.byte_total = tot[1]; h.dw_total = tot[2]; h.out_total = tot[3];
         h.done = 1;
-        *hdr_pay = h;
-        *hdr_host = h;
+    }
+    __syncthreads();
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(&sh.h);
+        uint32_t *d0 = reinterpret_cast<uint32_t *>(hdr_pay), *d1 = reinterpret_cast<uint32_t *>(hdr_host);
+        for (int i = tid; i < (int)(sizeof(FxBlockHdr) / 4); i += PLAN_THREADS) { const uint32_t w = src[i]; d0[i] = w; d1[i] = w; }
     }
     __syncthreads();
     {
@@ -2335,12 +2361,43 @@ void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_ba
     }
 }
 
+extern "C" __global__ __launch_bounds__(PLAN_THREADS)
+void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_base, FxPayJob *pjobs, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
+                         uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw)
+{
+    __shared__ PlanListsShared sh;
+    plan_lists_body(nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, pw, sh, nullptr);
+}
+
+// Both passes in ONE workgroup (launched as a grid of one: the usual case, a block of up to ~2048 frames): the grid-wide counts the
+// list pass waits for are this workgroup's own, so a barrier stands where the kernel boundary was.  With blocks in flight on few
+// hardware queues a launch costs its duration plus a gap, and these two are latency-bound single workgroups.
+// Workgroup 0 has nothing to look back at; its flag and inclusive prefix are still written (the header is built from them).
+extern "C" __global__ __launch_bounds__(PLAN_THREADS)
+void fx_planfused_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain, const uint32_t *chain_count,
+                         uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
+                         uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw)
+{
+    __shared__ uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
+    __shared__ uint32_t base_s[PLAN_NV];
+    __shared__ PlanListsShared sh;
+    __shared__ uint4 keep[PLAN_KEEP * PLAN_THREADS];
+    plan_jobs_body(streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0, mf_cap, vb_cap, pw, ws, base_s, keep);
+    __threadfence(); __syncthreads();
+    plan_lists_body(nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, pw, sh, keep);
+}
+
 extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
                                      const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap,
                                      uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
-                                     FxBlockHdr *hdr_host, uint32_t *plan_ws)
+                                     FxBlockHdr *hdr_host, uint32_t *plan_ws, int fused)
 {
     const unsigned g = grid < 1u ? 1u : (grid > PLAN_MAXG ? PLAN_MAXG : grid);
+    if (fused && g == 1u) {
+        hipLaunchKernelGGL(fx_planfused_kernel, dim3(1), dim3(PLAN_THREADS), 0, st, streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0,
+                           mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, plan_ws);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(fx_plan_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0,
                        mf_cap, vb_cap, plan_ws);
     hipLaunchKernelGGL(fx_planlists_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap,
@@ -4217,9 +4274,9 @@ __device__ __forceinline__ uint64_t vb_lds_word(const uint8_t *X, uint32_t w)
 // Rate 1/2 frames whose coded bits, as received, are exactly the encoding of a message with a zero tail: that message is what
 // the Viterbi decoder outputs (every other path into any state of it costs d_free = 10 or more), so it is written to A here
 // -- bit 7 of byte j is step 8 j, as the traceback leaves it -- and the frame is marked clean: the trellis kernels skip it and
-// fx_vbfinish_kernel goes straight to its tail (fx_vbclean.h: the code's feed-forward inverse, the re-encoding, the
-// comparison).  A lane per 32-step word, the words before it re-read from LDS for the carries.
-__device__ __forceinline__ void vb_clean_check(FxPayJob *jobs, uint32_t jf, uint32_t k, const uint8_t *X, uint8_t *A, int lane)
+// the frame's tail follows at once (fx_vbclean.h: the code's feed-forward inverse, the re-encoding, the comparison; DESIGN.md
+// section 2.3).  A lane per 32-step word, the words before it re-read from LDS for the carries.  Returns whether the frame is clean.
+__device__ __forceinline__ bool vb_clean_check(FxPayJob *jobs, uint32_t jf, uint32_t k, const uint8_t *X, uint8_t *A, int lane)
 {
     const uint32_t Tn = 8u * k + 6u, nw = (Tn + 31u) / 32u;
     bool ok = true;
@@ -4236,10 +4293,15 @@ __device__ __forceinline__ void vb_clean_check(FxPayJob *jobs, uint32_t jf, uint
         }
     }
     if (lane == 0) jobs[jf].vb_clean = clean ? 1u : 0u;
+    return clean;
 }
+// early_tail: a clean frame is finished here -- de-whitening, CRC, payload and record to the host (dec_tail) --, the wave has its job
+// and has just written the message; for any other frame one lane raises hdr_host->vb_dirty (a plain store, whoever gets there): the
+// host launches the trellis kernels with the chain only while such frames keep turning up, and otherwise when it collects a block
+// whose flag is up (fx_host.cpp).  early_tail == 0: the tail of every frame is fx_vbfinish_kernel's.
 extern "C" __global__ __launch_bounds__(DEC_THREADS)
 void fx_vbpre_kernel(FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB,
-                     const FxTables *T, uint32_t clean_on)
+                     const FxTables *T, uint32_t clean_on, uint32_t early_tail, uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host)
 {
     __shared__ __attribute__((aligned(16))) uint8_t X[VBPRE_LDS];
     const uint32_t njobs = hdr->n_dec_batch;
@@ -4276,7 +4338,13 @@ void fx_vbpre_kernel(FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *
         const uint32_t n16 = (job.l0 + 8u + 15u) / 16u;
         for (uint32_t j = lane; j < n16; j += DEC_THREADS) reinterpret_cast<uint4 *>(B)[j] = reinterpret_cast<const uint4 *>(X)[j];
         // (the check reads up to 8 bytes past the coded bits: zeroed above; packets on the global-memory branch below keep the trellis)
-        if (clean_on && conv_p(job.fec0) == 1) vb_clean_check(jobs, jf, __builtin_amdgcn_readfirstlane(job.k), X, A, lane);
+        job.k = __builtin_amdgcn_readfirstlane(job.k);
+        const bool clean = clean_on && conv_p(job.fec0) == 1 && vb_clean_check(jobs, jf, job.k, X, A, lane);
+        if (!early_tail) return;
+        if (!clean) { if (lane == 0) hdr_host->vb_dirty = 1u; return; }
+        job.pay_len = __builtin_amdgcn_readfirstlane(job.pay_len); job.check = __builtin_amdgcn_readfirstlane(job.check);
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();                // (the lanes' stores of the message to A)
+        dec_tail(job, jf, A, lane, out, recs, FX_REC_VB_CLEAN);
         return;
     }
     vb_pack_bytes(hs, job.bps, job.l1, A, lane);
@@ -4287,13 +4355,14 @@ void fx_vbpre_kernel(FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *
     deinterleave_wave(B, job.l0, lane);
     // (the window reads of the forward pass run up to 8 bytes past the coded bits: keep them defined)
     if (lane < 8) B[job.l0 + lane] = 0;
+    if (early_tail && lane == 0) hdr_host->vb_dirty = 1u;
 }
 
 // ---- back part, one wave per frame: the chain of traceback states across the frame's blocks, then the frame's tail ----
 extern "C" __global__ __launch_bounds__(64)
 void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHdr *hdr, uint32_t first_wave, uint8_t *bufA, uint8_t *bufB,
                         unsigned long long *dwv, const uint8_t *vec_arena, const uint32_t *vb_st, uint32_t *fb_list, uint32_t list_cap, uint8_t *out, FxOutRec *recs,
-                        FxBlockHdr *hdr_host)
+                        FxBlockHdr *hdr_host, uint32_t early_tail)
 {
     const uint32_t njobs = hdr->n_dec_batch, blk = hdr->vb_blk;
     const uint32_t ji = first_wave + blockIdx.x;
@@ -4305,8 +4374,9 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
     job.check = __builtin_amdgcn_readfirstlane(job.check); job.vb_nblk = (uint16_t)__builtin_amdgcn_readfirstlane(job.vb_nblk);
     job.vb_off = __builtin_amdgcn_readfirstlane(job.vb_off); job.vb_clean = (uint16_t)__builtin_amdgcn_readfirstlane(job.vb_clean);
     uint8_t *A = bufA + job.byte_off, *B = bufB + job.byte_off;
-    // a frame fx_vbpre_kernel decoded itself: its message is in A, and its trellis records are stale (no trellis ran)
-    if (job.vb_clean) { dec_tail(job, jf, A, lane, out, recs, FX_REC_VB_CLEAN); return; }
+    // a frame fx_vbpre_kernel decoded itself: its message is in A, and its trellis records are stale (no trellis ran); with
+    // early_tail the frame is finished already
+    if (job.vb_clean) { if (!early_tail) dec_tail(job, jf, A, lane, out, recs, FX_REC_VB_CLEAN); return; }
     const uint32_t Tn = 8u * job.k + 6u, at = job.vb_off, nblk = job.vb_nblk;
     bool bad = false, mism = false; uint32_t rep = 0;
     for (uint32_t base = 0; base < nblk; base += 64) {
@@ -4337,10 +4407,12 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
 }
 
 extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
-                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on)
+                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on, int early_tail, uint8_t *out, FxOutRec *recs,
+                                      FxBlockHdr *hdr_host)
 {
     if (n_waves == 0) return hipSuccess;
-    hipLaunchKernelGGL(fx_vbpre_kernel, dim3(n_waves), dim3(DEC_THREADS), 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, T, clean_on ? 1u : 0u);
+    hipLaunchKernelGGL(fx_vbpre_kernel, dim3(n_waves), dim3(DEC_THREADS), 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, T, clean_on ? 1u : 0u,
+                       early_tail ? 1u : 0u, out, recs, hdr_host);
     return hipGetLastError();
 }
 // forward pass, [hand-over check,] traceback: the lane-per-work-item kernels, over the same item slots
@@ -4358,10 +4430,11 @@ extern "C" hipError_t fx_launch_vbitems(unsigned first_item, unsigned n_items, h
 }
 extern "C" hipError_t fx_launch_vbfinish(unsigned first_wave, unsigned n_waves, hipStream_t st, const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHdr *hdr,
                                          uint8_t *bufA, uint8_t *bufB, unsigned long long *dwv, const uint8_t *vec_arena, const uint32_t *vb_st, uint32_t *fb_list, uint32_t list_cap,
-                                         uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host)
+                                         uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host, int early_tail)
 {
     if (n_waves == 0) return hipSuccess;
-    hipLaunchKernelGGL(fx_vbfinish_kernel, dim3(n_waves), dim3(64), 0, st, jobs, job_idx, hdr, first_wave, bufA, bufB, dwv, vec_arena, vb_st, fb_list, list_cap, out, recs, hdr_host);
+    hipLaunchKernelGGL(fx_vbfinish_kernel, dim3(n_waves), dim3(64), 0, st, jobs, job_idx, hdr, first_wave, bufA, bufB, dwv, vec_arena, vb_st, fb_list, list_cap, out, recs, hdr_host,
+                       early_tail ? 1u : 0u);
     return hipGetLastError();
 }
 

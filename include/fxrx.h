@@ -286,6 +286,8 @@ typedef struct {
     uint64_t late_decodes;                       /* blocks whose decode launches had to be completed at collect (more frames than the grids were sized for) */
     uint64_t vb_fallbacks;                       /* batch Viterbi: frames handed back to the wave-per-frame decoder (a hand-over that stayed unverified) */
     uint64_t vb_clean;                           /* batch Viterbi: rate-1/2 frames whose coded bits were a codeword as received, decoded without a trellis (FXRX_VB_CLEAN=0: none) */
+    uint64_t trellis_launched;                   /* batch Viterbi: 1 when the block's trellis kernels were launched with its chain, 0 when they were left out (clean
+                                                  * frames finish in fx_vbpre_kernel; FXRX_VB_EARLY_TAIL=0: always 1) */
 } fxrx_timing;
 int fxrx_last_timing(const fxrx_ctx *c, fxrx_timing *t);
 /* Stage times come from HIP events recorded between the kernels of a block, and every event is one more packet in the block's

@@ -22,3 +22,5 @@ for n, iv in by.items():
 perq = collections.defaultdict(list)
 for s, e, n, q in sel: perq[q].append((s, e))
 print("per hardware queue busy:", {q: "%.0f%%" % (100 * union(iv) / 1e6 / span) for q, iv in sorted(perq.items())})
+print("distinct hardware queues in the window: %d" % len(perq))
+print("launches per block: %.2f; kernel time per block (sum of durations) %.3f ms" % (len(sel) / nblk, sum(e - s for s, e, n, q in sel) / 1e6 / nblk))
