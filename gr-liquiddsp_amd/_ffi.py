@@ -68,7 +68,7 @@ class Timing(C.Structure):                  # fxrx_timing
                 ("host_submit_ms", C.c_double), ("host_walkwait_ms", C.c_double),
                 ("seekverify_ms", C.c_double), ("verify_hops", C.c_uint64), ("verify_failures", C.c_uint64),
                 ("host_collectwait_ms", C.c_double), ("walk_mode", C.c_uint64), ("chain_ms", C.c_double), ("replays", C.c_uint64), ("vb_blocks", C.c_uint64), ("vb_repairs", C.c_uint64), ("late_decodes", C.c_uint64), ("vb_fallbacks", C.c_uint64), ("vb_clean", C.c_uint64),
-                ("trellis_launched", C.c_uint64)]
+                ("trellis_launched", C.c_uint64), ("late_windows", C.c_uint64)]
 
 
 # every symbol include/fxrx.h declares (checked by tests/test_cabi.py)
@@ -88,6 +88,7 @@ EXPORTS = [
     "fxtx_create", "fxtx_destroy", "fxtx_frame_len", "fxtx_generate",
     "fxtx_apply_channel", "fxrx_set_timing", "fxrx_debug_block_times", "fxrx_ready", "fxrx_inflight", "fxrx_debug_fail", "fxrx_pinned_alloc", "fxrx_pinned_free", "fxrx_sync_context",
     "fxrx_debug_header_decode", "fxrx_debug_block_decode", "fxrx_sync_set_soft_block",
+    "fxrx_sync_set_streaming", "fxrx_qdet_flush", "fxrx_qdet_pending", "fxrx_qdet_set_block", "fxrx_qdet_context",
     "fxrx_iq_sample_bytes", "fxrx_set_iq_scale", "fxrx_submit_fmt", "fxrx_process_fmt", "fxrx_iq_convert_host", "fxtx_quantize",
 ]
 
@@ -98,6 +99,10 @@ class DropinStats(C.Structure):            # dropin_stats of csrc/blocks/dropin_
     _fields_ = [("seconds", C.c_double), ("frames", C.c_uint64), ("header_valid", C.c_uint64), ("payload_valid", C.c_uint64),
                 ("payload_bytes", C.c_uint64), ("constellation_syms", C.c_uint64), ("packet_infos", C.c_uint64),
                 ("payload_hash", C.c_uint64), ("errors", C.c_uint64), ("first_frame_seconds", C.c_double)]
+
+
+class DropinDetStats(C.Structure):         # dropin_det_stats of csrc/blocks/dropin_feed.cpp
+    _fields_ = [("seconds", C.c_double), ("detections", C.c_uint64), ("hash", C.c_uint64), ("errors", C.c_uint64), ("samples_fed", C.c_uint64)]
 
 
 _feed = None
@@ -117,6 +122,10 @@ def feed_lib():
         L.dropin_copy_ceiling.argtypes = [C.c_void_p, C.c_ulonglong, C.c_uint, C.c_uint]
         L.dropin_feed_threads.restype = C.c_int
         L.dropin_feed_threads.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_ulonglong), C.c_uint, C.c_uint, C.POINTER(DropinStats)]
+        L.dropin_feed_detector.restype = C.c_int
+        L.dropin_feed_detector.argtypes = [C.c_void_p, C.c_ulonglong, C.c_uint, C.c_ulonglong, C.c_float, C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(DropinDetStats)]
+        L.dropin_feed_paced.restype = C.c_int
+        L.dropin_feed_paced.argtypes = [C.c_void_p, C.c_ulonglong, C.c_double, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_double)]
         _feed = L
     return _feed
 
@@ -224,6 +233,11 @@ def lib():
     L.fxrx_sync_pending.argtypes = [C.c_void_p]; L.fxrx_sync_pending.restype = C.c_uint
     L.fxrx_sync_errors.argtypes = [C.c_void_p]; L.fxrx_sync_errors.restype = C.c_uint
     L.fxrx_qdet_errors.argtypes = [C.c_void_p]; L.fxrx_qdet_errors.restype = C.c_uint
+    L.fxrx_sync_set_streaming.argtypes = [C.c_void_p, C.c_uint]; L.fxrx_sync_set_streaming.restype = None
+    L.fxrx_qdet_flush.argtypes = [C.c_void_p]; L.fxrx_qdet_flush.restype = None
+    L.fxrx_qdet_pending.argtypes = [C.c_void_p]; L.fxrx_qdet_pending.restype = C.c_uint
+    L.fxrx_qdet_set_block.argtypes = [C.c_void_p, C.c_uint]; L.fxrx_qdet_set_block.restype = None
+    L.fxrx_qdet_context.argtypes = [C.c_void_p]; L.fxrx_qdet_context.restype = C.c_void_p
     L.msequence_create.restype = C.c_void_p; L.msequence_create.argtypes = [C.c_uint] * 3
     L.msequence_advance.restype = C.c_uint; L.msequence_advance.argtypes = [C.c_void_p]
     L.msequence_destroy.argtypes = [C.c_void_p]; L.msequence_destroy.restype = None

@@ -7,7 +7,9 @@
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <thread>
 #include <vector>
 #include "fx_blocks.hpp"
@@ -123,6 +125,119 @@ double dropin_copy_ceiling(const float *iq, unsigned long long n_samples, unsign
     return (double)(repeats ? repeats : 1u) * (double)(n_samples - n_samples % 256) / dt;
 }
 #endif
+
+// frame_detector_cc's boundary: the reference's per-sample loop (/root/reference/lib/frame_detector_cc_impl.cc:76-82) over a host buffer --
+// qdetector_cccf_execute(q, in[i]) for every sample, a non-NULL return is a detection.  Afterwards what is queued is flushed and the
+// pending detections are drawn with calls that hand in zeros.  Every detection's estimates and window are hashed in order of arrival
+// (FNV-1a over the four floats and the 512 samples), and copied to est (4 floats each) / wins (1024 floats each) for the first `cap`.
+// block: fxrx_qdet_set_block (0: default); fail_collect_at: sample index in front of which the next collect is made to fail (~0: never).
+struct dropin_det_stats { double seconds; uint64_t detections, hash, errors, samples_fed; };
+int dropin_feed_detector(const float *iq, unsigned long long n_samples, unsigned block, unsigned long long fail_collect_at, float threshold,
+                         float *est, float *wins, unsigned cap, dropin_det_stats *out)
+{
+    using clk = std::chrono::steady_clock;
+    dropin_det_stats st{}; st.hash = 14695981039346656037ull;
+    fx_complex pn[64];
+    msequence ms = msequence_create(7, 0x0089, 1);                          // :47-52
+    if (!ms) return -1;
+    for (int i = 0; i < 64; i++) {
+        pn[i].re = msequence_advance(ms) ? (float)M_SQRT1_2 : -(float)M_SQRT1_2;
+        pn[i].im = msequence_advance(ms) ? (float)M_SQRT1_2 : -(float)M_SQRT1_2;
+    }
+    msequence_destroy(ms);
+    qdetector_cccf q = qdetector_cccf_create_linear(pn, 64, LIQUID_FIRFILT_ARKAISER, 2, 7, 0.3f);   // :54
+    if (!q) return -1;
+    qdetector_cccf_set_threshold(q, threshold);                             // :55
+    if (block) fxrx_qdet_set_block(q, block);
+    auto take = [&](void *v) {
+        const float e[4] = { qdetector_cccf_get_tau(q), qdetector_cccf_get_gamma(q), qdetector_cccf_get_dphi(q), qdetector_cccf_get_phi(q) };
+        uint64_t h = st.hash;
+        const unsigned char *b = (const unsigned char *)e;
+        for (unsigned i = 0; i < sizeof e; i++) { h ^= b[i]; h *= 1099511628211ull; }
+        b = (const unsigned char *)v;
+        for (unsigned i = 0; i < 512 * sizeof(fx_complex); i++) { h ^= b[i]; h *= 1099511628211ull; }
+        st.hash = h;
+        if (st.detections < cap) {
+            if (est) std::memcpy(est + 4 * st.detections, e, sizeof e);
+            if (wins) std::memcpy(wins + 1024 * st.detections, v, 512 * sizeof(fx_complex));
+        }
+        st.detections++;
+    };
+    const fx_complex *in = (const fx_complex *)iq;
+    const auto t0 = clk::now();
+    for (unsigned long long i = 0; i < n_samples; i++) {
+        if (i == fail_collect_at) fxrx_debug_fail(fxrx_qdet_context(q), 0, 1);
+        void *v = qdetector_cccf_execute(q, in[i]);                         // :77
+        if (v) take(v);                                                     // :78-81
+    }
+    st.samples_fed = n_samples;
+    fxrx_qdet_flush(q);
+    const fx_complex zero{ 0.0f, 0.0f };
+    while (fxrx_qdet_pending(q)) { void *v = qdetector_cccf_execute(q, zero); if (v) take(v); }
+    st.seconds = std::chrono::duration<double>(clk::now() - t0).count();
+    st.errors = fxrx_qdet_errors(q);
+    qdetector_cccf_destroy(q);
+    *out = st;
+    return 0;
+}
+
+// A paced source: the buffer in 256-sample flexframesync_execute calls, call k not before t0 + 256 k / rate (busy-waiting on the wall
+// clock: an SDR's sample clock), streaming delivery with `streaming_floor` (0: off).  frame_end[j] is the index of the last sample of
+// injected frame j; frames arrive in order, so callback j belongs to it, and latency[j] (seconds) is the time from the entry of the call
+// that handed in that sample to the callback (never negative: a callback inside that very call counts from its entry).  No call is
+// made after the input ends: *undelivered = frames that had not arrived by then; a flush fetches them afterwards, they get no
+// latency.  The pairing is checked: -2 unless exactly n_frames callbacks came in all, every one with a valid header and payload.
+// Before the clock starts the first 2^18 samples run through the handle unpaced and unmeasured (first launches, first-size
+// allocations of the block's arenas), and the handle is reset.  Returns the number of callbacks with a latency, -1 or -2.
+struct pace_state { std::vector<double> *t_cb; std::chrono::steady_clock::time_point t0; unsigned invalid; };
+static int pace_cb(unsigned char *, int hv, unsigned char *, unsigned int, int pv, framesyncstats_s, void *ud)
+{
+    pace_state *s = (pace_state *)ud;
+    s->t_cb->push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - s->t0).count());
+    if (!hv || !pv) s->invalid++;
+    return 0;
+}
+int dropin_feed_paced(const float *iq, unsigned long long n_samples, double rate, unsigned streaming_floor, const unsigned long long *frame_end,
+                      unsigned n_frames, double *latency, unsigned *undelivered, double *achieved_rate)
+{
+    using clk = std::chrono::steady_clock;
+    std::vector<double> t_cb; pace_state ps; ps.t_cb = &t_cb; ps.invalid = 0; ps.t0 = clk::now();
+    flexframesync q = flexframesync_create(pace_cb, &ps);
+    if (!q) return -1;
+    fxrx_sync_set_streaming(q, streaming_floor);
+    const unsigned long long n_calls = n_samples / 256;
+    std::vector<double> t_in(n_calls);
+    {   // warm-up: a real block's worth, the way the measurement feeds
+        const unsigned long long w = std::min<unsigned long long>(n_calls, 1024);
+        for (unsigned long long k = 0; k < w; k++) flexframesync_execute(q, (fx_complex *)(iq + 512 * k), 256);
+        fxrx_sync_flush(q);
+        while (fxrx_sync_pending(q)) flexframesync_execute(q, nullptr, 0);
+        flexframesync_reset(q); t_cb.clear(); ps.invalid = 0;
+    }
+    ps.t0 = clk::now();
+    double t_last = 0.0;
+    for (unsigned long long k = 0; k < n_calls; k++) {
+        const double due = (double)(256 * k) / rate;
+        double now;
+        while ((now = std::chrono::duration<double>(clk::now() - ps.t0).count()) < due) { }
+        t_in[k] = now;
+        flexframesync_execute(q, (fx_complex *)(iq + 512 * k), 256);
+    }
+    t_last = std::chrono::duration<double>(clk::now() - ps.t0).count();
+    if (achieved_rate) *achieved_rate = n_calls ? (double)(256 * n_calls) / t_last : 0.0;
+    const unsigned got = (unsigned)std::min<size_t>(t_cb.size(), n_frames);
+    const size_t seen = t_cb.size();
+    for (unsigned j = 0; j < got; j++) {
+        const unsigned long long k = std::min<unsigned long long>(frame_end[j] / 256, n_calls ? n_calls - 1 : 0);
+        latency[j] = std::max(0.0, t_cb[j] - t_in[k]);
+    }
+    if (undelivered) *undelivered = n_frames - got;
+    fxrx_sync_flush(q);
+    while (fxrx_sync_pending(q)) flexframesync_execute(q, nullptr, 0);
+    const bool paired = seen <= n_frames && t_cb.size() == n_frames && ps.invalid == 0 && fxrx_sync_errors(q) == 0;
+    flexframesync_destroy(q);
+    return paired ? (int)got : -2;
+}
 
 // the same from `n_threads` threads at once, each with its own block instance (GNU Radio: one thread per block) and its own
 // buffer; stats[t] per thread.  Returns the number of threads that failed to make their block.

@@ -51,6 +51,22 @@ struct HeldFrame {
 constexpr unsigned kSyncBlockDefault = 1u << 20;    // samples per GPU block (fxrx_sync_set_block / FXRX_SYNC_BLOCK); see DESIGN.md section 7
 constexpr unsigned kSyncDepthDefault = 3;           // blocks in flight (FXRX_SYNC_DEPTH)
 constexpr unsigned kSyncPollEvery = 1u << 15;       // samples between two looks at whether the oldest block has finished (an event query costs about as much as copying 4000 samples)
+constexpr unsigned kQdetBlockDefault = 1u << 16;    // qdetector_cccf_execute: samples per GPU block (fxrx_qdet_set_block / FXRX_QDET_BLOCK)
+constexpr unsigned kQdetDepthDefault = 1;           // ... blocks in flight (FXRX_QDET_DEPTH)
+constexpr unsigned kQdetPollEvery = 1u << 10;       // ... calls between two looks at the oldest block in flight
+
+// a ring of `count` page-locked buffers of `samples` each; all or nothing
+bool alloc_ring(std::vector<fx_complex *> &ring, unsigned count, size_t samples)
+{
+    std::vector<fx_complex *> r;
+    for (unsigned i = 0; i < count; i++) {
+        fx_complex *p = (fx_complex *)fxrx_pinned_alloc(samples * sizeof(fx_complex));
+        if (!p) { for (auto o : r) fxrx_pinned_free(o); return false; }
+        r.push_back(p);
+    }
+    ring.swap(r);
+    return true;
+}
 
 }  // namespace
 
@@ -67,17 +83,17 @@ struct fxrx_sync_s {
     std::vector<fx_complex *> bufs; unsigned cur = 0; size_t fill = 0;     // ring of depth + 1 pinned input buffers of `block` samples
     std::deque<HeldFrame> pending; HeldFrame current;
     unsigned errors = 0, since_poll = 0;
+    unsigned stream_floor = 0;          // streaming delivery (fxrx_sync_set_streaming / FXRX_SYNC_STREAMING): 0 off, else the fewest samples worth a block
 
     ~fxrx_sync_s() { free_bufs(); }
     void free_bufs() { for (auto p : bufs) fxrx_pinned_free(p); bufs.clear(); cur = 0; fill = 0; }
-    bool alloc_bufs()
+    // a new ring of depth + 1 buffers of `samples`; the old one is given up only once the new one stands
+    bool alloc_bufs(unsigned samples)
     {
+        std::vector<fx_complex *> ring;
+        if (!alloc_ring(ring, depth + 1, samples)) return false;
         free_bufs();
-        for (unsigned i = 0; i < depth + 1; i++) {
-            fx_complex *p = (fx_complex *)fxrx_pinned_alloc((size_t)block * sizeof(fx_complex));
-            if (!p) { free_bufs(); return false; }
-            bufs.push_back(p);
-        }
+        bufs.swap(ring); block = samples;
         return true;
     }
     void report(const char *what, int rc)
@@ -153,7 +169,8 @@ flexframesync flexframesync_create(framesync_callback callback, void *userdata)
     if (const char *e = std::getenv("FXRX_SYNC_DEPTH")) q->depth = (unsigned)std::min(15, std::max(1, std::atoi(e)));
     q->ctx = sync_make_ctx(q.get());
     if (!q->ctx) return nullptr;
-    if (!q->alloc_bufs()) { fxrx_destroy(q->ctx); return nullptr; }
+    if (const char *e = std::getenv("FXRX_SYNC_STREAMING")) q->stream_floor = (unsigned)std::max(0, std::atoi(e));
+    if (!q->alloc_bufs(q->block)) { fxrx_destroy(q->ctx); return nullptr; }
     return q.release();
 }
 // /root/reference/lib/flex_rx_impl.cc:71
@@ -168,6 +185,7 @@ void flexframesync_reset(flexframesync q)
 void flexframesync_execute(flexframesync q, fx_complex *x, unsigned int n)
 {
     if (!q) return;
+    if (q->bufs.empty()) { q->errors++; return; }           // (cannot happen: a ring is only ever swapped for a complete one)
     q->since_poll += n;
     while (n) {
         const size_t take = std::min<size_t>(n, (size_t)q->block - q->fill);
@@ -175,10 +193,13 @@ void flexframesync_execute(flexframesync q, fx_complex *x, unsigned int n)
         q->fill += take; x += take; n -= (unsigned)take;
         if (q->fill == q->block) q->submit_current();
     }
-    if (q->since_poll >= kSyncPollEvery) {
+    if (q->since_poll >= (q->stream_floor ? std::min(kSyncPollEvery, q->stream_floor) : kSyncPollEvery)) {
         q->since_poll = 0;
         if (q->pending.empty() && fxrx_ready(q->ctx) == 1) q->collect_one();
     }
+    // streaming delivery: the GPU is idle and enough has gathered -- run it now, as the next (shorter) block of the continuing stream.
+    // While that block is under way the next one gathers, so block length follows the offered rate by itself.
+    if (q->stream_floor && q->fill >= q->stream_floor && fxrx_inflight(q->ctx) == 0) q->submit_current();
     q->deliver_one();
 }
 void fxrx_sync_flush(flexframesync q) { if (!q) return; q->submit_current(); q->drain(); }
@@ -189,10 +210,10 @@ void fxrx_sync_set_block(flexframesync q, unsigned int samples)
     if (nb == q->block) return;
     fxrx_sync_flush(q);                      // what is queued runs at the old size (buffers move)
     for (auto &h : q->pending) h.materialise();
-    const unsigned old = q->block;
-    q->block = nb;
-    if (!q->alloc_bufs()) { q->errors++; std::fprintf(stderr, "libfxrx: fxrx_sync_set_block: %s\n", fxrx_last_error()); q->block = old; (void)q->alloc_bufs(); }
+    q->current.materialise();
+    if (!q->alloc_bufs(nb)) { q->errors++; std::fprintf(stderr, "libfxrx: fxrx_sync_set_block: %s (block length unchanged)\n", fxrx_last_error()); }
 }
+void fxrx_sync_set_streaming(flexframesync q, unsigned int floor_samples) { if (q) q->stream_floor = floor_samples; }
 unsigned int fxrx_sync_pending(flexframesync q) { return q ? (unsigned)q->pending.size() : 0; }
 unsigned int fxrx_sync_errors(flexframesync q) { return q ? q->errors : 0; }
 fxrx_ctx *fxrx_sync_context(flexframesync q) { return q ? q->ctx : nullptr; }
@@ -240,37 +261,85 @@ void msequence_destroy(msequence ms) { delete ms; }
 }
 
 // ------------------------------------------------------------------------------------------ qdetector_cccf
+// The reference hands over one sample per call (/root/reference/lib/frame_detector_cc_impl.cc:76-82).  Built like fxrx_sync_s: a
+// call is one store into the page-locked buffer being filled plus a counter; a full buffer is submitted as the next block of one
+// continuing stream on a detector context that returns the aligned windows (want_framesyms: fx_detwin_kernel), and the next
+// buffer of the ring fills meanwhile.  A block in flight is collected when its slot is needed, when a poll finds it done, or --
+// so that delivery never depends on how fast the GPU happens to be -- once an eighth of a block length (plus depth - 1 block lengths)
+// has been handed in since it was submitted: a detection leaves at most that long after its block filled, whatever the timing.
+// That bound is kept by a forced wait: the call that reaches the age limit blocks in fxrx_collect, on the caller's thread, until the
+// GPU has finished the block (a block takes far less than an eighth of its length to fill only above some hundred Msamples/s).
+// Detections wait in `pending` with their windows (copies: the context's are valid until its next collect) and leave one per
+// call.  There is no host-side history of the samples.
 struct fxrx_qdet_s {
+    struct Det { float tau, gamma, dphi, phi; fx_complex win[FX_NFFT]; };
     fxrx_ctx *ctx = nullptr; float threshold = 0.5f;
-    std::vector<fx_complex> hist;       // samples since hist_base (kept long enough to cut aligned windows)
-    int64_t hist_base = 0; size_t fed = 0;     // `fed` samples of hist already given to the GPU
-    unsigned block = 1u << 16;
-    std::deque<fxrx_frame> pending;
-    fx_complex window[FX_NFFT];
+    unsigned block = kQdetBlockDefault, depth = kQdetDepthDefault;
+    std::vector<fx_complex *> bufs; unsigned cur = 0; size_t fill = 0;      // ring of depth + 1 pinned buffers of `block` samples
+    std::deque<uint64_t> submitted_at;  // per block in flight: `count` when it was submitted
+    uint64_t count = 0;                 // samples handed in so far
+    std::deque<Det> pending;
+    fx_complex window[FX_NFFT];         // what the last non-NULL call returned (valid until the next call)
     float tau = 0, gamma = 0, dphi = 0, phi = 0;
-    unsigned errors = 0;
-    bool make_ctx()                     // a failed re-creation keeps the old context
+    unsigned errors = 0, since_poll = 0;
+
+    ~fxrx_qdet_s() { for (auto p : bufs) fxrx_pinned_free(p); }
+    fxrx_ctx *new_ctx()
     {
-        fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_DETECTOR; cfg.n_streams = 1; cfg.threshold = threshold;
+        fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_DETECTOR; cfg.n_streams = 1; cfg.threshold = threshold; cfg.want_framesyms = 1;
         if (const char *d = std::getenv("FXRX_DEVICE")) cfg.device = std::atoi(d);
         fxrx_ctx *nc = fxrx_create(&cfg);
+        if (nc && fxrx_set_depth(nc, depth) != 0) { fxrx_destroy(nc); nc = nullptr; }
+        return nc;
+    }
+    bool make_ctx()                     // a failed re-creation keeps the old context
+    {
+        fxrx_ctx *nc = new_ctx();
         if (!nc) { errors++; std::fprintf(stderr, "libfxrx: qdetector_cccf: %s\n", fxrx_last_error()); return false; }
         if (ctx) fxrx_destroy(ctx);
-        ctx = nc;
+        ctx = nc; submitted_at.clear(); pending.clear(); fill = 0;
         return true;
     }
-    void run()
+    void report(const char *what, int rc)
     {
-        const void *p = hist.data() + fed; uint64_t n = hist.size() - fed;
-        int nr = fxrx_process(ctx, &p, &n, 0);
-        if (nr < 0) {                   // samples stay un-fed: they run again with the next block
-            if (errors++ == 0 || (errors & (errors - 1)) == 0)
-                std::fprintf(stderr, "libfxrx: qdetector_cccf_execute: block of %llu samples failed (%d): %s [%u failures so far]\n",
-                             (unsigned long long)n, nr, fxrx_last_error(), errors);
-            return;
+        if (errors++ == 0 || (errors & (errors - 1)) == 0)
+            std::fprintf(stderr, "libfxrx: %s failed (%d): %s [%u failures so far]\n", what, rc, fxrx_last_error(), errors);
+    }
+    // the oldest block in flight: wait for it, queue its detections
+    void collect_one()
+    {
+        const int nr = fxrx_collect(ctx);
+        if (nr < 0) { report("qdetector_cccf_execute: block", nr); submitted_at.clear(); return; }   // (every block in flight went with it; the detector restarts fresh)
+        if (!submitted_at.empty()) submitted_at.pop_front();
+        for (int i = 0; i < nr; i++) {
+            fxrx_frame f;
+            // (a detection without its window cannot be handed out: it is dropped, counted and reported, never passed over in silence)
+            if (fxrx_result(ctx, (unsigned)i, &f) != 0 || !f.framesyms || f.num_framesyms != FX_NFFT) { report("qdetector_cccf_execute: a detection's window", FXRX_ERR_STATE); continue; }
+            pending.emplace_back();
+            Det &d = pending.back();
+            d.tau = f.tau; d.gamma = f.gamma; d.dphi = f.dphi; d.phi = f.phi;
+            std::memcpy(d.win, f.framesyms, sizeof d.win);
         }
-        fed = hist.size();
-        for (int i = 0; i < nr; i++) { fxrx_frame f; if (fxrx_result(ctx, (unsigned)i, &f) == 0) pending.push_back(f); }
+    }
+    void drain() { while (fxrx_inflight(ctx)) collect_one(); }
+    // hand the buffer being filled to the GPU as the stream's next block
+    void submit_current()
+    {
+        if (!fill) return;
+        if (fxrx_inflight(ctx) >= depth) collect_one();
+        const void *p = bufs[cur]; uint64_t n = fill;
+        const int r = fxrx_submit(ctx, &p, &n, 0);
+        if (r < 0) {                    // these samples are lost to the detector, never fed again: it restarts freshly reset behind the gap
+            report("qdetector_cccf_execute: submit", r);
+            drain();
+            fxrx_reset(ctx);
+        } else submitted_at.push_back(count);
+        cur = (cur + 1) % (unsigned)bufs.size(); fill = 0;
+    }
+    void poll()
+    {
+        const uint64_t age_limit = (uint64_t)(depth - 1) * block + block / 8;
+        while (!submitted_at.empty() && (count - submitted_at.front() >= age_limit || fxrx_ready(ctx) == 1)) collect_one();
     }
 };
 extern "C" {
@@ -281,45 +350,51 @@ qdetector_cccf qdetector_cccf_create_linear(fx_complex *seq, unsigned int len, i
     if (!seq || len != FX_PN_LEN || ftype != LIQUID_FIRFILT_ARKAISER || k != FX_K || m != FX_M || std::fabs(beta - FX_BETA) > 1e-6f) return nullptr;
     for (unsigned i = 0; i < len; i++)
         if (std::fabs(seq[i].re - T.pn[i].re) > 1e-6f || std::fabs(seq[i].im - T.pn[i].im) > 1e-6f) return nullptr;
-    fxrx_qdet_s *q = new fxrx_qdet_s; q->make_ctx();
-    if (!q->ctx) { delete q; return nullptr; }
-    return q;
+    std::unique_ptr<fxrx_qdet_s> q(new fxrx_qdet_s);
+    if (const char *e = std::getenv("FXRX_QDET_BLOCK")) q->block = (unsigned)std::max(FX_NFFT, std::atoi(e));
+    if (const char *e = std::getenv("FXRX_QDET_DEPTH")) q->depth = (unsigned)std::min(15, std::max(1, std::atoi(e)));
+    if (!q->make_ctx()) return nullptr;
+    if (!alloc_ring(q->bufs, q->depth + 1, q->block)) { fxrx_destroy(q->ctx); return nullptr; }
+    return q.release();
 }
 // /root/reference/lib/frame_detector_cc_impl.cc:63
 void qdetector_cccf_destroy(qdetector_cccf q) { if (!q) return; fxrx_destroy(q->ctx); delete q; }
-// /root/reference/lib/frame_detector_cc_impl.cc:55
+// /root/reference/lib/frame_detector_cc_impl.cc:55.  The detector starts over (what is queued or in flight is dropped), as before.
 void qdetector_cccf_set_threshold(qdetector_cccf q, float t)
 {
     if (!q) return;
     const float old = q->threshold;
     q->threshold = t;
-    if (!q->make_ctx()) { q->threshold = old; return; }
-    q->hist.clear(); q->hist_base = 0; q->fed = 0; q->pending.clear();
+    if (!q->make_ctx()) q->threshold = old;
 }
 unsigned int fxrx_qdet_errors(qdetector_cccf q) { return q ? q->errors : 0; }
+unsigned int fxrx_qdet_pending(qdetector_cccf q) { return q ? (unsigned)q->pending.size() : 0; }
+fxrx_ctx *fxrx_qdet_context(qdetector_cccf q) { return q ? q->ctx : nullptr; }
+void fxrx_qdet_flush(qdetector_cccf q) { if (!q || !q->ctx) return; q->submit_current(); q->drain(); }
+void fxrx_qdet_set_block(qdetector_cccf q, unsigned int samples)
+{
+    if (!q || !q->ctx) return;
+    const unsigned nb = samples < FX_NFFT ? (unsigned)FX_NFFT : samples;
+    if (nb == q->block) return;
+    fxrx_qdet_flush(q);                     // what is queued runs at the old size (buffers move)
+    std::vector<fx_complex *> ring;
+    if (!alloc_ring(ring, q->depth + 1, nb)) { q->errors++; std::fprintf(stderr, "libfxrx: fxrx_qdet_set_block: %s (block length unchanged)\n", fxrx_last_error()); return; }
+    q->bufs.swap(ring);
+    for (auto p : ring) fxrx_pinned_free(p);
+    q->block = nb; q->cur = 0; q->fill = 0;
+}
 // /root/reference/lib/frame_detector_cc_impl.cc:77
 void *qdetector_cccf_execute(qdetector_cccf q, fx_complex x)
 {
     if (!q || !q->ctx) return nullptr;
-    q->hist.push_back(x);
-    if (q->hist.size() - q->fed >= q->block) {
-        q->run();
-        // drop history no pending detection can need any more (keep 2 windows of slack)
-        int64_t keep_from = q->hist_base + (int64_t)q->fed - 4 * FX_NFFT;
-        for (const auto &f : q->pending) keep_from = std::min<int64_t>(keep_from, f.start);
-        if (keep_from > q->hist_base) {
-            size_t drop = (size_t)(keep_from - q->hist_base);
-            q->hist.erase(q->hist.begin(), q->hist.begin() + (std::ptrdiff_t)drop);
-            q->hist_base += (int64_t)drop; q->fed -= drop;
-        }
-    }
+    q->bufs[q->cur][q->fill++] = x; q->count++;
+    if (q->fill == q->block) q->submit_current();
+    if (++q->since_poll >= kQdetPollEvery) { q->since_poll = 0; q->poll(); }
     if (q->pending.empty()) return nullptr;
-    fxrx_frame f = q->pending.front(); q->pending.pop_front();
-    q->tau = f.tau; q->gamma = f.gamma; q->dphi = f.dphi; q->phi = f.phi;
-    for (int i = 0; i < FX_NFFT; i++) {
-        int64_t p = f.start + i - q->hist_base;
-        q->window[i] = (p >= 0 && p < (int64_t)q->hist.size() && f.start + i >= 0) ? q->hist[(size_t)p] : fx_complex{ 0, 0 };
-    }
+    const fxrx_qdet_s::Det &d = q->pending.front();
+    q->tau = d.tau; q->gamma = d.gamma; q->dphi = d.dphi; q->phi = d.phi;      // (estimates first, then the pointer: the order callers rely on)
+    std::memcpy(q->window, d.win, sizeof q->window);
+    q->pending.pop_front();
     return q->window;
 }
 // /root/reference/lib/frame_detector_cc_impl.cc:90-93 (commented-out getters)

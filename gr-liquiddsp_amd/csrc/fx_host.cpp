@@ -13,10 +13,11 @@
 //   chain                               -- fx_chainfast_kernel: stitch / resume state / carried tail, per stream
 //   plan                                -- fx_planfused_kernel (or fx_plan_kernel + fx_planlists_kernel): payload jobs, work lists, host result records
 //   payload MF -> PLL -> packet decode  -- results land in pinned host memory
+//   (detector mode with want_framesyms: fx_detwin_kernel instead -- the detections' aligned windows into pinned host memory)
 //
-// Slow paths, all at fxrx_collect (repair_and_replay, finish_decode): repair rounds (segments walked again in parallel:
+// Slow paths, all at fxrx_collect (repair_and_replay, finish_decode, finish_windows): repair rounds (segments walked again in parallel:
 // hand-off misses, fired skipped hops), the full-size fx_chain_kernel, a whole-block walk without hop skipping, carry
-// buffers that have to grow, decode launches that the hint-sized grids did not cover.
+// buffers that have to grow, decode launches that the hint-sized grids did not cover, windows beyond the reserved slots.
 //
 // Why segments: liquid's synchroniser is one sequential state machine per stream (where the detector restarts after a
 // frame depends on that frame's header).  Each stream is cut into segments that are walked concurrently from a
@@ -82,6 +83,9 @@ extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wav
 extern "C" hipError_t fx_launch_symcopy(unsigned grid, hipStream_t st, const FxBlockHdr *hdr, const float2 *sym, float2 *host);
 extern "C" hipError_t fx_launch_upload(hipStream_t st, const void *src, void *dst, size_t bytes, unsigned n_cus);
 extern "C" hipError_t fx_launch_ingest(hipStream_t st, int fmt, const void *src, float2 *dst, size_t n, float scale, unsigned n_cus);   // fx_ingest.hip
+extern "C" hipError_t fx_launch_detwin(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, const uint32_t *stream_base, const FxPayJob *pjobs,
+                                       const FxBlockHdr *hdr, uint32_t first, uint32_t reserved, float2 *out, float2 *out_tail, uint32_t *flag_host, int with_tails,
+                                       int skip_tail);   // fx_detwin.hip
 extern "C" hipError_t fx_launch_copy_u32(hipStream_t st, const uint32_t *src, uint32_t *dst);
 extern "C" hipError_t fx_launch_softdemod(unsigned grid, hipStream_t st, const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr,
                                           const float2 *framesyms, const uint8_t *hard, uint8_t *soft_arena, const FxTables *T);
@@ -124,6 +128,15 @@ template <class T> struct PinBuf {
         p = nullptr; cap = 0;
         if (hipHostMalloc((void **)&p, nc * sizeof(T), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return FXRX_ERR_HIP; }
         cap = nc; return 0;
+    }
+    // grow to n elements and keep the first `keep` of what is there
+    int grow_keep(size_t n, size_t keep)
+    {
+        if (n <= cap) return 0;
+        T *np = nullptr;
+        if (hipHostMalloc((void **)&np, n * sizeof(T), hipHostMallocDefault) != hipSuccess) { set_err("hipHostMalloc failed"); return FXRX_ERR_HIP; }
+        if (p) { std::memcpy(np, p, std::min(keep, cap) * sizeof(T)); (void)hipHostFree(p); }
+        p = np; cap = n; return 0;
     }
     ~PinBuf() { if (p) (void)hipHostFree(p); }
 };
@@ -203,6 +216,10 @@ struct Slot {
     DevBuf<uint8_t> d_hard, d_bufA, d_bufB, d_soft; DevBuf<unsigned long long> d_dw;
     // results (pinned host memory the kernels write into)
     PinBuf<FxBlockHdr> h_hdr; PinBuf<FxOutRec> h_recs; PinBuf<uint8_t> h_out, h_soft; PinBuf<float2> h_framesyms;
+    // detector mode with want_framesyms: the detections' aligned windows, 512 samples (4096 bytes) a slot.  h_win: slot i = record i, for the
+    // win_reserved records the block was sized for (and, once finish_windows has grown it, for all of them); h_wintail: slot 2 s + k = record k
+    // of stream s where that record lies beyond the reservation and starts in the carried tail; h_winflag: a third such record turned up
+    PinBuf<float2> h_win, h_wintail; PinBuf<uint32_t> h_winflag; uint32_t win_reserved = 0;
     std::vector<Out> out;
     uint64_t n_syms = 0;
     fxrx_timing timing{};
@@ -262,6 +279,8 @@ struct fxrx_ctx_s {
     std::vector<std::unique_ptr<Slot>> slots; unsigned depth = 1, head = 0, tail = 0, inflight = 0;
     Slot *last = nullptr;                // slot whose results are currently exposed through fxrx_result
     uint64_t replays = 0, repairs_host = 0, late_decodes = 0;
+    uint64_t late_windows = 0;           // blocks whose aligned windows had to be completed at collect (more detections than slots were reserved)
+    uint32_t detwin_reserve = 0;         // FXRX_DETWIN_RESERVE (tests): window slots reserved per block instead of the last block's count plus a margin
     unsigned noskip_left = 0;            // blocks still to be walked with the exact detector on every hop (after a verification failure)
     unsigned debug_fail_submit = 0, debug_fail_collect = 0;   // tests (fxrx_debug_fail): the next n submits / collects report a failure
     uint64_t discarded = 0;              // blocks dropped by a failing fxrx_collect (see discard_inflight)
@@ -443,6 +462,7 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_MF_PER_CU")) c->mf_per_cu = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_INGEST_KERNEL_MAX")) c->ingest_kernel_max = (size_t)std::max<long long>(0, std::atoll(e));
     if (const char *e = std::getenv("FXRX_PLAN_GRID")) c->plan_grid = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
+    if (const char *e = std::getenv("FXRX_DETWIN_RESERVE")) c->detwin_reserve = (uint32_t)std::max(0, std::atoi(e));
     if (const char *e = std::getenv("FXRX_VB_DEBUG")) c->vb_debug = (uint32_t)std::atoi(e);
     // (a block is at least as long as the warm-up of the next one: 128 steps)
     if (const char *e = std::getenv("FXRX_VB_BLK")) if (std::atoi(e) > 0) c->vb_blk_force = (uint32_t)std::min(4096, std::max(128, (std::atoi(e) + 63) / 64 * 64));
@@ -654,6 +674,14 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl)
     if (!detect && (sl.d_symraw.reserve(sl.sym_cap) || sl.d_hard.reserve(sl.sym_cap + 64) ||
                     sl.d_bufA.reserve(sl.byte_cap + 256) || sl.d_bufB.reserve(sl.byte_cap + 256) || sl.d_dw.reserve(sl.dw_cap) || sl.h_out.reserve(sl.out_cap))) return FXRX_ERR_HIP;
     if (!detect && c->cfg.want_framesyms && sl.h_framesyms.reserve(sl.sym_cap)) return FXRX_ERR_HIP;
+    if (detect && c->cfg.want_framesyms) {
+        // aligned windows: one 4 KB slot per detection the block is expected to hold -- the last collected block's count plus a margin, as
+        // for the other lists only the device can count (one slot per possible detection would be twice the input, in pinned memory); a
+        // block that holds more is completed when it is collected (finish_windows)
+        sl.win_reserved = (uint32_t)std::min<uint64_t>(chain_slots, c->detwin_reserve ? c->detwin_reserve : c->frames_hint + c->frames_hint / 2 + 64);
+        if (sl.h_win.reserve((size_t)sl.win_reserved * FX_NFFT) || sl.h_wintail.reserve(2 * (size_t)NS * FX_NFFT) || sl.h_winflag.reserve(1)) return FXRX_ERR_HIP;
+        *sl.h_winflag.p = 0u;
+    }
     if (!sl.d_plan_ws.p) {
         if (sl.d_plan_ws.reserve(fx_plan_ws_words())) return FXRX_ERR_HIP;
         HIP_OK(hipMemsetAsync(sl.d_plan_ws.p, 0, fx_plan_ws_words() * sizeof(uint32_t), st));
@@ -848,6 +876,10 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         if (c->cfg.want_framesyms)
             HIP_OK(fx_launch_symcopy(2u * (unsigned)c->n_cus, st, hdr_pay, sl.d_symraw.p, sl.h_framesyms.p));
     } else {
+        // (in front of the event the next-but-one block's chain kernel waits for before it writes over the carried tail this one reads)
+        if (c->cfg.want_framesyms)
+            HIP_OK(fx_launch_detwin(st, std::min<unsigned>(std::max<unsigned>(sl.win_reserved, 1u), 4u * (unsigned)c->n_cus), d_streams, NS, sl.d_stream_base.p, sl.d_pjobs.p, hdr_pay, 0u,
+                                    sl.win_reserved, sl.h_win.p, sl.h_wintail.p, sl.h_winflag.p, 1, 0));
         HIP_OK(hipEventRecord(sl.ev[5], st));
         if (tl >= 1) HIP_OK(hipEventRecord(sl.ev[6], st));
         if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[7], st));
@@ -1167,6 +1199,23 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     return 0;
 }
 
+// Detector mode with want_framesyms: a block with more detections than window slots were reserved for it.  The slots are grown to the
+// count -- what is there is kept -- and fx_detwin_kernel runs for the rest, from the block's input (valid until now: the API asks for
+// that).  Windows that start in the carried tail, which is not, were written with the chain (fx_detwin.hip).
+static int finish_windows(fxrx_ctx_s *c, Slot &sl)
+{
+    if (*(volatile const uint32_t *)sl.h_winflag.p) { set_err("fxrx_collect: more than two detections of a stream start in its carried tail (internal sizing error)"); return FXRX_ERR_STATE; }
+    const uint32_t n = sl.h_hdr.p->n_frames;
+    if (n <= sl.win_reserved) return 0;
+    { const int r = sl.h_win.grow_keep((size_t)n * FX_NFFT, (size_t)sl.win_reserved * FX_NFFT); if (r) return r; }     // (n > win_reserved: every reserved slot was written)
+    const FxStreamDesc *d_streams = reinterpret_cast<const FxStreamDesc *>(sl.d_desc.p + sl.o_streams);
+    HIP_OK(fx_launch_detwin(sl.st, std::min<unsigned>(n - sl.win_reserved, 4u * (unsigned)c->n_cus), d_streams, c->cfg.n_streams, sl.d_stream_base.p, sl.d_pjobs.p, sl.d_hdr.p + 1,
+                            sl.win_reserved, n, sl.h_win.p, sl.h_wintail.p, sl.h_winflag.p, 0, 1));
+    HIP_OK(hipStreamSynchronize(sl.st));
+    c->late_windows++;
+    return 0;
+}
+
 // A block that cannot be completed takes the blocks in flight behind it along (they continue its streams, or at least share its
 // arenas' fate): everything in flight is dropped, the slots' device-side counters are cleared, and every stream restarts from a
 // freshly reset synchroniser with its next block -- sample positions keep counting, the dropped samples are simply never
@@ -1296,6 +1345,7 @@ static int collect_block(fxrx_ctx_s *c)
     if (sl.timing_level >= 2 && c->ref_event) { float m = 0; (void)hipEventElapsedTime(&m, c->ref_event, sl.ev[0]); sl.dbg_gpu_start_ms = m; (void)hipEventElapsedTime(&m, c->ref_event, sl.ev[8]); sl.dbg_gpu_done_ms = m; }
     if (c->debug_stop_after) { sl.out.clear(); sl.busy = false; c->last = &sl; c->tail = (c->tail + 1) % nslots; c->inflight--; return 0; }
     if (c->cfg.mode != FXRX_MODE_DETECTOR) { int r = finish_decode(c, sl); if (r) return r; }
+    else if (c->cfg.want_framesyms) { int r = finish_windows(c, sl); if (r) return r; }
     if (sl.h_hdr.p->n_repair_req) c->inchain_left = 16;
     if (sl.h_hdr.p->n_repair_req && sl.h_hdr.p->verify_failures) {
         // the chain mended something by itself: streams in which a skipped hop fired are walked with the exact detector on every
@@ -1311,6 +1361,7 @@ static int collect_block(fxrx_ctx_s *c)
     sl.out.resize(h.n_frames);
     uint64_t vb_rep = 0;                       // trellis blocks the batch Viterbi path had to run again (hand-over check failed)
     uint64_t vb_clean = 0;                     // frames it decoded by the codeword check alone
+    uint32_t s_cur = 0xFFFFFFFFu, s_first = 0; // detector windows: the stream of the last record and that stream's first record
     for (uint32_t i = 0; i < h.n_frames; i++) {
         const FxOutRec &r = sl.h_recs.p[i];
         fxrx_frame &f = sl.out[i].f; std::memset(&f, 0, sizeof f);
@@ -1320,6 +1371,13 @@ static int collect_block(fxrx_ctx_s *c)
         f.header_valid = (r.flags & FX_FLAG_HEADER_VALID) ? 1 : 0;
         std::memcpy(f.header, r.header, FX_HDR_DEC);
         f.rssi_db = 20.0f * log10f(r.gamma); f.cfo = r.dphi;
+        if (detect && c->cfg.want_framesyms && r.stream < NS) {
+            if (r.stream != s_cur) { s_cur = r.stream; s_first = i; }
+            // (beyond the reservation a window that starts in the carried tail has its own slot: see fx_detwin.hip)
+            const bool tail = i >= sl.win_reserved && r.start < sl.snap[r.stream].tot0;
+            f.framesyms = (const fx_complex *)(tail ? sl.h_wintail.p + (2 * (size_t)r.stream + (i - s_first)) * FX_NFFT : sl.h_win.p + (size_t)i * FX_NFFT);
+            f.num_framesyms = FX_NFFT;
+        }
         if (!detect && f.header_valid) {
             f.mod_scheme = r.ms; f.mod_bps = r.bps; f.check = r.check; f.fec0 = r.fec0; f.fec1 = r.fec1;
             f.payload_len = r.pay_len; f.num_framesyms = r.nsym;
@@ -1364,7 +1422,7 @@ static int collect_block(fxrx_ctx_s *c)
     t.payload_symbols = h.sym_total; t.verify_hops = h.verify_hops + sl.kept_vhops; t.verify_failures = h.verify_failures + sl.kept_vfail;
     t.host_submit_ms = sl.host_submit_ms; t.host_walkwait_ms = 0.0; t.walk_mode = sl.any_late ? 1 : 0; t.replays = c->replays + c->repairs_host;
     t.vb_blocks = h.n_vb_items; t.vb_repairs = vb_rep; t.late_decodes = c->late_decodes; t.vb_fallbacks = h.n_vb_fallback;
-    t.vb_clean = vb_clean;
+    t.vb_clean = vb_clean; t.late_windows = c->late_windows;
     sl.busy = false; c->last = &sl;
     c->tail = (c->tail + 1) % nslots; c->inflight--;
     return (int)sl.out.size();

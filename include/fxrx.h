@@ -76,7 +76,14 @@ void flexframesync_reset(flexframesync q);
  * fxrx_sync_flush: run whatever is queued now and wait for everything in flight (frames are then pending: n = 0 calls
  * deliver them).  fxrx_sync_set_block: flushes, then changes the block length. */
 void fxrx_sync_flush(flexframesync q);
-void fxrx_sync_set_block(flexframesync q, unsigned int samples);
+void fxrx_sync_set_block(flexframesync q, unsigned int samples);     /* (if the new buffers cannot be had, the old length stays and fxrx_sync_errors goes up) */
+/* Streaming delivery (opt-in; off by default).  floor_samples > 0: whenever a call ends with nothing in flight on the GPU and at least
+ * floor_samples queued, the partly filled buffer is run at once as the next, shorter, block of the continuing stream, and finished blocks
+ * are looked for at least every floor_samples samples.  Frames then reach the callback without fxrx_sync_flush and without waiting for a
+ * block to fill; block length follows the offered rate by itself (while one block runs the next gathers).  Still at most one frame per
+ * call, buffers valid until the next call on the handle.  0: off.  A sensible floor is 8192.  Environment: FXRX_SYNC_STREAMING=<floor>,
+ * read by flexframesync_create -- how an unmodified caller turns it on. */
+void fxrx_sync_set_streaming(flexframesync q, unsigned int floor_samples);
 void fxrx_sync_set_threshold(flexframesync q, float threshold);
 void fxrx_sync_set_equalizer(flexframesync q, int on);   /* re-creates the context like fxrx_sync_set_threshold */
 void fxrx_sync_set_soft(flexframesync q, int on);        /* likewise: soft-decision payload decoding */
@@ -106,16 +113,28 @@ qdetector_cccf qdetector_cccf_create_linear(fx_complex *sequence, unsigned int s
                                             unsigned int k, unsigned int m, float beta);
 void   qdetector_cccf_destroy(qdetector_cccf q);
 void   qdetector_cccf_set_threshold(qdetector_cccf q, float threshold);
-/* Per-sample entry kept for link compatibility.  Samples are queued and searched on the GPU in
- * blocks; every detection is reported exactly once (non-NULL = the 512 aligned samples), possibly
- * some samples later than liquid would.  Block users should call fxrx_detect_* instead. */
+/* Per-sample entry kept for link compatibility.  A call stores the sample in a page-locked buffer; a full buffer (65 536 samples;
+ * FXRX_QDET_BLOCK / fxrx_qdet_set_block, at least 512) is searched on the GPU as the next block of one continuing stream while the
+ * next buffer fills, FXRX_QDET_DEPTH (default 1) blocks in flight.  Every detection is reported exactly once, one per call, later
+ * than liquid would: at the latest an eighth of a block length (plus depth - 1 block lengths, and up to 1024 calls) after its block filled, earlier when a
+ * poll finds the block done.  That bound holds whatever the GPU's timing because it is enforced by a wait: the call that reaches it
+ * blocks in fxrx_collect, on the caller's thread, until the block is done.  tau, gamma, dphi, phi are set before the pointer is returned; the pointer is the handle's own buffer
+ * of the 512 aligned samples (cut on the GPU, fxrx_config.want_framesyms), valid until the next call.  Block users should use the
+ * batched API in detector mode instead. */
 void  *qdetector_cccf_execute(qdetector_cccf q, fx_complex x);
 float  qdetector_cccf_get_tau(qdetector_cccf q);
 float  qdetector_cccf_get_gamma(qdetector_cccf q);
 float  qdetector_cccf_get_dphi(qdetector_cccf q);
 float  qdetector_cccf_get_phi(qdetector_cccf q);
 unsigned int qdetector_cccf_get_buf_len(qdetector_cccf q);
-unsigned int fxrx_qdet_errors(qdetector_cccf q);     /* as fxrx_sync_errors */
+unsigned int fxrx_qdet_errors(qdetector_cccf q);     /* as fxrx_sync_errors: a failed block's samples are dropped, never fed twice; the detector restarts freshly reset behind the gap */
+/* extensions (additive).  fxrx_qdet_flush: submit what is queued, wait for everything in flight; detections are then pending (further
+ * calls deliver them, one each).  fxrx_qdet_set_block: flushes, then changes the block length (unchanged, and an error counted, if the
+ * buffers cannot be had).  fxrx_qdet_context: the batched detector context underneath (tests, statistics). */
+void         fxrx_qdet_flush(qdetector_cccf q);
+unsigned int fxrx_qdet_pending(qdetector_cccf q);
+void         fxrx_qdet_set_block(qdetector_cccf q, unsigned int samples);
+struct fxrx_ctx_s *fxrx_qdet_context(qdetector_cccf q);
 
 /* frame generator (test / loopback source) -- /root/reference/lib/flex_tx_impl.cc:51,56,72,188,198-201 */
 typedef struct { unsigned int check, fec0, fec1, mod_scheme; } flexframegenprops_s;
@@ -146,7 +165,10 @@ typedef struct {
     float        threshold;      /* 0 -> default (0.5 flex_rx like liquid's flexframesync, 0.45 detector like
                                     /root/reference/lib/frame_detector_cc_impl.cc:55) */
     unsigned int segment_len;    /* speculation granularity in samples (0 -> auto) */
-    int          want_framesyms; /* copy payload symbols back to the host with each result */
+    int          want_framesyms; /* copy payload symbols back to the host with each result.  Detector mode: every detection carries its 512 aligned
+                                    samples instead (fxrx_frame.framesyms, num_framesyms = 512): x[start, start + 512) of its stream, bit for bit,
+                                    (0, 0) below the stream's zero-floor (index < 0 since create / fxrx_reset) -- what liquid's
+                                    qdetector_cccf_execute returns.  Valid, like payloads, until the next fxrx_collect / fxrx_process */
     int          equalizer;      /* 1: optional equaliser stage on (liquid: FLEXFRAMESYNC_ENABLE_EQ, compiled out of a stock libliquid):
                                     13-tap eqlms at 2 samples/symbol behind the matched filter, trained on the 64 p/n symbols, frozen
                                     afterwards; symbol instants move 3 symbols later.  0 (default): what flexframesync executes */
@@ -178,7 +200,7 @@ typedef struct {
     int          header_valid, payload_valid;
     unsigned char header[20];    /* 14 user bytes + 6 protocol bytes */
     const unsigned char *payload; unsigned int payload_len;
-    const fx_complex *framesyms; unsigned int num_framesyms;   /* host pointer or NULL */
+    const fx_complex *framesyms; unsigned int num_framesyms;   /* host pointer or NULL (detector mode: the aligned window, see want_framesyms) */
     float        evm_db, rssi_db, cfo, evm_sum;
     unsigned int mod_scheme, mod_bps, check, fec0, fec1;
     const unsigned char *soft_bits; unsigned int num_soft_bits;   /* soft_decision + want_framesyms: one byte per coded bit in channel
@@ -288,6 +310,8 @@ typedef struct {
     uint64_t vb_clean;                           /* batch Viterbi: rate-1/2 frames whose coded bits were a codeword as received, decoded without a trellis (FXRX_VB_CLEAN=0: none) */
     uint64_t trellis_launched;                   /* batch Viterbi: 1 when the block's trellis kernels were launched with its chain, 0 when they were left out (clean
                                                   * frames finish in fx_vbpre_kernel; FXRX_VB_EARLY_TAIL=0: always 1) */
+    uint64_t late_windows;                       /* detector mode with want_framesyms: blocks so far whose aligned windows had to be completed at collect (more
+                                                  * detections than window slots were reserved from the previous block's count; FXRX_DETWIN_RESERVE sets the number) */
 } fxrx_timing;
 int fxrx_last_timing(const fxrx_ctx *c, fxrx_timing *t);
 /* Stage times come from HIP events recorded between the kernels of a block, and every event is one more packet in the block's

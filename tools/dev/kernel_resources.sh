@@ -1,7 +1,7 @@
 #!/bin/bash
-# Per-kernel VGPR / SGPR / spill / LDS / occupancy table of fx_kernels.hip, then of fx_ingest.hip, as hipcc compiles them for gfx950.
+# Per-kernel VGPR / SGPR / spill / LDS / occupancy table of fx_kernels.hip, then of fx_ingest.hip and fx_detwin.hip, as hipcc compiles them for gfx950.
 cd "$(dirname "$0")/../../gr-liquiddsp_amd/csrc" || exit 1
-for src in fx_kernels.hip fx_ingest.hip; do
+for src in fx_kernels.hip fx_ingest.hip fx_detwin.hip; do
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math $EXTRA \
   -x hip --cuda-device-only -c $src -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1
 done |
