@@ -294,3 +294,17 @@ static_assert(sizeof(FxPayJob) == 128, "FxPayJob: two 64-byte lines");
 struct FxPayResult {        // diagnostic builds (-DFX_STAMPS) only: shader-clock deltas of the decode phases
     uint32_t stamp[8];
 };
+
+// ---- gang launches: fx_paypll_kernel and fx_vbpre_kernel are as long for the frames of four blocks as for those of one (a lane / a
+// wave per frame, far fewer than the chip has room for), so one launch can serve up to FX_GANG_MAX blocks in flight.  Passed by
+// value; blockIdx.y selects the member, and within it the kernel does what it does for a lone block (n = 1). ----
+#define FX_GANG_MAX 4
+struct FxPllMember {
+    const FxPayJob *jobs; const uint32_t *pll_list; const FxBlockHdr *hdr; const float2 *sym_raw; float2 *framesyms; uint8_t *hard; FxOutRec *recs;
+};
+struct FxPllGang { uint32_t n; FxPllMember m[FX_GANG_MAX]; };
+struct FxVbpreMember {
+    FxPayJob *jobs; const uint32_t *job_idx; const FxBlockHdr *hdr; const uint8_t *hard; uint8_t *bufA, *bufB, *out; FxOutRec *recs; FxBlockHdr *hdr_host;
+    uint32_t first_wave, n_waves;        // the waves this member would have launched alone: blockIdx.x = 0 .. n_waves - 1 stands for job first_wave + blockIdx.x
+};
+struct FxVbpreGang { uint32_t n; FxVbpreMember m[FX_GANG_MAX]; };

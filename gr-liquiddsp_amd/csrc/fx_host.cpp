@@ -64,9 +64,8 @@ extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStre
                                      uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
                                      FxBlockHdr *hdr_host, uint32_t *plan_ws, int fused);
 extern "C" unsigned fx_plan_ws_words(void);
-extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
-                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on, int early_tail, uint8_t *out, FxOutRec *recs,
-                                      FxBlockHdr *hdr_host);
+// (gang launches, fx_common.h: one launch for up to FX_GANG_MAX blocks; members without waves are left out)
+extern "C" hipError_t fx_launch_vbpre(const FxVbpreGang *gang, hipStream_t st, const FxTables *T, int clean_on, int early_tail);
 extern "C" hipError_t fx_launch_vbitems(unsigned first_item, unsigned n_items, hipStream_t st, const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap,
                                         const FxBlockHdr *hdr, uint8_t *bufA, const uint8_t *bufB, unsigned long long *dwv, uint8_t *vec_arena, uint32_t *vb_st, uint32_t dbg, int packed,
                                         int with_fix);
@@ -75,8 +74,7 @@ extern "C" hipError_t fx_launch_vbfinish(unsigned first_wave, unsigned n_waves, 
                                          uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host, int early_tail);
 extern "C" hipError_t fx_launch_paymf(unsigned grid, int eq, hipStream_t st, const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr,
                                       const FxFrame *chain, float2 *sym_raw, const FxTables *T);
-extern "C" hipError_t fx_launch_paypll(unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs, const uint32_t *pll_list, const FxBlockHdr *hdr,
-                                       const float2 *sym_raw, float2 *framesyms, uint8_t *hard, FxOutRec *recs, const FxTables *T);
+extern "C" hipError_t fx_launch_paypll(const FxPllGang *gang, const unsigned *grid_waves, unsigned waves_per_wg, hipStream_t st, const FxTables *T);
 extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host);
@@ -231,6 +229,11 @@ struct Slot {
     int timing_level = 0;                    // which stage events this block recorded (fxrx_set_timing)
     bool inchain = false;                    // the repair round within the chain was enqueued with it
     uint32_t kept_hops = 0, kept_cheap = 0, kept_vhops = 0, kept_vfail = 0, kept_repairs = 0;   // walk-phase counters of a block whose back part was run again
+    // the block's tail -- everything behind the payload matched filter: PLL, decode launches, symbol copy, ev[6..8] --, whose grids are
+    // fixed when the block is submitted; the launches themselves may wait in the context's open gang (launch_tails)
+    unsigned tail_pll_waves = 0, tail_mf_grid = 0; int tail_vb_packed = 0, tail_with_fix = 0;
+    bool tail_launched = true;               // false: deferred -- ev[8] has not been recorded for this block, nobody may wait for it
+    hipStream_t tail_st = nullptr;           // the stream the tail went to (a gang's: its last member's)
 };
 
 struct fxrx_ctx_s {
@@ -289,6 +292,11 @@ struct fxrx_ctx_s {
     // the two routes are equal within the spread up to 1 MB raw, and the kernel read is slower from 2 MB on.
     size_t ingest_kernel_max = 1u << 20;
     float iq_scale[3] = { 1.0f, 1.0f / 32768.0f, 1.0f / 128.0f };   // fxrx_set_iq_scale, indexed by FXRX_IQ_*
+    // FXRX_TAIL_GANG: tails per gang launch (1: off; at most FX_GANG_MAX).  The PLL and fx_vbpre_kernel hold a hardware queue for as
+    // long with one block's frames as with four blocks', and queue time is what bounds the pipeline.
+    unsigned tail_gang = 4;
+    std::vector<Slot *> gang;            // the open gang: blocks in flight whose tails are deferred, oldest first
+    uint64_t gang_launches = 0, gang_members = 0;   // fxrx_debug_gang_stats: tail launches that carried more than one block / the blocks they carried
 };
 
 namespace {
@@ -400,6 +408,7 @@ static int make_slot(fxrx_ctx_s *c)
     return 0;
 }
 
+static int close_gang(fxrx_ctx_s *c);
 static void sync_all(fxrx_ctx_s *c) { if (c->st_chain) (void)hipStreamSynchronize(c->st_chain); for (auto &s : c->slots) if (s->st) (void)hipStreamSynchronize(s->st); }
 
 // FXRX_DEBUG_SUBMIT_PROFILE: where the host time of fxrx_submit goes (printed when a context is destroyed)
@@ -410,6 +419,7 @@ void fxrx_destroy(fxrx_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
+    (void)close_gang(c);
     sync_all(c);
     if (g_prof_on && g_prof_n) {
         std::fprintf(stderr, "[fxrx] submit profile over %lu blocks (ms per block): upload + bookkeeping %.4f, segments %.4f, memory + descriptors %.4f, front launches %.4f, back launches %.4f\n",
@@ -464,6 +474,7 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_PLAN_GRID")) c->plan_grid = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_DETWIN_RESERVE")) c->detwin_reserve = (uint32_t)std::max(0, std::atoi(e));
     if (const char *e = std::getenv("FXRX_VB_DEBUG")) c->vb_debug = (uint32_t)std::atoi(e);
+    if (const char *e = std::getenv("FXRX_TAIL_GANG")) c->tail_gang = (unsigned)std::min(FX_GANG_MAX, std::max(1, std::atoi(e)));
     // (a block is at least as long as the warm-up of the next one: 128 steps)
     if (const char *e = std::getenv("FXRX_VB_BLK")) if (std::atoi(e) > 0) c->vb_blk_force = (uint32_t)std::min(4096, std::max(128, (std::atoi(e) + 63) / 64 * 64));
     hipDeviceProp_t prop;
@@ -495,8 +506,9 @@ void fxrx_reset(fxrx_ctx *c)
 int fxrx_set_depth(fxrx_ctx *c, unsigned int depth)
 {
     if (!c || depth == 0 || depth > kMaxDepth) return FXRX_ERR_ARG;
-    if (c->inflight) { set_err("fxrx_set_depth: blocks in flight"); return FXRX_ERR_STATE; }
     HIP_OK(hipSetDevice(c->cfg.device));
+    { const int r = close_gang(c); if (r) return r; }
+    if (c->inflight) { set_err("fxrx_set_depth: blocks in flight"); return FXRX_ERR_STATE; }
     while (c->slots.size() < depth + 1) if (make_slot(c) != 0) return FXRX_ERR_HIP;
     c->depth = depth; c->head = c->tail = 0; c->last = nullptr;
     return 0;
@@ -516,6 +528,7 @@ int fxrx_set_timing(fxrx_ctx *c, int level)
 {
     if (!c || level < -1 || level > 2) return FXRX_ERR_ARG;
     c->timing_level = level;
+    if (!c->gang.empty()) { HIP_OK(hipSetDevice(c->cfg.device)); return close_gang(c); }
     return 0;
 }
 
@@ -531,10 +544,10 @@ const void *fxrx_device_framesyms(const fxrx_ctx *c, uint64_t *n)
 }
 
 enum { kChainFast = 0, kChainFull = 1, kChainDone = 2 };
-static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t chain_st = nullptr);
+static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t chain_st = nullptr, bool may_defer = false);
 
 // ---- enqueue the whole kernel chain of the block in `sl` (descriptors are rebuilt: a replay calls this again) ----
-static int enqueue_block(fxrx_ctx_s *c, Slot &sl)
+static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
 {
     const unsigned NS = c->cfg.n_streams;
     const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR;
@@ -755,14 +768,110 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl)
     if (late.empty() && c->prev_chain) HIP_OK(hipStreamWaitEvent(cst, c->prev_chain, 0));
     if (c->carry_reader[(b + 1) % 3]) HIP_OK(hipStreamWaitEvent(cst, c->carry_reader[(b + 1) % 3], 0));
     const double tp3 = g_prof_on ? prof_now() : 0.0;
-    const int rb = enqueue_back(c, sl, kChainFast, cst);
+    const int rb = enqueue_back(c, sl, kChainFast, cst, may_defer);
     if (g_prof_on) { const double tp4 = prof_now(); g_prof[1] += tp1 - tp0; g_prof[2] += tp2 - tp1; g_prof[3] += tp3 - tp2; g_prof[4] += tp4 - tp3; g_prof_n++; }
     return rb;
 }
 
+static FxVbpreMember vbpre_member(Slot &sl, uint32_t first_wave, uint32_t n_waves)
+{
+    const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
+    return FxVbpreMember{ sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, sl.d_hdr.p + 1, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p,
+                          first_wave, n_waves };
+}
+// ---- the tails of n blocks (n <= FX_GANG_MAX; n = 1: a block's own tail, on its own stream), on the last one's stream: one PLL
+// launch for all, each block's own decode launches where it has any, one fx_vbpre_kernel launch for all, each block's trellis
+// kernels / fallback decoder / symbol copy, and every block's ev[8] ----
+static int launch_tails(fxrx_ctx_s *c, Slot *const *m, unsigned n)
+{
+    hipStream_t st = m[n - 1]->st;
+    for (unsigned i = 0; i + 1 < n; i++) HIP_OK(hipStreamWaitEvent(st, m[i]->ev[5], 0));      // (the other members' matched filters)
+    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? 2 : 1) : 0;     // (fx_launch_paydec)
+    auto done = [&]() -> int {
+        for (unsigned i = 0; i < n; i++) { HIP_OK(hipEventRecord(m[i]->ev[8], st)); m[i]->tail_launched = true; m[i]->tail_st = st; }
+        if (n > 1) { c->gang_launches++; c->gang_members += n; }
+        return 0;
+    };
+    {
+        FxPllGang g; unsigned waves[FX_GANG_MAX];
+        g.n = n;
+        for (unsigned i = 0; i < n; i++) {
+            Slot &sl = *m[i];
+            g.m[i] = FxPllMember{ sl.d_pjobs.p, sl.d_pll_list.p, sl.d_hdr.p + 1, sl.d_symraw.p, sl.d_symraw.p, sl.d_hard.p, sl.h_recs.p };
+            waves[i] = sl.tail_pll_waves;
+        }
+        HIP_OK(fx_launch_paypll(&g, waves, c->pll_waves, st, c->d_tables));
+    }
+    for (unsigned i = 0; i < n; i++) if (m[i]->timing_level >= 1) HIP_OK(hipEventRecord(m[i]->ev[6], st));
+    if (c->debug_stop_after == 6) return done();
+    for (unsigned i = 0; i < n; i++) {
+        Slot &sl = *m[i];
+        const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
+        FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
+        FxPayResult *pres = nullptr;
+#ifdef FX_STAMPS
+        pres = sl.d_pres.p;
+#endif
+        if (soft) {
+            // per-bit soft values from the carrier-recovered symbols (data parallel, off the PLL's recurrence); the decoder
+            // de-interleaves them in place, so a caller that wants to see them gets a copy first
+            HIP_OK(fx_launch_softdemod(sl.tail_mf_grid, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, hdr_pay, sl.d_symraw.p, sl.d_hard.p, sl.d_soft.p, c->d_tables));
+            if (c->cfg.want_framesyms) HIP_OK(hipMemcpyAsync(sl.h_soft.p, sl.d_soft.p, 8 * sl.byte_cap, hipMemcpyDeviceToHost, st));
+        }
+        // decode, one wave per frame: the lean instance, then the Reed-Solomon instance (which strides)
+        HIP_OK(fx_launch_paydec(0, soft, 0, sl.dec_launched, c->dec_waves, st, sl.d_pjobs.p, sl.d_dec_list.p, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.d_soft.p,
+                                sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
+        HIP_OK(fx_launch_paydec(1, soft, 0, sl.rs_launched, 1u, st, sl.d_pjobs.p, sl.d_dec_list.p + list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p,
+                                sl.d_bufB.p, sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
+    }
+    {
+        FxVbpreGang g; g.n = n;
+        for (unsigned i = 0; i < n; i++) g.m[i] = vbpre_member(*m[i], 0u, m[i]->vb_blk ? m[i]->vb_pre_launched : 0u);
+        HIP_OK(fx_launch_vbpre(&g, st, c->d_tables, c->vb_clean ? 1 : 0, c->vb_early_tail && c->vb_clean ? 1 : 0));
+    }
+    for (unsigned i = 0; i < n; i++) {
+        Slot &sl = *m[i];
+        const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
+        FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
+        FxPayResult *pres = nullptr;
+#ifdef FX_STAMPS
+        pres = sl.d_pres.p;
+#endif
+        if (sl.vb_blk) {
+            HIP_OK(fx_launch_vbitems(0, sl.vb_items_launched, st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p,
+                                     sl.d_vb_st.p, c->vb_debug, sl.tail_vb_packed, sl.tail_with_fix));
+            HIP_OK(fx_launch_vbfinish(0, sl.vb_fin_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
+                                      sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0));
+            HIP_OK(fx_launch_paydec(0, 0, 0, sl.fb_launched, 1u, st, sl.d_pjobs.p, sl.d_dec_list.p + 3 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
+                                    sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, sl.h_hdr.p));
+        }
+        if (sl.timing_level >= 2) HIP_OK(hipEventRecord(sl.ev[7], st));
+        // (a copy kernel: it knows how many symbols the block really holds)
+        if (c->cfg.want_framesyms)
+            HIP_OK(fx_launch_symcopy(2u * (unsigned)c->n_cus, st, hdr_pay, sl.d_symraw.p, sl.h_framesyms.p));
+    }
+    return done();
+}
+
+// launch what the open gang holds (nothing: no-op).  Called when the gang is full, and before anything that waits for a member's
+// ev[8], moves what the members read, or changes what a submit means.
+// If a launch fails part-way the gang is empty all the same and its members stay without a tail (tail_launched false: nobody
+// waits on their ev[8]).  The HIP error goes up to the caller; fxrx_collect, when it reaches such a member, reports a block
+// without a tail and drops everything in flight (discard_inflight).  Not mended further: a HIP error at launch is fatal to
+// the context, every later call fails the same way.
+static int close_gang(fxrx_ctx_s *c)
+{
+    if (c->gang.empty()) return 0;
+    if (c->gang.size() > FX_GANG_MAX) { set_err("open gang larger than FX_GANG_MAX (internal error)"); return FXRX_ERR_STATE; }   // (the deferral rule closes it at tail_gang <= FX_GANG_MAX)
+    Slot *m[FX_GANG_MAX]; unsigned n = 0;
+    for (Slot *s : c->gang) m[n++] = s;
+    c->gang.clear();
+    return launch_tails(c, m, n);
+}
+
 // ---- back part of the chain: chain kernel, plan, payload stage.  `full`: the full-size chain kernel, which can walk
 // (fxrx_collect runs it for a block whose lean chain kernel reported FX_BLK_NEEDS_REPAIR) ----
-static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t chain_st)
+static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t chain_st, bool may_defer)
 {
     const unsigned NS = c->cfg.n_streams;
     const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR;
@@ -773,6 +882,7 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
     const FxStreamDesc *d_streams = reinterpret_cast<const FxStreamDesc *>(sl.d_desc.p + sl.o_streams);
     const uint32_t chain_slots = sl.chain_cap, list_cap = chain_slots + 64 * FX_PLL_CLASSES;
     FxBlockHdr *hdr = sl.d_hdr.p, *hdr_pay = sl.d_hdr.p + 1;
+    sl.tail_launched = true; sl.tail_st = st;
     if (chain_mode == kChainFull)
         HIP_OK(fx_launch_chain(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, NS, st, d_streams, d_jobs, (uint32_t)sl.NJ, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, sl.d_runs.p, sl.run_cap,
                                hdr, c->chain_slow ? 1u : 0u, c->d_tables));
@@ -817,24 +927,9 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         HIP_OK(hipEventRecord(sl.ev[5], st));
         c->carry_reader[b % 3] = sl.ev[5];
         if (c->debug_stop_after == 5) { HIP_OK(hipEventRecord(sl.ev[8], st)); return 0; }
-        HIP_OK(fx_launch_paypll((unsigned)(fh / 64 + FX_PLL_CLASSES), c->pll_waves, st, sl.d_pjobs.p, sl.d_pll_list.p, hdr_pay, sl.d_symraw.p, sl.d_symraw.p,
-                                sl.d_hard.p, sl.h_recs.p, c->d_tables));
-        if (tl >= 1) HIP_OK(hipEventRecord(sl.ev[6], st));
-        if (c->debug_stop_after == 6) { HIP_OK(hipEventRecord(sl.ev[8], st)); return 0; }
-        FxPayResult *pres = nullptr;
-#ifdef FX_STAMPS
-        pres = sl.d_pres.p;
-#endif
-        // decode: one wave per frame.  The lean instance has no loop (it would double its registers): its grid covers what
-        // the last block held plus a margin, and a second, usually empty launch covers the rest of the list's capacity in
-        // big workgroups (few of them).  The Reed-Solomon instance strides.
-        const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? 2 : 1) : 0;     // (fx_launch_paydec)
-        if (soft) {
-            // per-bit soft values from the carrier-recovered symbols (data parallel, off the PLL's recurrence); the decoder
-            // de-interleaves them in place, so a caller that wants to see them gets a copy first
-            HIP_OK(fx_launch_softdemod(mf_grid, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, hdr_pay, sl.d_symraw.p, sl.d_hard.p, sl.d_soft.p, c->d_tables));
-            if (c->cfg.want_framesyms) HIP_OK(hipMemcpyAsync(sl.h_soft.p, sl.d_soft.p, 8 * sl.byte_cap, hipMemcpyDeviceToHost, st));
-        }
+        // ---- the block's tail: its grids now (they stride over lists whose lengths only the device knows, sized from what the last
+        // collected block held), its launches now or with the gang (launch_tails) ----
+        sl.tail_pll_waves = (unsigned)(fh / 64 + FX_PLL_CLASSES); sl.tail_mf_grid = mf_grid;
         // decode: one wave per frame.  The lean instance has no loop (it would double its registers) and an empty workgroup
         // still has to be given its registers before it can leave: so the grid covers what the last block held plus a margin,
         // not the list's capacity, and the Reed-Solomon instance (256 registers a wave) is only launched while such frames
@@ -842,39 +937,38 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         // (the plain instance too is only launched while such frames keep turning up: with the batch path on, a block normally has none)
         sl.dec_launched = c->first_block ? chain_slots : (c->plain_hint || !sl.vb_blk ? (unsigned)std::min<uint64_t>(chain_slots, c->plain_hint + c->plain_hint / 2 + 64) : 0u);
         sl.rs_launched = c->rs_hint ? (unsigned)std::min<uint64_t>(chain_slots, c->rs_hint + c->rs_hint / 2 + 64) : 0u;
-        HIP_OK(fx_launch_paydec(0, soft, 0, sl.dec_launched, c->dec_waves, st, sl.d_pjobs.p, sl.d_dec_list.p, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.d_soft.p,
-                                sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
-        HIP_OK(fx_launch_paydec(1, soft, 0, sl.rs_launched, 1u, st, sl.d_pjobs.p, sl.d_dec_list.p + list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p,
-                                sl.d_bufB.p, sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
         // batch Viterbi path (most frames: hard decisions, convolutional fec0): front part, forward pass over trellis blocks, back part
         if (sl.vb_blk) {
             sl.vb_pre_launched = c->first_block ? chain_slots : (unsigned)std::min<uint64_t>(chain_slots, c->batch_hint + c->batch_hint / 2 + 64);
             // (two work items per lane once the items fill the chip or other blocks do; one per lane for a lone small block)
-            const int vb_packed = (c->depth > 1 || c->vb_items_hint > 64ull * 4ull * (uint64_t)c->n_cus * 3ull / 2ull) ? 1 : 0;
+            sl.tail_vb_packed = (c->depth > 1 || c->vb_items_hint > 64ull * 4ull * (uint64_t)c->n_cus * 3ull / 2ull) ? 1 : 0;
+            sl.tail_with_fix = (c->first_block || c->vbfix_hint || c->vb_debug) ? 1 : 0;
             // (the trellis kernels: always without the early tail; with it, while the traffic has frames for them)
             sl.vb_early = c->vb_early_tail && c->vb_clean;
             const bool trellis = !sl.vb_early || c->first_block || c->vb_debug || c->trellis_left > 0;
             if (c->trellis_left) c->trellis_left--;
             sl.vb_items_launched = !trellis ? 0u : c->first_block ? sl.vb_cap : (unsigned)std::min<uint64_t>(sl.vb_cap, c->vb_items_hint + c->vb_items_hint / 2 + 1024);
             sl.vb_fin_launched = trellis ? sl.vb_pre_launched : 0u;
-            HIP_OK(fx_launch_vbpre(0, sl.vb_pre_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0,
-                                   sl.vb_early ? 1 : 0, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p));
-            HIP_OK(fx_launch_vbitems(0, sl.vb_items_launched, st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p,
-                                     sl.d_vb_st.p, c->vb_debug, vb_packed, (c->first_block || c->vbfix_hint || c->vb_debug) ? 1 : 0));
-            HIP_OK(fx_launch_vbfinish(0, sl.vb_fin_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
-                                      sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0));
             // frames whose hand-overs could not be verified (a block that ran again and ended differently): the wave-per-frame decoder,
             // launched with the chain only while such frames keep turning up (the count reaches the host either way; what a launch
             // did not cover is decoded when the block is collected)
             sl.fb_launched = trellis && (c->first_block || c->fb_hint || c->vb_debug) ? (uint32_t)std::min<uint64_t>(chain_slots, std::max<uint64_t>(kFallbackWaves, c->fb_hint + c->fb_hint / 2 + 16)) : 0u;
-            HIP_OK(fx_launch_paydec(0, 0, 0, sl.fb_launched, 1u, st, sl.d_pjobs.p, sl.d_dec_list.p + 3 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
-                                    sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, sl.h_hdr.p));
-        } else { sl.vb_pre_launched = sl.vb_items_launched = sl.vb_fin_launched = sl.fb_launched = 0; sl.vb_early = false; }
+        } else { sl.vb_pre_launched = sl.vb_items_launched = sl.vb_fin_launched = sl.fb_launched = 0; sl.vb_early = false; sl.tail_vb_packed = sl.tail_with_fix = 0; }
         sl.timing.trellis_launched = sl.vb_fin_launched ? 1 : 0;
-        if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[7], st));
-        // (a copy kernel: it knows how many symbols the block really holds)
-        if (c->cfg.want_framesyms)
-            HIP_OK(fx_launch_symcopy(2u * (unsigned)c->n_cus, st, hdr_pay, sl.d_symraw.p, sl.h_framesyms.p));
+        // Deferred into the open gang when there is enough ahead of this block to keep the queues busy meanwhile: a deep pipeline
+        // (depth >= 4), the traffic known (not the first block), no more events than the PLL's pair, and at least a gang's worth of
+        // blocks in flight in front of it whose tails are out.  Anything else goes at once, alone, behind whatever the gang holds.
+        unsigned ahead = 0;
+        for (unsigned k = 0; k < c->inflight; k++) ahead += c->slots[(c->tail + k) % (c->depth + 1)]->tail_launched ? 1u : 0u;
+        const unsigned G = c->tail_gang;
+        if (G >= 2 && may_defer && c->depth >= 4 && !c->first_block && !c->debug_stop_after && tl <= 1 && ahead >= G) {
+            sl.tail_launched = false; sl.tail_st = nullptr;
+            c->gang.push_back(&sl);
+            return c->gang.size() >= G ? close_gang(c) : 0;
+        }
+        { const int r = close_gang(c); if (r) return r; }
+        Slot *one = &sl;
+        return launch_tails(c, &one, 1u);
     } else {
         // (in front of the event the next-but-one block's chain kernel waits for before it writes over the carried tail this one reads)
         if (c->cfg.want_framesyms)
@@ -975,7 +1069,7 @@ static int submit_block(fxrx_ctx *c, const void *const *iq, const uint64_t *n_sa
     sl.timing.samples = total_new;
     if (c->debug_fail_submit) { c->debug_fail_submit--; set_err("fxrx_submit: injected failure (fxrx_debug_fail)"); return FXRX_ERR_STATE; }
     if (g_prof_on) g_prof[0] += prof_now() - std::chrono::duration<double, std::milli>(t_enter.time_since_epoch()).count();
-    int r = enqueue_block(c, sl);
+    int r = enqueue_block(c, sl, /* may_defer */ true);
     if (r) return r;
     undo.armed = false;
     c->seq++;
@@ -1075,9 +1169,16 @@ static int repair_and_replay(fxrx_ctx_s *c, Slot &sl)
     }
     const hipEvent_t newest_chain = c->prev_chain;
     bool carry_moved = false;
+    // (blocks behind this one may sit in the open gang: their tails go out now, so that every block in flight is on streams that
+    // can be drained; the tails enqueued from here are replays and go alone)
+    { const int r = close_gang(c); if (r) return r; }
     for (int round = 0; round < 6; round++) {
         HIP_OK(hipStreamSynchronize(sl.st));
-        for (unsigned k = 1; k <= n_dep; k++) HIP_OK(hipStreamSynchronize(c->slots[(c->tail + k) % nslots]->st));
+        for (unsigned k = 1; k <= n_dep; k++) {
+            const Slot &nx = *c->slots[(c->tail + k) % nslots];
+            HIP_OK(hipStreamSynchronize(nx.st));
+            if (nx.tail_st && nx.tail_st != nx.st) HIP_OK(hipStreamSynchronize(nx.tail_st));      // (its tail ran with a gang, on another block's stream)
+        }
         const uint32_t flags = sl.h_hdr.p->flags;
         if (std::getenv("FXRX_DEBUG_ROUNDS")) std::fprintf(stderr, "[fxrx] block %llu at collect: flags %x verify_failures %u (pass %d)\n", (unsigned long long)sl.seq, flags, sl.h_hdr.p->verify_failures, round);
         if (flags & FX_BLK_NEEDS_REPAIR) {
@@ -1176,8 +1277,10 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     if (more_batch || late_trellis) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
         HIP_OK(hipMemsetAsync(&hdr_pay->n_vb_fallback, 0, sizeof(uint32_t), sl.st));
         if (more_batch)
-            HIP_OK(fx_launch_vbpre(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, c->d_tables, c->vb_clean ? 1 : 0,
-                                   sl.vb_early ? 1 : 0, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p));
+        {
+            FxVbpreGang g; g.n = 1; g.m[0] = vbpre_member(sl, 0u, h.n_dec_batch);
+            HIP_OK(fx_launch_vbpre(&g, sl.st, c->d_tables, c->vb_clean ? 1 : 0, sl.vb_early ? 1 : 0));
+        }
         HIP_OK(fx_launch_vbitems(0, h.n_vb_items, sl.st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, c->vb_debug, 1, 1));
         HIP_OK(fx_launch_vbfinish(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
                                   sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0));
@@ -1223,6 +1326,7 @@ static int finish_windows(fxrx_ctx_s *c, Slot &sl)
 static void discard_inflight(fxrx_ctx_s *c)
 {
     const std::string keep = g_err;
+    (void)close_gang(c);
     sync_all(c);
     const unsigned nslots = c->depth + 1;
     while (c->inflight) {
@@ -1252,15 +1356,27 @@ int fxrx_collect(fxrx_ctx *c)
     return r;
 }
 
-int fxrx_ready(const fxrx_ctx *c)
+int fxrx_ready(fxrx_ctx *c)
 {
     if (!c) return FXRX_ERR_ARG;
     if (!c->inflight) return 0;
+    if (!c->slots[c->tail]->tail_launched) {                   // still in the open gang: out with it, or a caller that polls would wait for ever
+        if (hipSetDevice(c->cfg.device) != hipSuccess || close_gang(c)) return FXRX_ERR_HIP;
+    }
     const hipError_t e = hipEventQuery(c->slots[c->tail]->ev[8]);
     return e == hipSuccess ? 1 : (e == hipErrorNotReady ? 0 : FXRX_ERR_HIP);
 }
 
 unsigned int fxrx_inflight(const fxrx_ctx *c) { return c ? c->inflight : 0; }
+
+int fxrx_debug_gang_stats(const fxrx_ctx *c, uint64_t out[2])
+{
+    if (!c || !out) return FXRX_ERR_ARG;
+    out[0] = c->gang_launches; out[1] = c->gang_members;
+    return 0;
+}
+
+int fxrx_debug_gang_open(const fxrx_ctx *c) { return c ? (int)c->gang.size() : FXRX_ERR_ARG; }
 
 int fxrx_debug_fail(fxrx_ctx *c, unsigned int submits, unsigned int collects)
 {
@@ -1332,7 +1448,12 @@ static int collect_block(fxrx_ctx_s *c)
     const unsigned nslots = c->depth + 1;
     Slot &sl = *c->slots[c->tail];
     const auto tw = std::chrono::steady_clock::now();
+    // (a block whose tail is still deferred has no ev[8] to wait for: waiting on the event as an earlier use left it would return at once)
+    if (!sl.tail_launched) { const int r = close_gang(c); if (r) return r; }
+    if (!sl.tail_launched) { set_err("fxrx_collect: block without a tail (internal error)"); return FXRX_ERR_STATE; }
     HIP_OK(hipEventSynchronize(sl.ev[8]));
+    // what collect still enqueues for this block goes to its own stream: behind the tail, wherever that ran
+    if (sl.tail_st != sl.st) { HIP_OK(hipStreamWaitEvent(sl.st, sl.ev[8], 0)); sl.tail_st = sl.st; }
     if (c->debug_fail_collect) { c->debug_fail_collect--; set_err("fxrx_collect: injected failure (fxrx_debug_fail)"); return FXRX_ERR_STATE; }
     {
         const uint32_t flags = sl.h_hdr.p->flags;

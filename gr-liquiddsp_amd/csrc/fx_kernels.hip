@@ -2667,10 +2667,13 @@ __device__ __forceinline__ void pll_frame(uint32_t f, const FxPayJob *jobs, cons
 // One kernel for all modulation schemes: fx_plan_kernel lists the frames per scheme, each list padded to whole waves, so
 // a wave runs exactly one instantiation of the loop (the demodulator is resolved at compile time, straight-line code).
 // The number of waves is only known on the device: the grid strides over them.
+// One launch serves the blocks of a gang (FxPllGang, fx_common.h): blockIdx.y is the member, the grid's x extent the largest any
+// member asked for; a lone block is a gang of one.
 __global__ __launch_bounds__(PLL_THREADS * PLL_MAX_WAVES)
-void fx_paypll_kernel(const FxPayJob *jobs, const uint32_t *pll_list, const FxBlockHdr *hdr, const float2 *sym_raw,
-                      float2 *framesyms, uint8_t *hard, FxOutRec *recs, const FxTables *T)
+void fx_paypll_kernel(const FxPllGang g, const FxTables *T)
 {
+    const FxPllMember m = g.m[blockIdx.y];
+    const FxBlockHdr *hdr = m.hdr;
     const uint32_t nw = hdr->pll_base[FX_PLL_CLASSES] >> 6;
     const uint32_t wpg = blockDim.x >> 6, w0 = blockIdx.x * wpg + (threadIdx.x >> 6);
     if (blockIdx.x * wpg >= nw) return;
@@ -2685,25 +2688,29 @@ void fx_paypll_kernel(const FxPayJob *jobs, const uint32_t *pll_list, const FxBl
         uint32_t cls = 0;
         while (cls + 1 < FX_PLL_CLASSES && (w << 6) >= hdr->pll_base[cls + 1]) cls++;
         cls = __builtin_amdgcn_readfirstlane(cls);
-        const uint32_t f = pll_list[(w << 6) + lane];
-#define FX_PLL_CASE(C, M) case C: pll_frame<M>(f, jobs, sc, sym_raw, framesyms, hard, recs); break;
+        const uint32_t f = m.pll_list[(w << 6) + lane];
+#define FX_PLL_CASE(C, M) case C: pll_frame<M>(f, m.jobs, sc, m.sym_raw, m.framesyms, m.hard, m.recs); break;
         switch (cls) {
             FX_PLL_CASE(0, FX_MODEM_PSK2) FX_PLL_CASE(1, FX_MODEM_PSK4) FX_PLL_CASE(2, FX_MODEM_PSK8) FX_PLL_CASE(3, FX_MODEM_PSK16)
             FX_PLL_CASE(4, FX_MODEM_DPSK2) FX_PLL_CASE(5, FX_MODEM_DPSK4) FX_PLL_CASE(6, FX_MODEM_DPSK8) FX_PLL_CASE(7, FX_MODEM_ASK4)
             FX_PLL_CASE(8, FX_MODEM_QAM16) FX_PLL_CASE(9, FX_MODEM_QAM32) FX_PLL_CASE(10, FX_MODEM_QAM64)
-            default: pll_frame<FX_MODEM_QPSK>(f, jobs, sc, sym_raw, framesyms, hard, recs); break;
+            default: pll_frame<FX_MODEM_QPSK>(f, m.jobs, sc, m.sym_raw, m.framesyms, m.hard, m.recs); break;
         }
 #undef FX_PLL_CASE
     }
 }
 
-// host-side launcher
-extern "C" hipError_t fx_launch_paypll(unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs, const uint32_t *pll_list, const FxBlockHdr *hdr,
-                                       const float2 *sym_raw, float2 *framesyms, uint8_t *hard, FxOutRec *recs, const FxTables *T)
+// host-side launcher.  grid_waves[i]: the waves member i would have launched alone (0: nothing of it to do; the member is left out)
+extern "C" hipError_t fx_launch_paypll(const FxPllGang *gang, const unsigned *grid_waves, unsigned waves_per_wg, hipStream_t st, const FxTables *T)
 {
-    if (grid_waves == 0) return hipSuccess;
+    if (gang->n > FX_GANG_MAX) return hipErrorInvalidValue;
+    FxPllGang g; g.n = 0;
+    unsigned gw = 0;
+    for (uint32_t i = 0; i < gang->n; i++) if (grid_waves[i]) { g.m[g.n++] = gang->m[i]; gw = grid_waves[i] > gw ? grid_waves[i] : gw; }
+    if (g.n == 0) return hipSuccess;
+    for (uint32_t i = g.n; i < FX_GANG_MAX; i++) g.m[i] = g.m[0];
     const unsigned w = waves_per_wg < 1u ? 1u : (waves_per_wg > PLL_MAX_WAVES ? PLL_MAX_WAVES : waves_per_wg);
-    hipLaunchKernelGGL(fx_paypll_kernel, dim3((grid_waves + w - 1) / w), dim3(PLL_THREADS * w), 0, st, jobs, pll_list, hdr, sym_raw, framesyms, hard, recs, T);
+    hipLaunchKernelGGL(fx_paypll_kernel, dim3((gw + w - 1) / w, g.n), dim3(PLL_THREADS * w), 0, st, g, T);
     return hipGetLastError();
 }
 
@@ -4300,15 +4307,19 @@ __device__ __forceinline__ bool vb_clean_check(FxPayJob *jobs, uint32_t jf, uint
 // host launches the trellis kernels with the chain only while such frames keep turning up, and otherwise when it collects a block
 // whose flag is up (fx_host.cpp).  early_tail == 0: the tail of every frame is fx_vbfinish_kernel's.
 extern "C" __global__ __launch_bounds__(DEC_THREADS)
-void fx_vbpre_kernel(FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB,
-                     const FxTables *T, uint32_t clean_on, uint32_t early_tail, uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host)
+void fx_vbpre_kernel(const FxVbpreGang g, const FxTables *T, uint32_t clean_on, uint32_t early_tail)
 {
     __shared__ __attribute__((aligned(16))) uint8_t X[VBPRE_LDS];
-    const uint32_t njobs = hdr->n_dec_batch;
-    const uint32_t ji = first_wave + blockIdx.x;
+    // (a gang of blocks, FxVbpreGang in fx_common.h: blockIdx.y is the member, the grid's x extent the largest member's)
+    const FxVbpreMember m = g.m[blockIdx.y];
+    if (blockIdx.x >= m.n_waves) return;
+    const uint32_t njobs = m.hdr->n_dec_batch;
+    const uint32_t ji = m.first_wave + blockIdx.x;
     if (ji >= njobs) return;
+    FxPayJob *jobs = m.jobs; const uint8_t *hard = m.hard; uint8_t *bufA = m.bufA, *bufB = m.bufB, *out = m.out;
+    FxOutRec *recs = m.recs; FxBlockHdr *hdr_host = m.hdr_host;
     const int lane = threadIdx.x & 63;
-    const uint32_t jf = job_idx[ji];
+    const uint32_t jf = m.job_idx[ji];
     FxPayJob job = jobs[jf];
     job.l0 = __builtin_amdgcn_readfirstlane(job.l0); job.l1 = __builtin_amdgcn_readfirstlane(job.l1);
     job.fec1 = __builtin_amdgcn_readfirstlane(job.fec1); job.bps = __builtin_amdgcn_readfirstlane(job.bps);
@@ -4406,13 +4417,16 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
     dec_tail(job, jf, A, lane, out, recs, rep << 8);
 }
 
-extern "C" hipError_t fx_launch_vbpre(unsigned first_wave, unsigned n_waves, hipStream_t st, FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr,
-                                      const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, const FxTables *T, int clean_on, int early_tail, uint8_t *out, FxOutRec *recs,
-                                      FxBlockHdr *hdr_host)
+// (members without waves are left out)
+extern "C" hipError_t fx_launch_vbpre(const FxVbpreGang *gang, hipStream_t st, const FxTables *T, int clean_on, int early_tail)
 {
-    if (n_waves == 0) return hipSuccess;
-    hipLaunchKernelGGL(fx_vbpre_kernel, dim3(n_waves), dim3(DEC_THREADS), 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, T, clean_on ? 1u : 0u,
-                       early_tail ? 1u : 0u, out, recs, hdr_host);
+    if (gang->n > FX_GANG_MAX) return hipErrorInvalidValue;
+    FxVbpreGang g; g.n = 0;
+    unsigned gw = 0;
+    for (uint32_t i = 0; i < gang->n; i++) if (gang->m[i].n_waves) { g.m[g.n++] = gang->m[i]; gw = gang->m[i].n_waves > gw ? gang->m[i].n_waves : gw; }
+    if (g.n == 0) return hipSuccess;
+    for (uint32_t i = g.n; i < FX_GANG_MAX; i++) g.m[i] = g.m[0];
+    hipLaunchKernelGGL(fx_vbpre_kernel, dim3(gw, g.n), dim3(DEC_THREADS), 0, st, g, T, clean_on ? 1u : 0u, early_tail ? 1u : 0u);
     return hipGetLastError();
 }
 // forward pass, [hand-over check,] traceback: the lane-per-work-item kernels, over the same item slots

@@ -129,6 +129,20 @@ class RxContext:
         if self.L.fxrx_set_timing(self.h, int(level)) != 0:
             raise RxError("fxrx_set_timing: bad level")
 
+    def gang_stats(self):
+        """(tail launches so far that served more than one block in flight, blocks they carried): see fxrx_debug_gang_stats."""
+        out = (C.c_uint64 * 2)()
+        if self.L.fxrx_debug_gang_stats(self.h, C.byref(out)) != 0:
+            raise RxError("fxrx_debug_gang_stats failed")
+        return int(out[0]), int(out[1])
+
+    def gang_open(self):
+        """Blocks in flight whose tails are deferred at this moment: see fxrx_debug_gang_open."""
+        n = self.L.fxrx_debug_gang_open(self.h)
+        if n < 0:
+            raise RxError("fxrx_debug_gang_open failed")
+        return int(n)
+
     def submit_raw(self, ptrs, counts, on_device, fmt=0):
         n = self.n_streams
         a = (C.c_void_p * n)(*ptrs)

@@ -270,11 +270,17 @@ int fxrx_process_fmt(fxrx_ctx *c, const void *const *iq, const uint64_t *n_sampl
  * out_re_im.  FXRX_IQ_FC32 copies.  Returns 0, or FXRX_ERR_ARG for an unknown format or a NULL pointer */
 int fxrx_iq_convert_host(int fmt, float scale, const void *in, uint64_t n_samples, float *out_re_im);
 /* 1: the oldest block in flight has finished (fxrx_collect will not wait), 0: not yet / nothing in flight, < 0: FXRX_ERR_* */
-int fxrx_ready(const fxrx_ctx *c);
+/* (a block whose tail waits in an open gang, FXRX_TAIL_GANG, is launched by this call: hence no const) */
+int fxrx_ready(fxrx_ctx *c);
 unsigned int fxrx_inflight(const fxrx_ctx *c);
 /* tests: make the next `submits` calls of fxrx_submit / `collects` calls of fxrx_collect fail (FXRX_ERR_STATE) after they have
  * done their bookkeeping, to exercise the paths above */
 int fxrx_debug_fail(fxrx_ctx *c, unsigned int submits, unsigned int collects);
+/* tests: out[0] = tail launches so far that served more than one block in flight (the payload PLL and the decode front of up to four
+ * blocks in one launch each: FXRX_TAIL_GANG, 1 = off; only with fxrx_set_depth >= 4), out[1] = the blocks they carried */
+int fxrx_debug_gang_stats(const fxrx_ctx *c, uint64_t out[2]);
+/* tests: blocks in flight whose tails are deferred at this moment (the open gang's members; 0 .. 3) */
+int fxrx_debug_gang_open(const fxrx_ctx *c);
 /* tests: run the walker's header decoder on the GPU over n headers given in host memory.  soft != 0: `in` holds 432 soft values per
  * header (0 = surely 0 ... 255 = surely 1) in channel order, before the header's first de-interleaver; soft == 0: the 54 received bytes.
  * Writes 20 decoded bytes per header to out20 and the CRC-32 verdict (1 / 0) to valid[i].  Synchronous, on the current HIP device;
