@@ -128,6 +128,13 @@ def table(name, n, complex_=True):
     return a.view(np.complex64) if complex_ else a
 
 
+def eq_init_taps():
+    """The 13 start taps of the optional equaliser (fxr_eq_init_taps), as data."""
+    out = np.empty(13, np.float32)
+    lib().fxr_eq_init_taps(out.ctypes.data)
+    return out
+
+
 def fft512(x, inverse=False):
     x = np.ascontiguousarray(x, dtype=np.complex64)
     out = np.empty(512, np.complex64)
