@@ -46,6 +46,10 @@ class Config(C.Structure):                  # fxrx_config
                 ("soft_header", C.c_int), ("soft_block", C.c_int)]
 
 
+class ConfigChain(Config):                  # the whole fxrx_config: Config is its part up to soft_block; fxrx_create takes this one
+    _fields_ = [("soft_chain", C.c_int)]
+
+
 class Frame(C.Structure):                   # fxrx_frame
     _fields_ = [("stream", C.c_uint), ("start", C.c_int64), ("cfo_bin", C.c_int),
                 ("rxy", C.c_float), ("tau", C.c_float), ("gamma", C.c_float), ("dphi", C.c_float), ("phi", C.c_float),
@@ -88,6 +92,7 @@ EXPORTS = [
     "fxtx_create", "fxtx_destroy", "fxtx_frame_len", "fxtx_generate",
     "fxtx_apply_channel", "fxrx_set_timing", "fxrx_debug_block_times", "fxrx_ready", "fxrx_inflight", "fxrx_debug_fail", "fxrx_debug_gang_stats", "fxrx_debug_gang_open", "fxrx_pinned_alloc", "fxrx_pinned_free", "fxrx_sync_context",
     "fxrx_debug_header_decode", "fxrx_debug_block_decode", "fxrx_sync_set_soft_block",
+    "fxrx_debug_block_siso", "fxrx_sync_set_soft_chain",
     "fxrx_sync_set_streaming", "fxrx_qdet_flush", "fxrx_qdet_pending", "fxrx_qdet_set_block", "fxrx_qdet_context",
     "fxrx_iq_sample_bytes", "fxrx_set_iq_scale", "fxrx_submit_fmt", "fxrx_process_fmt", "fxrx_iq_convert_host", "fxtx_quantize",
 ]
@@ -230,6 +235,9 @@ def lib():
     L.fxrx_sync_set_equalizer.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_equalizer.restype = None
     L.fxrx_sync_set_soft.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft.restype = None
     L.fxrx_sync_set_soft_block.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_block.restype = C.c_int
+    L.fxrx_sync_set_soft_chain.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_chain.restype = C.c_int
+    L.fxrx_debug_block_siso.restype = C.c_int
+    L.fxrx_debug_block_siso.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
     L.flexframesync_decode_header_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_header_soft.restype = C.c_int
     L.flexframesync_decode_payload_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_payload_soft.restype = C.c_int
     L.fxrx_sync_pending.argtypes = [C.c_void_p]; L.fxrx_sync_pending.restype = C.c_uint

@@ -56,6 +56,7 @@ extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, int sh, unsigned ns
                                       FxBlockHdr *hdr, uint32_t force_slow, const FxTables *T);
 extern "C" hipError_t fx_launch_hdrdec(int soft, unsigned n, hipStream_t st, const uint8_t *in, uint8_t *out, int32_t *valid, const FxTables *T);
 extern "C" hipError_t fx_launch_blkdec(int soft, unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T);
+extern "C" hipError_t fx_launch_blksiso(unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T);
 extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, const FxWalkResult *results,
                                           const FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxBlockHdr *hdr, uint32_t force_repair,
                                           FxWalkJob *jobs_rw, uint32_t *req_list, uint32_t *stat, uint32_t pass);
@@ -445,6 +446,9 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (cfg->soft_block && (cfg->mode == FXRX_MODE_DETECTOR || !cfg->soft_decision)) {
         set_err("fxrx_create: soft_block needs soft_decision and flex_rx mode (FXRX_ERR_ARG)"); return nullptr;
     }
+    if (cfg->soft_chain && (cfg->mode == FXRX_MODE_DETECTOR || !cfg->soft_decision || !cfg->soft_block)) {
+        set_err("fxrx_create: soft_chain needs soft_block, soft_decision and flex_rx mode (FXRX_ERR_ARG)"); return nullptr;
+    }
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || cfg->device >= nd) {
         set_err("fxrx_create: no usable HIP device (this library has no CPU path)"); return nullptr;
@@ -786,7 +790,7 @@ static int launch_tails(fxrx_ctx_s *c, Slot *const *m, unsigned n)
 {
     hipStream_t st = m[n - 1]->st;
     for (unsigned i = 0; i + 1 < n; i++) HIP_OK(hipStreamWaitEvent(st, m[i]->ev[5], 0));      // (the other members' matched filters)
-    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? 2 : 1) : 0;     // (fx_launch_paydec)
+    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? (c->cfg.soft_chain ? 3 : 2) : 1) : 0;     // (fx_launch_paydec)
     auto done = [&]() -> int {
         for (unsigned i = 0; i < n; i++) { HIP_OK(hipEventRecord(m[i]->ev[8], st)); m[i]->tail_launched = true; m[i]->tail_st = st; }
         if (n > 1) { c->gang_launches++; c->gang_members += n; }
@@ -1263,7 +1267,7 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     if (!more_plain && !more_rs && !more_batch && !more_fb && !late_trellis) return 0;
     const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
     FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
-    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? 2 : 1) : 0;     // (fx_launch_paydec)
+    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? (c->cfg.soft_chain ? 3 : 2) : 1) : 0;     // (fx_launch_paydec)
     FxPayResult *pres = nullptr;
 #ifdef FX_STAMPS
     pres = sl.d_pres.p;
@@ -1434,6 +1438,33 @@ int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned
         HIP_OK(fx_launch_blkdec(soft ? 1 : 0, fec, n, count, nullptr, d_in, d_out, d_t));
         HIP_OK(hipDeviceSynchronize());
         HIP_OK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out }) if (p) (void)hipFree(p);
+    return rc;
+}
+
+int fxrx_debug_block_siso(unsigned int fec, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out_soft)
+{
+    const bool block = fec == FX_FEC_HAMMING74 || fec == FX_FEC_HAMMING84 || fec == FX_FEC_HAMMING128 || fec == FX_FEC_GOLAY2412 ||
+                       fec == FX_FEC_SECDED2216 || fec == FX_FEC_SECDED3932 || fec == FX_FEC_SECDED7264;
+    if (!block || !in || !out_soft || n == 0 || n > 65535) { set_err("fxrx_debug_block_siso: bad argument"); return FXRX_ERR_ARG; }
+    if (count == 0) return 0;
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_err("fxrx_debug_block_siso: no usable HIP device"); return FXRX_ERR_NODEVICE; }
+    const size_t in_bytes = (size_t)count * fx::fec_enc_len(fec, n) * 8, out_bytes = (size_t)count * n * 8;
+    std::unique_ptr<FxTables> t = make_tables();
+    FxTables *d_t = nullptr; uint8_t *d_in = nullptr, *d_out = nullptr;
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void **)&d_t, sizeof(FxTables)));
+        HIP_OK(hipMalloc((void **)&d_in, in_bytes + 16));                // (the decoders load whole words)
+        HIP_OK(hipMalloc((void **)&d_out, out_bytes));
+        HIP_OK(hipMemcpy(d_t, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
+        HIP_OK(fx_launch_blksiso(fec, n, count, nullptr, d_in, d_out, d_t));
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipMemcpy(out_soft, d_out, out_bytes, hipMemcpyDeviceToHost));
         return 0;
     };
     const int rc = run();

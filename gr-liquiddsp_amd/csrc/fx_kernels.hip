@@ -3169,6 +3169,253 @@ __device__ __forceinline__ void block_fec_decode_soft(unsigned fs, uint32_t n, c
     }
 }
 
+// ===================================================================== payload: soft-output block decoders (fxrx_config.soft_chain)
+// block_fec_decode_soft's decoders, emitting one soft value per message bit (0 = surely 0 ... 255 = surely 1, in the order of the
+// output bytes, MSB first) instead of hard bytes, so that a convolutional fec0 behind a block fec1 decodes with the soft-input
+// Viterbi.  The rule is this project's (include/fxrx.h), integers only:
+//   d = block_fec_decode_soft's message (same ties), C = the cost above, L_i >= 0 the margin of message bit i,
+//   o_i = d_i ? min(255, max(128, (255 + L_i + 1) >> 1)) : max(0, min(127, (255 - L_i) >> 1))        -- o_i > 127 <=> d_i = 1
+//   Hamming codes: L_i = min{C(c) : m_i != d_i} - C(d) over all codewords (max-log-MAP) = |min over m_i = 1 - min over m_i = 0|;
+//   Golay, SECDED: the same minimum over the Chase candidates (the successful re-encodings); no such candidate: L_i = 255; no
+//     candidate at all (the output is the hard decoder's on the hard word): o_i = d_i ? 192 : 64 (SISO_NO_CANDIDATE).
+// Positions a short last block does not transmit and padding bits past 8 n are not emitted.
+#define SISO_NO_CANDIDATE 64u                   // distance from 128 of an output bit that no Chase candidate backs; not tuned
+#define SISO_INF 0x7fffffffu
+
+// decision d and margin L (any size; saturates from 254 / 255 on) -> the soft output
+__device__ __forceinline__ uint32_t siso_out(uint32_t d, uint32_t L)
+{
+    L = min(L, 255u);
+    return d ? (256u + L) >> 1 : (255u - L) >> 1;
+}
+
+// exhaustive ML over the 2^K codewords enc[d] of N bits (sb_ml) with max-log-MAP margins: per message bit the least cost of the
+// codewords with that bit clear (m0) and set (m1) stay in registers.  The low four message bits are unrolled (compile-time
+// sides: one v_min per bit and codeword), the high ones are a wave-uniform loop whose sides are picked per sixteen codewords.
+// out: K soft values, message bit MSB first, four per word
+template <int K, int N, class E>
+__device__ __forceinline__ void sb_ml_siso(const uint32_t (&sw)[(N + 3) / 4], const E *enc, uint32_t (&out)[K / 4])
+{
+    uint32_t m0[K], m1[K], best = ~0u;
+#pragma unroll
+    for (int q = 0; q < K; q++) { m0[q] = SISO_INF; m1[q] = SISO_INF; }
+    for (uint32_t dh = 0; dh < (1u << (K - 4)); dh++) {
+        uint32_t cmin = SISO_INF;
+#pragma unroll
+        for (uint32_t dl = 0; dl < 16u; dl++) {
+            const uint32_t d = dh * 16u + dl;
+            const uint32_t pm[1] = { __builtin_bitreverse32((uint32_t)enc[d]) >> (32 - N) };
+            const uint32_t c = sb_cost<(N + 3) / 4>(sw, pm);
+            best = min(best, (c << K) | d);
+            cmin = min(cmin, c);
+#pragma unroll
+            for (int q = 0; q < 4; q++) { if ((dl >> q) & 1u) m1[q] = min(m1[q], c); else m0[q] = min(m0[q], c); }
+        }
+#pragma unroll
+        for (int q = 4; q < K; q++) {
+            const bool one = (dh >> (q - 4)) & 1u;
+            m1[q] = min(m1[q], one ? cmin : SISO_INF); m0[q] = min(m0[q], one ? SISO_INF : cmin);
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < K / 4; w++) out[w] = 0;
+#pragma unroll
+    for (int i = 0; i < K; i++) {                                                  // message bit i, MSB first = bit K - 1 - i of d
+        const int q = K - 1 - i;
+        const uint32_t L = m1[q] > m0[q] ? m1[q] - m0[q] : m0[q] - m1[q];
+        out[i >> 2] |= siso_out((best >> q) & 1u, L) << (8 * (i & 3));
+    }
+}
+
+// Chase candidates -> soft outputs.  cc[p]: cost of candidate p (SISO_INF: pattern p did not succeed), cm[p]: its message bits as
+// a position mask (bit i = message bit i, MSB-first order of the output); best: the winner's (cost << 4 | p) or ~0 (none),
+// dm: the winner's mask (none: the hard decoder's).  Writes nw words of four soft values.
+template <class MT>
+__device__ __forceinline__ void siso_chase_out(const uint32_t (&cc)[16], const MT (&cm)[16], uint32_t best, MT dm, uint32_t nw, uint32_t *out)
+{
+    const bool any = best != ~0u;
+    const uint32_t cd = best >> 4;
+    for (uint32_t w = 0; w < nw; w++) {
+        uint32_t L[4] = { SISO_INF, SISO_INF, SISO_INF, SISO_INF };
+#pragma unroll
+        for (int p = 0; p < 16; p++) {
+            const uint32_t x = (uint32_t)((cm[p] ^ dm) >> (4u * w)) & 15u;
+#pragma unroll
+            for (int b = 0; b < 4; b++) L[b] = min(L[b], (x >> b) & 1u ? cc[p] : SISO_INF);
+        }
+        const uint32_t nib = (uint32_t)(dm >> (4u * w)) & 15u;
+        uint32_t word = 0;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const uint32_t d = (nib >> b) & 1u;
+            const uint32_t o = any ? siso_out(d, L[b] - cd) : (d ? 128u + SISO_NO_CANDIDATE : 128u - SISO_NO_CANDIDATE);
+            word |= o << (8 * b);
+        }
+        out[w] = word;
+    }
+}
+
+// Golay(24,12), Chase-4 (sb_golay), keeping every candidate: message bit i is codeword position i
+__device__ __forceinline__ void sb_golay_siso(const uint32_t (&sw)[6], const FxTables *T, uint32_t (&cc)[16], uint32_t (&cm)[16], uint32_t &best, uint32_t &dm)
+{
+    uint32_t pm[1], t[4], tr[4], tc[4];
+    sb_hard<6>(sw, pm);
+    sb_least4<6>(sw, 24u, t);
+    const uint32_t r = __builtin_bitreverse32(pm[0]) >> 8;                     // received word, MSB first (position b = bit 23 - b)
+    const uint32_t syn = (T->golenc[r >> 12] ^ r) & 0xfffu;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint32_t q = 23u - t[j];
+        tr[j] = 1u << q;
+        tc[j] = q >= 12u ? T->golenc[1u << (q - 12u)] & 0xfffu : tr[j];
+    }
+    best = ~0u; dm = pm[0] & 0xfffu;
+#pragma unroll
+    for (int p = 0; p < 16; p++) {
+        uint32_t s = syn, rp = r;
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (p & (1 << j)) { s ^= tc[j]; rp ^= tr[j]; }
+        const uint32_t e = T->golerr[s];
+        cc[p] = SISO_INF; cm[p] = 0;
+        if (e != 0xFFFFFFFFu) {
+            const uint32_t cw[1] = { __builtin_bitreverse32(rp ^ e) >> 8 };
+            cc[p] = sb_cost<6>(sw, cw); cm[p] = cw[0] & 0xfffu;
+            const uint32_t key = (cc[p] << 4) | (uint32_t)p;
+            if (key < best) { best = key; dm = cm[p]; }
+        }
+    }
+}
+
+// SECDED, Chase-4 (sb_secded_block), keeping every candidate: message bit i is codeword position 8 + i
+template <int ND> struct siso_mask { typedef uint32_t type; };
+template <> struct siso_mask<8> { typedef unsigned long long type; };
+template <int M, class MT>
+__device__ __forceinline__ MT siso_data_mask(const uint32_t (&c)[M])
+{
+    if constexpr (M == 1) return (MT)(c[0] >> 8);
+    else if constexpr (M == 2) return (MT)((c[0] >> 8) | (c[1] << 24));
+    else return (MT)(c[0] >> 8) | ((MT)c[1] << 24) | ((MT)c[2] << 56);
+}
+template <int ND>
+__device__ __forceinline__ void sb_secded_siso(const uint8_t *S, uint32_t nb, const uint8_t *col, const uint8_t *inv, uint32_t (&cc)[16],
+                                               typename siso_mask<ND>::type (&cm)[16], uint32_t &best, typename siso_mask<ND>::type &dm)
+{
+    typedef typename siso_mask<ND>::type MT;
+    constexpr int W = 2 + 2 * ND, M = (W + 7) / 8;
+    const uint32_t nvalid = 8u + 8u * nb;
+    uint32_t sw[W], y[M], t[4], tm[4][M], tc[4];
+    sb_load<W>(S, nvalid / 4u, sw);
+    sb_hard<W>(sw, y);
+    sb_least4<W>(sw, nvalid, t);
+    uint32_t syn = __builtin_bitreverse32(y[0]) >> 24;
+#pragma unroll
+    for (int j = 0; j < 8 * ND; j++) if ((y[(8 + j) >> 5] >> ((8 + j) & 31)) & 1u) syn ^= col[j];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+#pragma unroll
+        for (int i = 0; i < M; i++) tm[j][i] = 0;
+        sb_flip<M>(tm[j], t[j]);
+        tc[j] = t[j] < 8u ? 0x80u >> t[j] : (uint32_t)col[t[j] - 8u];
+    }
+    best = ~0u; dm = siso_data_mask<M, MT>(y);
+#pragma unroll
+    for (int p = 0; p < 16; p++) {
+        uint32_t s = syn, c[M];
+#pragma unroll
+        for (int i = 0; i < M; i++) c[i] = y[i];
+#pragma unroll
+        for (int j = 0; j < 4; j++) if (p & (1 << j)) {
+            s ^= tc[j];
+#pragma unroll
+            for (int i = 0; i < M; i++) c[i] ^= tm[j][i];
+        }
+        const uint32_t iv = inv[s];
+        cc[p] = SISO_INF; cm[p] = 0;
+        if (s == 0u || __popc(s) == 1u || iv != 0u) {
+            if (iv != 0u && iv - 1u < 8u * nb) sb_flip<M>(c, 8u + iv - 1u);
+            else c[0] ^= __builtin_bitreverse32(s) >> 24;
+            cc[p] = sb_cost<W>(sw, c); cm[p] = siso_data_mask<M, MT>(c);
+            const uint32_t key = (cc[p] << 4) | (uint32_t)p;
+            if (key < best) { best = key; dm = cm[p]; }
+        }
+    }
+}
+
+// In place (Sout == Sin, the decode kernel) the outputs of one group land where other lanes' inputs lie, so the work goes in
+// rounds of 64 groups: every lane reads all of its group's inputs and decodes into registers, a wave barrier, then the writes.
+// A group's outputs (one per message bit) are never more than its inputs (one per coded bit) and start no later, so round r's
+// writes end at or before the place where round r + 1's reads begin, and what rounds before r read is no longer needed.
+template <int ND>
+__device__ __forceinline__ void sb_secded_siso_rounds(const uint8_t *col, const uint8_t *inv, uint32_t n, const uint8_t *Sin, uint8_t *Sout, int lane)
+{
+    typedef typename siso_mask<ND>::type MT;
+    const uint32_t nblk = (n + ND - 1) / ND;
+    for (uint32_t b0 = 0; b0 < nblk; b0 += DEC_THREADS) {
+        const uint32_t blk = b0 + lane;
+        const uint32_t nb = blk < nblk ? min((uint32_t)ND, n - ND * blk) : 0u;
+        uint32_t cc[16], best = ~0u; MT cm[16], dm = 0;
+        if (blk < nblk) sb_secded_siso<ND>(Sin + 8 * (ND + 1) * (size_t)blk, nb, col, inv, cc, cm, best, dm);
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        if (blk < nblk) siso_chase_out<MT>(cc, cm, best, dm, 2u * nb, reinterpret_cast<uint32_t *>(Sout + 8 * ND * (size_t)blk));
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// soft-output counterpart of block_fec_decode_soft: Sin, the soft values of fec_enc_len(fs, n) coded bytes (8-byte aligned) -> Sout,
+// 8 n soft values (8-byte aligned; may be Sin).  One lane per codeword (SECDED: per block): codeword j's outputs are a whole
+// number of words at a word-aligned place -- Hamming(7,4) / (8,4): 4 at 4 j (inputs: 7 at 7 j, byte loads / 8 at 8 j), Hamming(12,8):
+// 8 at 8 j (12 at 12 j), Golay: 12 at 12 j (24 at 24 j), SECDED: 8 nb at 8 ND j (8 + 8 nb at 8 (ND + 1) j; a short last block has
+// nb < ND data bytes and emits only those).
+__device__ __forceinline__ void block_fec_decode_siso(unsigned fs, uint32_t n, const uint8_t *Sin, uint8_t *Sout, const FxTables *T, int lane)
+{
+    uint32_t *out = reinterpret_cast<uint32_t *>(Sout);
+    if (fs == FX_FEC_HAMMING84 || fs == FX_FEC_HAMMING74) {
+        const uint32_t ncw = 2 * n;
+        for (uint32_t j0 = 0; j0 < ncw; j0 += DEC_THREADS) {
+            const uint32_t j = j0 + lane;
+            uint32_t o[1] = { 0 };
+            if (j < ncw) {
+                uint32_t a[2] = { 0, 0 };
+                if (fs == FX_FEC_HAMMING84) { sb_load<2>(Sin + 8 * (size_t)j, 2u, a); sb_ml_siso<4, 8>(a, T->h84enc, o); }
+                else {
+                    const uint8_t *p = Sin + 7 * (size_t)j;
+#pragma unroll
+                    for (int i = 0; i < 7; i++) a[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
+                    sb_ml_siso<4, 7>(a, T->h74enc, o);
+                }
+            }
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
+            if (j < ncw) out[j] = o[0];
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        }
+    } else if (fs == FX_FEC_HAMMING128) {
+        for (uint32_t j0 = 0; j0 < n; j0 += DEC_THREADS) {
+            const uint32_t j = j0 + lane;
+            uint32_t o[2] = { 0, 0 };
+            if (j < n) { uint32_t a[3]; sb_load<3>(Sin + 12 * (size_t)j, 3u, a); sb_ml_siso<8, 12>(a, T->h128enc, o); }
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
+            if (j < n) { out[2 * j] = o[0]; out[2 * j + 1] = o[1]; }
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        }
+    } else if (fs == FX_FEC_GOLAY2412) {
+        const uint32_t ncw = (8 * n + 11) / 12;                                 // the last codeword may carry bits past 8 n: not emitted
+        for (uint32_t j0 = 0; j0 < ncw; j0 += DEC_THREADS) {
+            const uint32_t j = j0 + lane;
+            uint32_t cc[16], cm[16], best = ~0u, dm = 0;
+            if (j < ncw) { uint32_t a[6]; sb_load<6>(Sin + 24 * (size_t)j, 6u, a); sb_golay_siso(a, T, cc, cm, best, dm); }
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
+            if (j < ncw) siso_chase_out<uint32_t>(cc, cm, best, dm, min(3u, 2u * n - 3u * j), out + 3 * (size_t)j);
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        }
+    } else if (fs == FX_FEC_SECDED7264) {
+        sb_secded_siso_rounds<8>(T->sdcol, T->sdinv[2], n, Sin, Sout, lane);
+    } else if (fs == FX_FEC_SECDED3932) {
+        sb_secded_siso_rounds<4>(T->sd39col, T->sdinv[1], n, Sin, Sout, lane);
+    } else if (fs == FX_FEC_SECDED2216) {
+        sb_secded_siso_rounds<2>(T->sd22col, T->sdinv[0], n, Sin, Sout, lane);
+    }
+}
+
 // K=7 (0x6d, 0x4f) hard-decision Viterbi, one lane per state, exchange-free of LDS.
 //
 // A shift-register trellis is a perfect shuffle: state p feeds rotl(p,1) (input bit = p's old MSB) and
@@ -3529,7 +3776,9 @@ __device__ __forceinline__ void deinterleave_staged(uint8_t *buf, uint32_t n, ui
 }
 
 // SB (fxrx_config.soft_block): a block code (not Reed-Solomon) in a stage that decodes from soft values uses its soft-input decoder
-template <bool WITH_RS, bool SOFT, bool SB = false>
+// SC (fxrx_config.soft_chain, with SB): a soft-block fec1 in front of a convolutional fec0 hands it soft values (block_fec_decode_siso,
+// in place in the soft arena), and fec0 decodes them as it does behind FEC_NONE: soft de-interleaver, soft-input Viterbi
+template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false>
 __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob *jobs, const uint32_t *job_idx, const uint8_t *hard, uint8_t *bufA,
                                           uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res,
                                           const FxTables *T, uint8_t *X)
@@ -3554,6 +3803,7 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
         bool still_soft = false;
         if (pc1) viterbi27<2>(pc1, job.l0, S, B, dw_arena + job.dw_off, A, lane, nullptr);
         else if (job.fec1 == FX_FEC_NONE) still_soft = true;
+        else if (SC && pc0 && sb_code(job.fec1)) { block_fec_decode_siso(job.fec1, job.l0, S, S, T, lane); still_soft = true; }
         else if (SB && sb_code(job.fec1)) block_fec_decode_soft(job.fec1, job.l0, S, B, T, lane);
         else {
             soft_to_hard_wave(S, A, job.l1, lane);
@@ -3663,7 +3913,31 @@ void fx_paydec_sb_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const Fx
     }
 }
 
-// soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input block decoders (fx_paydec_sb_kernel)
+// the soft-chain variant (fxrx_config.soft_chain): fx_paydec_sb_kernel with soft-output block decoders in front of a convolutional
+// fec0, again in kernels of its own
+template <bool WITH_RS>
+__global__ __launch_bounds__(WITH_RS ? DEC_THREADS : DEC_THREADS * DEC_MAX_WAVES)
+void fx_paydec_sc_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA,
+                         uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T,
+                         FxBlockHdr *fallback_host)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t Xs[WITH_RS ? 16 : DEC_LDS];
+    uint8_t *X = (!WITH_RS && blockDim.x == 64) ? Xs : nullptr;
+    const uint32_t njobs = WITH_RS ? hdr->n_dec_rs : (fallback_host ? hdr->n_vb_fallback : hdr->n_dec_plain);
+    const uint32_t wpg = blockDim.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const uint32_t ji0 = __builtin_amdgcn_readfirstlane(first_wave + blockIdx.x * wpg + (threadIdx.x >> 6));
+    if (ji0 >= njobs) return;
+    __builtin_amdgcn_s_setprio(2);
+    if constexpr (WITH_RS) {
+        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, true, true, true>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
+    } else {
+        dec_frame<false, true, true, true>(ji0, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
+    }
+}
+
+// soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input block decoders (fx_paydec_sb_kernel), 3 those with
+// soft-output block decoders in front of a convolutional fec0 (fx_paydec_sc_kernel)
 extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host)
@@ -3673,9 +3947,12 @@ extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wav
     const dim3 grid((grid_waves + w - 1) / w), block(DEC_THREADS * w);
 #define FX_DEC_LAUNCH(RS, SF) hipLaunchKernelGGL((fx_paydec_kernel<RS, SF>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
 #define FX_DEC_SB_LAUNCH(RS) hipLaunchKernelGGL((fx_paydec_sb_kernel<RS>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
-    if (soft == 2) { if (with_rs) FX_DEC_SB_LAUNCH(true); else FX_DEC_SB_LAUNCH(false); }
+#define FX_DEC_SC_LAUNCH(RS) hipLaunchKernelGGL((fx_paydec_sc_kernel<RS>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
+    if (soft == 3) { if (with_rs) FX_DEC_SC_LAUNCH(true); else FX_DEC_SC_LAUNCH(false); }
+    else if (soft == 2) { if (with_rs) FX_DEC_SB_LAUNCH(true); else FX_DEC_SB_LAUNCH(false); }
     else if (with_rs) { if (soft) FX_DEC_LAUNCH(true, true); else FX_DEC_LAUNCH(true, false); }
     else { if (soft) FX_DEC_LAUNCH(false, true); else FX_DEC_LAUNCH(false, false); }
+#undef FX_DEC_SC_LAUNCH
 #undef FX_DEC_SB_LAUNCH
 #undef FX_DEC_LAUNCH
     return hipGetLastError();
@@ -3699,6 +3976,23 @@ extern "C" hipError_t fx_launch_blkdec(int soft, unsigned fs, unsigned n, unsign
     if (count == 0) return hipSuccess;
     if (soft) hipLaunchKernelGGL(fx_blkdec_kernel<true>, dim3(count), dim3(DEC_THREADS), 0, st, fs, n, count, in, out, T);
     else hipLaunchKernelGGL(fx_blkdec_kernel<false>, dim3(count), dim3(DEC_THREADS), 0, st, fs, n, count, in, out, T);
+    return hipGetLastError();
+}
+
+// tests (fxrx_debug_block_siso): the soft-output block decoders on `count` crafted packets of n message bytes, one wave per packet:
+// 8 fec_enc_len(fs, n) soft values in (codeword bit order), 8 n out
+__global__ __launch_bounds__(DEC_THREADS)
+void fx_blksiso_kernel(unsigned fs, uint32_t n, uint32_t count, const uint8_t *in, uint8_t *out, const FxTables *T)
+{
+    const uint32_t p = blockIdx.x;
+    if (p >= count) return;
+    block_fec_decode_siso(fs, n, in + 8 * (size_t)fec_enc_len(fs, n) * p, out + 8 * (size_t)n * p, T, threadIdx.x);
+}
+
+extern "C" hipError_t fx_launch_blksiso(unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(fx_blksiso_kernel, dim3(count), dim3(DEC_THREADS), 0, st, fs, n, count, in, out, T);
     return hipGetLastError();
 }
 

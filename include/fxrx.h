@@ -90,6 +90,10 @@ void fxrx_sync_set_soft(flexframesync q, int on);        /* likewise: soft-decis
 /* soft-input block decoders (fxrx_config.soft_block), in force while soft payload decoding is on.  Re-creates the context; returns 0,
  * or -1 if that failed, in which case the previous setting stays */
 int  fxrx_sync_set_soft_block(flexframesync q, int on);
+/* soft values carried from a block fec1 into a convolutional fec0 (fxrx_config.soft_chain), in force while soft payload decoding and
+ * soft_block are on.  Re-creates the context; returns 0, or -1 if that failed or if, with on != 0, soft payload decoding or soft_block
+ * is off, in which case the previous setting stays */
+int  fxrx_sync_set_soft_chain(flexframesync q, int on);
 unsigned int fxrx_sync_pending(flexframesync q);     /* completed frames not yet delivered */
 /* the liquid signatures return void: when a block fails on the GPU its samples (and those of the blocks in flight with it) are
  * dropped -- never fed twice --, the synchroniser restarts freshly reset behind the gap, the text stays in fxrx_last_error(),
@@ -188,6 +192,24 @@ typedef struct {
                                     positions flipped in all 16 patterns, the cheapest re-encoded success, ties to the smallest pattern).
                                     These rules are this project's, not pinned to liquid's fec_decode_soft.  Needs soft_decision = 1 and
                                     flex_rx mode (fxrx_create fails with FXRX_ERR_ARG otherwise).  0 (default): hard decisions there */
+    int          soft_chain;     /* 1: when fec1 is one of soft_block's codes and fec0 is convolutional, fec1's decoder emits one soft value per
+                                    message bit (8 l0 of them, in the order of its output bytes, MSB first) instead of hard bytes; they pass
+                                    the soft de-interleaver and fec0 decodes with the soft-input Viterbi.  Every other pair (fec1 none,
+                                    convolutional or Reed-Solomon; a block fec0 behind a block fec1) decodes as under soft_block.
+                                    The soft-output rule, integers only, is this project's, not liquid's.  With s_b the soft value of
+                                    codeword position b (0 = surely 0, 255 = surely 1), C(c) = sum_b (c_b ? 255 - s_b : s_b) the cost of
+                                    codeword c, d the message soft_block's decoder returns (same ties) and L_i >= 0 the margin of message
+                                    bit i, the output is
+                                        o_i = min(255, max(128, (255 + L_i + 1) >> 1))   if d_i = 1,
+                                        o_i = max(0, min(127, (255 - L_i) >> 1))         if d_i = 0,
+                                    so o_i > 127 exactly when d_i = 1, in the unit of the input (a channel value s has margin |2 s - 255|).
+                                    Hamming(7,4) / (8,4) / (12,8): L_i = min{C(c) : m_i != d_i} - C(d) over all codewords (max-log-MAP).
+                                    Golay, SECDED (Chase-4): the same minimum over the candidates, the successful re-encodings of the 16
+                                    patterns; no candidate with m_i != d_i: L_i = 255 (the output saturates at 0 / 255); no candidate at
+                                    all (the output is the hard decoder's on the hard word): o_i = d_i ? 192 : 64.  Positions a short last
+                                    block does not transmit and padding bits past 8 l0 are not emitted.
+                                    Needs soft_block = 1 (hence soft_decision = 1 and flex_rx mode; fxrx_create fails with FXRX_ERR_ARG
+                                    otherwise).  0 (default): fec1 hands fec0 hard bytes */
 } fxrx_config;
 
 typedef struct {
@@ -291,6 +313,10 @@ int fxrx_debug_header_decode(int soft, const uint8_t *in, unsigned int n, uint8_
  * bit order (after the stage's de-interleaver); soft == 0: the fec_enc_len(fec, n) coded bytes.  Writes n bytes per packet to out.
  * Synchronous, on the current HIP device; returns 0 or FXRX_ERR_* */
 int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out);
+/* tests: its soft-output twin (fxrx_config.soft_chain): `in` holds 8 fec_enc_len(fec, n) soft values per packet in codeword bit order,
+ * out_soft receives 8 n soft values per packet, one per message bit, MSB first.  Synchronous, on the current HIP device; returns 0 or
+ * FXRX_ERR_* */
+int fxrx_debug_block_siso(unsigned int fec, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out_soft);
 /* diagnostic builds (-DFX_STAMPS) only: shader-clock deltas of the decode phases of payload job i */
 int fxrx_debug_stamps(const fxrx_ctx *c, unsigned int i, uint32_t out[8]);
 int fxrx_debug_chain_stamps(const fxrx_ctx *c, uint32_t out[8]);  /* chain kernel phase clocks (stream 0) of the last collected block */
