@@ -5,7 +5,9 @@ equaliser, the pilot estimates over the header and the decision-directed payload
 below, sharing no code with the oracle (oracle/fxref_frame.c) or the kernels (gr-liquiddsp_amd/csrc/fx_kernels.hip):
 numpy complex128 and np.exp throughout -- no float32, no sin/cos table, no series, no 32-bit phase, no tree sums.
 Conventions come in as *data* (the 64 p/n symbols, the 15 pilots, the 897-tap receive prototype, the 13 equaliser start
-taps: `Tables`); constellations and decisions are ref_decode's.
+taps: `Tables`); constellations and decisions are ref_decode's.  `Tables.from_reference()` (= ref_framegen.tables()) builds
+them from their definitions in tests/ref_framegen.py, `Tables.from_oracle()` reads the oracle's; tests/test_ref_framegen.py
+pins the two to each other (p/n and pilots exactly, taps within one float32 ulp).
 
 Inputs: the capture x, a frame's `start` (aligned sample 0 is x[start]) and the ALIGN estimates tau, gamma, dphi, phi as
 the receiver reported them (float32 values taken exactly; tests/ref_detect.py pins those).
@@ -129,6 +131,12 @@ class Tables:
     def from_oracle(cls, oracle):
         return cls(oracle.table("fxr_preamble_pn", PN_LEN), oracle.table("fxr_pilots", N_PILOTS),
                    oracle.table("fxr_mf_proto", NPFB * MF_TAPS + 1, complex_=False), oracle.eq_init_taps())
+
+    @classmethod
+    def from_reference(cls):
+        """The tables from their definitions (tests/ref_framegen.py), in float64: no oracle."""
+        import ref_framegen
+        return ref_framegen.tables()
 
 
 def tie_margin(ms):
