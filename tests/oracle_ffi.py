@@ -156,7 +156,7 @@ def gen_frame(payload, mod=2, fec0=FEC_CONV_V27, fec1=FEC_NONE, check=CRC_24, he
 
 
 class Frame:
-    __slots__ = ("header", "header_valid", "payload", "payload_valid", "evm", "rssi", "cfo", "framesyms",
+    __slots__ = ("header", "header20", "header_valid", "payload", "payload_valid", "evm", "rssi", "cfo", "framesyms",
                  "mod_scheme", "mod_bps", "check", "fec0", "fec1", "info", "soft")
 
     def __repr__(self):
@@ -182,7 +182,8 @@ class Sync:
 
     def _on_frame(self, header, hv, payload, plen, pv, st, ud):
         f = Frame()
-        f.header = bytes(bytearray(header[i] for i in range(14)))
+        f.header20 = bytes(bytearray(header[i] for i in range(20)))     # the oracle hands out all FXR_HDR_DEC decoded bytes
+        f.header = f.header20[:14]
         f.header_valid, f.payload_valid = int(hv), int(pv)
         f.payload = bytes(bytearray(payload[i] for i in range(plen))) if plen else b""
         f.evm, f.rssi, f.cfo = st.evm, st.rssi, st.cfo

@@ -25,6 +25,7 @@ def compare_frames(of, gf, check_syms=True):
         assert i["offset"] == b["cfo_bin"]
         assert a.header_valid == b["header_valid"]
         assert a.header == b["header"][:14]
+        assert a.header20 == b["header"], "protocol bytes of the header differ at frame start %d" % i["start"]    # all 20 decoded bytes, rejected headers included
         assert i["pfb_index"] == b["pfb_index"]
         for k, kb in (("rxy", "rxy"), ("tau", "tau"), ("gamma", "gamma"), ("dphi", "dphi"), ("phi", "phi")):
             dev["est"] = max(dev["est"], abs(i[k] - b[kb]))

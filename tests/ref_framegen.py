@@ -257,16 +257,24 @@ def frame_len(n, mod, fec0, fec1, check):
     return K * (PN_LEN + HDR_SYM + num_payload_symbols(n, mod, fec0, fec1, check) + FLUSH)
 
 
-def frame_symbols(payload, mod, fec0, fec1, check, header=None, pilot_shift=0, **payload_controls):
+def frame_symbols(payload, mod, fec0, fec1, check, header=None, pilot_shift=0, hdr20=None, points=None, **payload_controls):
+    """hdr20: all 20 header bytes as given (the six protocol bytes are then NOT derived from the payload's properties: a test
+    can state a header no generator would build); the payload symbols are still those of (payload, mod, fec0, fec1, check),
+    stated separately, or `points` when given explicitly."""
     payload = np.asarray(payload, np.uint8)
-    hdr = compose_header(header, len(payload), mod, check, fec0, fec1)
-    return np.concatenate([preamble(), header_symbols(hdr, pilot_shift),
-                           payload_points(payload, mod, check, fec0, fec1, **payload_controls), np.zeros(FLUSH, np.complex128)])
+    if hdr20 is None:
+        hdr = compose_header(header, len(payload), mod, check, fec0, fec1)
+    else:
+        assert header is None
+        hdr = np.asarray(hdr20, np.uint8)
+        assert len(hdr) == RS.HDR_DEC
+    pts = payload_points(payload, mod, check, fec0, fec1, **payload_controls) if points is None else np.asarray(points, np.complex128)
+    return np.concatenate([preamble(), header_symbols(hdr, pilot_shift), pts, np.zeros(FLUSH, np.complex128)])
 
 
-def frame(payload, mod, fec0, fec1, check, header=None, dt=0.0, dt_sign=1, tap_shift=0, **symbol_controls):
+def frame(payload, mod, fec0, fec1, check, header=None, dt=0.0, dt_sign=1, tap_shift=0, hdr20=None, **symbol_controls):
     """The frame's samples, complex128.  dt: the delay, rounded once to the float32 the generators take."""
-    x = frame_symbols(payload, mod, fec0, fec1, check, header, **symbol_controls)
+    x = frame_symbols(payload, mod, fec0, fec1, check, header, hdr20=hdr20, **symbol_controls)
     h = tx_taps(dt_sign * float(np.float32(dt)))
     if tap_shift:
         h = np.concatenate([np.zeros(tap_shift), h[:len(h) - tap_shift]])
