@@ -53,18 +53,34 @@ FX_DEV float2 cmulc(float2 a, float2 b)
 }
 FX_DEV float cm2(float2 a) { return fmaf(a.x, a.x, a.y * a.y); }
 
+// The one float -> integer rule of the canonical arithmetic: NaN gives 0, anything else saturates at the
+// largest binary32 values inside the integer type, then converts -- written out, so that it is the same on every machine and
+// in the oracle (oracle/fxref.h: fxr_f2i_sat / fxr_f2ll_sat).  Values in range convert exactly as a plain cast does.
+FX_DEV int f2i_sat(float t)
+{
+    if (t != t) return 0;
+    t = t < -2147483520.0f ? -2147483520.0f : t;
+    t = t > 2147483520.0f ? 2147483520.0f : t;
+    return (int)t;
+}
+FX_DEV long long f2ll_sat(float t)
+{
+    if (t != t) return 0;
+    t = t < -9223371487098961920.0f ? -9223371487098961920.0f : t;
+    t = t > 9223371487098961920.0f ? 9223371487098961920.0f : t;
+    return (long long)t;
+}
+
 FX_DEV uint32_t rad2u32(float rad)
 {
     float t = rintf(rad * 683565248.0f);
-    return (uint32_t)(long long)t;
+    return (uint32_t)f2ll_sat(t);
 }
 
 // PLL increments, already in phase units: round, clamp below 2^31, plain 32-bit convert
 FX_DEV uint32_t phase_inc(float units)
 {
-    float t = rintf(units);
-    t = fminf(fmaxf(t, -2147483520.0f), 2147483520.0f);
-    return (uint32_t)(int)t;
+    return (uint32_t)f2i_sat(rintf(units));
 }
 
 FX_DEV void sincos_u32(uint32_t th, const float2 *sc, float &c, float &s)
@@ -83,7 +99,8 @@ FX_DEV void sincos_u32(uint32_t th, const float2 *sc, float &c, float &s)
 // carrier phasor by this between table look-ups
 FX_DEV float phase_step(float units)
 {
-    return fminf(fmaxf(rintf(units), -2147483520.0f), 2147483520.0f);
+    const float t = fminf(fmaxf(rintf(units), -2147483520.0f), 2147483520.0f);
+    return units != units ? 0.0f : t;           // NaN: no advance (fmaxf alone would turn it into the lower bound)
 }
 FX_DEV void sincos_small(float step_units, float &c, float &s)
 {
@@ -307,7 +324,7 @@ FX_DEV unsigned pam_index(float v, float inv2al, unsigned Lv)
     float t = floorf(fmaf(v, inv2al, 0.5f * (float)Lv));
     if (t < 0.0f) t = 0.0f;
     if (t > (float)(Lv - 1)) t = (float)(Lv - 1);
-    return (unsigned)t;
+    return (unsigned)f2i_sat(t);                // NaN -> level 0
 }
 
 FX_DEV unsigned psk_index(float2 r, unsigned bps)
@@ -319,7 +336,7 @@ FX_DEV unsigned psk_index(float2 r, unsigned bps)
     }
     float th = atan2c(r.y, r.x);
     float t = rintf(th * ((float)(1u << bps) * 0.159154943f));
-    return (unsigned)((int)t) & ((1u << bps) - 1u);
+    return (unsigned)f2i_sat(t) & ((1u << bps) - 1u);
 }
 
 // unit phasor at phase index idx of 2^bps: exact axis points up to 4-PSK, the sincos table beyond

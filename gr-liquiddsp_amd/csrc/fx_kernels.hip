@@ -1173,8 +1173,8 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         }
 
         // ------------------------------------------------------------ flex_rx: preamble + header span
-        if (tau > 0.0f) { fr.pfb = (unsigned)(tau * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 0; }
-        else { fr.pfb = (unsigned)((1.0f + tau) * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 1; }
+        if (tau > 0.0f) { fr.pfb = (unsigned)f2i_sat(tau * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 0; }
+        else { fr.pfb = (unsigned)f2i_sat((1.0f + tau) * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 1; }
         fr.mf_scale = 0.5f / gamma;
         constexpr int dly = EQ ? FX_EQ_DELAY : 0;                      // the equaliser moves every symbol instant 3 symbols later
         const int nh = (int)sym_sample(FX_SYM0_PAY + dly - 1, fr.mfc0);  // sample of the last header symbol

@@ -261,6 +261,8 @@ int fxrx_result(const fxrx_ctx *c, unsigned int i, fxrx_frame *out);
  * valid until the next fxrx_collect / fxrx_process on the context (a submit in between does not touch them).  Returns 0
  * (submit) / result count (collect) or FXRX_ERR_*. */
 int fxrx_set_depth(fxrx_ctx *c, unsigned int depth);
+/* Any binary32 value is valid input: NaN, +-Inf and overflowing samples never make a call fail, never change another stream of
+ * the batch, and change only the frames whose windows and filter spans read them ("Bad samples"). */
 int fxrx_submit(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device);
 int fxrx_collect(fxrx_ctx *c);
 /* Failure semantics.  A failing fxrx_submit (bad arguments, a batch too large for the arenas, an allocation that fails) leaves

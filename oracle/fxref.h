@@ -79,6 +79,23 @@ enum {
 #define FXR_EQ_MU        0.05f
 
 /* ------------------------------------------------------------------ math (fxref_math.c) */
+/* The one float -> integer rule of the canonical arithmetic: NaN gives 0, anything else saturates at the
+ * largest binary32 values inside the integer type, then converts.  Values in range are untouched, so finite, well-scaled input
+ * converts exactly as a plain cast does.  The kernels' twins are f2i_sat / f2ll_sat in csrc/fx_device.h. */
+static inline int32_t fxr_f2i_sat(float t)
+{
+    if (t != t) return 0;
+    t = t < -2147483520.0f ? -2147483520.0f : t;
+    t = t > 2147483520.0f ? 2147483520.0f : t;
+    return (int32_t)t;
+}
+static inline int64_t fxr_f2ll_sat(float t)
+{
+    if (t != t) return 0;
+    t = t < -9223371487098961920.0f ? -9223371487098961920.0f : t;
+    t = t > 9223371487098961920.0f ? 9223371487098961920.0f : t;
+    return (int64_t)t;
+}
 void     fxr_init(void);                        /* builds all shared tables once (idempotent) */
 uint32_t fxr_rad2u32(float rad);                /* rintf(rad * 2^32/2pi) wrapped mod 2^32 */
 uint32_t fxr_phase_inc(float units);            /* rintf(units) clamped below 2^31: PLL increments in phase units */

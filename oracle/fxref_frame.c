@@ -517,7 +517,7 @@ static void sync_on_symbol(fxr_sync *q, fxr_c32 y)
     /* loop filter kept in phase units: alpha = 1e-4 and beta = 1e-2 pre-multiplied by 2^32/2pi */
     q->pll_f = fmaf(pe, 68356.5248f, q->pll_f);
     float step = fxr_phase_step(fmaf(pe, 6835652.5f, q->pll_f));
-    q->pll_th += (uint32_t)(int32_t)step;
+    q->pll_th += (uint32_t)fxr_f2i_sat(step);
     {
         float cd, sd; fxr_sincos_small(step, &cd, &sd);
         float c2 = fmaf(q->pll_c, cd, -(q->pll_s * sd)), s2 = fmaf(q->pll_s, cd, q->pll_c * sd);
@@ -539,8 +539,8 @@ static void sync_run(fxr_sync *q, const fxr_c32 *x, unsigned n, int top)
             q->fi.offset = fxr_qdet_offset(q->det); q->fi.rxy = fxr_qdet_rxy(q->det);
             q->fi.tau = fxr_qdet_tau(q->det); q->fi.gamma = fxr_qdet_gamma(q->det);
             q->fi.dphi = fxr_qdet_dphi(q->det); q->fi.phi = fxr_qdet_phi(q->det);
-            if (q->fi.tau > 0.0f) { q->pfb = (unsigned)(q->fi.tau * (float)FXR_NPFB) % FXR_NPFB; q->mf_counter = 0; }
-            else { q->pfb = (unsigned)((1.0f + q->fi.tau) * (float)FXR_NPFB) % FXR_NPFB; q->mf_counter = 1; }
+            if (q->fi.tau > 0.0f) { q->pfb = (unsigned)fxr_f2i_sat(q->fi.tau * (float)FXR_NPFB) % FXR_NPFB; q->mf_counter = 0; }
+            else { q->pfb = (unsigned)fxr_f2i_sat((1.0f + q->fi.tau) * (float)FXR_NPFB) % FXR_NPFB; q->mf_counter = 1; }
             q->fi.pfb_index = q->pfb; q->fi.mf_counter0 = q->mf_counter;
             q->mf_scale = 0.5f / q->fi.gamma;
             q->mix_dl = fxr_rad2u32(q->fi.dphi); q->mix_th = fxr_rad2u32(q->fi.phi);

@@ -38,15 +38,14 @@ const fxr_c32 *fxr_sincos_table(void) { fxr_math_init_(); return g_sc; }
 uint32_t fxr_rad2u32(float rad)
 {
     float t = rintf(rad * 683565248.0f);        /* 2^32/(2 pi) rounded to binary32 */
-    return (uint32_t)(int64_t)t;
+    return (uint32_t)fxr_f2ll_sat(t);
 }
 
 /* PLL increments, already in phase units (2^32 = one turn); clamp so that a 32-bit convert is exact on any input */
 uint32_t fxr_phase_inc(float units)
 {
     float t = rintf(units);
-    t = fminf(fmaxf(t, -2147483520.0f), 2147483520.0f);
-    return (uint32_t)(int32_t)t;
+    return (uint32_t)fxr_f2i_sat(t);
 }
 
 /* cos/sin of a 32-bit phase: table on the top 10 bits, series on the remaining 22 */
@@ -67,6 +66,7 @@ void fxr_sincos_u32(uint32_t th, float *c, float *s)
 float fxr_phase_step(float units)
 {
     float t = rintf(units);
+    if (t != t) return 0.0f;                    /* NaN: no advance (fxr_f2i_sat's rule, kept in the float the series takes) */
     if (t < -2147483520.0f) t = -2147483520.0f;
     if (t > 2147483520.0f) t = 2147483520.0f;
     return t;

@@ -89,7 +89,7 @@ static inline unsigned pam_index(float v, float inv2al, unsigned L)
     float t = floorf(fmaf(v, inv2al, 0.5f * (float)L));
     if (t < 0.0f) t = 0.0f;
     if (t > (float)(L - 1)) t = (float)(L - 1);
-    return (unsigned)t;
+    return (unsigned)fxr_f2i_sat(t);            /* NaN -> level 0 */
 }
 
 /* nearest of M equally spaced phases: index = round(theta * M / 2pi) mod M */
@@ -102,12 +102,13 @@ static inline unsigned psk_index(fxr_c32 r, unsigned bps)
     }
     float th = fxr_atan2(r.im, r.re);
     float t = rintf(th * ((float)(1u << bps) * 0.159154943f));              /* M / 2pi */
-    return (unsigned)((int)t) & ((1u << bps) - 1u);
+    return (unsigned)fxr_f2i_sat(t) & ((1u << bps) - 1u);
 }
 
 unsigned fxr_modem_demod(fxr_modem *q, fxr_c32 r, fxr_c32 *xhat, float *phase_err)
 {
     unsigned sym; fxr_c32 xh = { 0, 0 };
+    int axis = 0; float pe_axis = 0.0f;
     switch (q->ms) {
     case FXR_MODEM_QPSK:
         sym = (r.re > 0.0f ? 0u : 1u) | (r.im > 0.0f ? 0u : 2u);
@@ -117,6 +118,12 @@ unsigned fxr_modem_demod(fxr_modem *q, fxr_c32 r, fxr_c32 *xhat, float *phase_er
     case FXR_MODEM_PSK2: case FXR_MODEM_PSK4: case FXR_MODEM_PSK8: case FXR_MODEM_PSK16: {
         unsigned idx = psk_index(r, q->bps);
         sym = gray_enc(idx); xh = psk_point(idx, q->bps);
+        if (q->bps <= 2) {
+            /* exact axis points: r conj(xhat) is a swap / sign flip, taken as such (no product with the zero component, which
+             * would turn an infinite r into NaN); bit-identical to the fma form below on finite r */
+            unsigned k = q->bps == 1 ? 2u * (idx & 1u) : (idx & 3u);
+            axis = 1; pe_axis = k == 0 ? r.im : (k == 1 ? -r.re : (k == 2 ? -r.im : r.re));
+        }
         break; }
     case FXR_MODEM_DPSK2: case FXR_MODEM_DPSK4: case FXR_MODEM_DPSK8: {
         unsigned M1 = (1u << q->bps) - 1u;
@@ -140,7 +147,7 @@ unsigned fxr_modem_demod(fxr_modem *q, fxr_c32 r, fxr_c32 *xhat, float *phase_er
     if (xhat) *xhat = xh;
     if (phase_err) {
         /* [RECALLED liquid modem_get_demodulator_phase_error]: imag(r * conj(xhat)), not its argument */
-        *phase_err = fmaf(r.im, xh.re, -(r.re * xh.im));
+        *phase_err = axis ? pe_axis : fmaf(r.im, xh.re, -(r.re * xh.im));
     }
     return sym;
 }
@@ -156,7 +163,7 @@ static inline uint8_t soft_byte(float d0, float d1, float gamma16)
     float t = rintf(fmaf(d0 - d1, gamma16, 127.0f));
     if (t < 0.0f) t = 0.0f;
     if (t > 255.0f) t = 255.0f;
-    return (uint8_t)t;
+    return (uint8_t)fxr_f2i_sat(t);             /* NaN -> 0 */
 }
 /* one axis of an ASK / QAM constellation: L levels (2 i - (L-1)) al, label gray(i), nb bits */
 static void soft_axis(float v, unsigned nb, float al, float gamma16, uint8_t *soft)

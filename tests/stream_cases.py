@@ -67,6 +67,42 @@ def build(case):
     return x.astype(np.complex64)
 
 
+def check_roles(case, frames, x_len):
+    """the frames a case placed against what a receiver reports (dicts with start, tau, header_valid, header, payload,
+    payload_valid): list of failure strings"""
+    import ref_detect as rd
+    import ref_stream as S
+    rd.set_template(S.conventions()[1])
+    bad = []
+    for f in case["frames"]:
+        hit = [g for g in frames if abs(g["start"] - f["at"]) <= 2]
+        role = f["role"]
+        if role in ("absent", "cut"):
+            if hit:
+                bad.append("%s frame at %d is reported" % (role, f["at"]))
+            continue
+        if len(hit) != 1 or hit[0]["start"] != f["at"]:
+            bad.append("%s frame at %d: reported starts %r" % (role, f["at"], [g["start"] for g in hit]))
+            continue
+        g = hit[0]
+        if role == "detected":
+            continue
+        # check_truth's start rule: start + tau against the arrival time.  The frame is advanced by dt (ref_framegen's convention)
+        tol = rd.tolerances(case["snr_db"] + 20.0 * np.log10(f["amp"]))["arrival"]
+        if abs(g["start"] + g["tau"] - (f["at"] - f["dt"])) > tol:
+            bad.append("%s frame at %d: arrival %.4f vs %.4f (tolerance %.3f)" % (role, f["at"], g["start"] + g["tau"], f["at"] - f["dt"], tol))
+        if bytes(g["header"]) != hdr20(f).tobytes():
+            bad.append("%s frame at %d: header bytes" % (role, f["at"]))
+        if role == "rejected":
+            if g["header_valid"]:
+                bad.append("rejected frame at %d has a valid header" % f["at"])
+        elif not g["header_valid"]:
+            bad.append("%s frame at %d: header not valid" % (role, f["at"]))
+        elif role == "good" and not (g["payload_valid"] and bytes(g["payload"]) == payload(f).tobytes()):
+            bad.append("good frame at %d: payload" % f["at"])
+    return bad
+
+
 def _case(name, frames, seed, snr_db=15.0, threshold=0.5, tail=700, **kw):
     total = max(f["at"] + length(f) for f in frames) + tail
     assert total <= 40_000 and all(f["n"] <= 100 for f in frames) and snr_db >= 12.0

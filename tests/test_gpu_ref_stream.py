@@ -17,7 +17,7 @@ import ref_stream as S
 import ref_sync as rs
 import stream_cases as SC
 from parity_util import compare_frames, oracle_frames
-from test_ref_stream import check_roles
+from stream_cases import check_roles
 
 pytestmark = pytest.mark.gpu
 
