@@ -1785,11 +1785,22 @@ __device__ __forceinline__ void chain_finish(const FxStreamDesc &sd, uint32_t s,
     }
 }
 
-__device__ __forceinline__ bool chain_state_in(const FxStreamDesc &sd, uint32_t s, FxStreamState &st_in, uint32_t *chain_count, FxBlockHdr *hdr)
+// A block builds on its predecessor as a whole: when ANY stream's start state is invalid the host will run the predecessor's
+// back part again (a repair) or replay this block (an overflow), and either reads carry buffers of the OTHER streams a second
+// time -- carry[b % 3] of the repaired block b, which block b + 2's chain would overwrite here (carry_reader only makes it wait
+// for the first reading), and carry[(b + 1) % 3], which block b + 3's would.  So no stream of such a block writes a tail or a
+// state: the buffers stay as the last good block left them until the host has enqueued everything again, in order.
+// (Called by all threads of the workgroup, one workgroup per stream: gridDim.x streams.)
+__device__ __forceinline__ bool chain_state_in(const FxStreamDesc *streams, const FxStreamDesc &sd, uint32_t s, FxStreamState &st_in, uint32_t *chain_count, FxBlockHdr *hdr)
 {
     st_in.pos = 0; st_in.floor = 0; st_in.carry_len = 0; st_in.fresh = 1; st_in.invalid = 0; st_in.overflow = 0; st_in.pad_ = 0;
     if (sd.state_in) st_in = *sd.state_in;
-    if (!st_in.invalid) return true;
+    int other = 0;
+    for (uint32_t t = threadIdx.x; t < gridDim.x; t += blockDim.x) {
+        const FxStreamState *p = streams[t].state_in;
+        if (p && p->invalid) other = 1;
+    }
+    if (!__syncthreads_or(other) && !st_in.invalid) return true;
     if (threadIdx.x == 0) {                                     // nothing to build on: say so downstream, the host replays
         FxStreamState so = st_in; so.invalid = 1; so.overflow = 0;
         *sd.state_out = so; *sd.state_out_host = so; chain_count[s] = 0;
@@ -1817,7 +1828,7 @@ void fx_chainfast_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, con
     if (pass == 2u && stat[s] != 2u) return;                    // settled in pass 1, or beyond a repair round
     const FxStreamDesc sd = streams[s];
     FxStreamState st_in;
-    if (!chain_state_in(sd, s, st_in, chain_count, hdr)) { if (pass == 1u && threadIdx.x == 0) stat[s] = 3u; return; }
+    if (!chain_state_in(streams, sd, s, st_in, chain_count, hdr)) { if (pass == 1u && threadIdx.x == 0) stat[s] = 3u; return; }
     uint32_t cnt = 0; int64_t fin_pos = 0, fin_floor = 0; bool fin_fresh = true;
     const unsigned long long t0_ = __builtin_readcyclecounter();
     if (threadIdx.x == 0) C.sh[5] = 0;
@@ -1866,7 +1877,7 @@ __device__ __forceinline__ void chain_kernel_body(const FxStreamDesc *streams, c
     const int tid = threadIdx.x, lane = tid & 63;
     FxFrame *out = chain + sd.chain_base;
     FxStreamState st_in;
-    if (!chain_state_in(sd, s, st_in, chain_count, hdr)) return;
+    if (!chain_state_in(streams, sd, s, st_in, chain_count, hdr)) return;
     float2 twA[7], twB[7];
 #pragma unroll
     for (int r = 1; r < 8; r++) { twA[r - 1] = T->tw[lane * r]; twB[r - 1] = T->tw[8 * (lane & 7) * r]; }

@@ -19,6 +19,19 @@ def run_fuzz(fx, oracle, iters, seed, verbose=True):
             else: os.environ[k] = v
 
 
+def _cuts(xs, ncut, seed, it):
+    """interior cuts at len k / ncut plus a per-stream offset of up to half a block either way, so that a cut meets a frame at an
+    arbitrary phase.  The offsets come from a generator of their own, keyed by (seed, iteration): every other draw of a seed
+    stays what it was."""
+    crng = np.random.default_rng([seed, it, 0xC075])
+    out = []
+    for x in xs:
+        half = len(x) // (2 * ncut)
+        off = int(crng.integers(-half + 1, half)) if ncut > 1 else 0
+        out.append([0] + [len(x) * k // ncut + off for k in range(1, ncut)] + [len(x)])
+    return out
+
+
 def _run(fx, oracle, iters, seed, verbose):
     rng = np.random.default_rng(seed)
     mods, inner, outer = list(fx.MOD_BY_INDEX), list(fx.INNER_BY_INDEX), list(fx.OUTER_BY_INDEX)
@@ -42,7 +55,7 @@ def _run(fx, oracle, iters, seed, verbose):
         if rng.random() < 0.12:                                                      # ... and the detector-only mode (frame_detector_cc)
             ctx = fx.RxContext(ns, mode=fx.MODE_DETECTOR, threshold=0.45, segment_len=seg); ctx.set_depth(depth)
             got, inflight, keep = [], 0, []
-            cuts = [[len(x) * k // ncut for k in range(ncut + 1)] for x in xs]
+            cuts = _cuts(xs, ncut, seed, it)
             for k in range(ncut):
                 parts = [np.ascontiguousarray(x[c[k]:c[k + 1]]) for x, c in zip(xs, cuts)]; keep.append(parts)
                 if inflight == depth: got += ctx.results(ctx.collect_raw()); inflight -= 1
@@ -62,7 +75,7 @@ def _run(fx, oracle, iters, seed, verbose):
         ofs = [oracle_frames(oracle, x, equalizer=eq, soft=soft) for x in xs]
         ctx = fx.RxContext(ns, want_framesyms=True, segment_len=seg, equalizer=eq, soft_decision=soft); ctx.set_depth(depth)
         got, inflight = [], 0
-        cuts = [[len(x) * k // ncut for k in range(ncut + 1)] for x in xs]
+        cuts = _cuts(xs, ncut, seed, it)
         keep = []
         on_dev = bool(rng.random() < 0.25)                                       # inputs already in device memory (used in place)
         for k in range(ncut):
