@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "fx_common.h"
+#include "fx_launch.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

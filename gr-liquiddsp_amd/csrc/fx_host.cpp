@@ -45,49 +45,7 @@
 #include "../../include/fxrx.h"
 #include "fx_device.h"
 #include "fx_codec.hpp"
-
-extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, int sh, unsigned njobs, hipStream_t st, const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results,
-                                     FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, const FxTables *T, int ext, uint32_t n_jobs_total,
-                                     const uint32_t *n_list, uint32_t list_cap);
-extern "C" hipError_t fx_launch_seekverify(unsigned grid, hipStream_t st, const FxVerifyRun *runs, uint32_t run_cap, const FxWalkJob *jobs, FxWalkResult *results,
-                                           FxFrame *frames, FxBlockHdr *hdr, const FxTables *T, uint32_t phase);
-extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, int sh, unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total,
-                                      FxWalkResult *results, FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap,
-                                      FxBlockHdr *hdr, uint32_t force_slow, const FxTables *T);
-extern "C" hipError_t fx_launch_hdrdec(int soft, unsigned n, hipStream_t st, const uint8_t *in, uint8_t *out, int32_t *valid, const FxTables *T);
-extern "C" hipError_t fx_launch_blkdec(int soft, unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T);
-extern "C" hipError_t fx_launch_blksiso(unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T);
-extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, const FxWalkResult *results,
-                                          const FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxBlockHdr *hdr, uint32_t force_repair,
-                                          FxWalkJob *jobs_rw, uint32_t *req_list, uint32_t *stat, uint32_t pass);
-extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
-                                     const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap,
-                                     uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
-                                     FxBlockHdr *hdr_host, uint32_t *plan_ws, int fused);
-extern "C" unsigned fx_plan_ws_words(void);
-// (gang launches, fx_common.h: one launch for up to FX_GANG_MAX blocks; members without waves are left out)
-extern "C" hipError_t fx_launch_vbpre(const FxVbpreGang *gang, hipStream_t st, const FxTables *T, int clean_on, int early_tail);
-extern "C" hipError_t fx_launch_vbitems(unsigned first_item, unsigned n_items, hipStream_t st, const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap,
-                                        const FxBlockHdr *hdr, uint8_t *bufA, const uint8_t *bufB, unsigned long long *dwv, uint8_t *vec_arena, uint32_t *vb_st, uint32_t dbg, int packed,
-                                        int with_fix);
-extern "C" hipError_t fx_launch_vbfinish(unsigned first_wave, unsigned n_waves, hipStream_t st, const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHdr *hdr,
-                                         uint8_t *bufA, uint8_t *bufB, unsigned long long *dwv, const uint8_t *vec_arena, const uint32_t *vb_st, uint32_t *fb_list, uint32_t list_cap,
-                                         uint8_t *out, FxOutRec *recs, FxBlockHdr *hdr_host, int early_tail);
-extern "C" hipError_t fx_launch_paymf(unsigned grid, int eq, hipStream_t st, const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr,
-                                      const FxFrame *chain, float2 *sym_raw, const FxTables *T);
-extern "C" hipError_t fx_launch_paypll(const FxPllGang *gang, const unsigned *grid_waves, unsigned waves_per_wg, hipStream_t st, const FxTables *T);
-extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
-                                       const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
-                                       unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host);
-extern "C" hipError_t fx_launch_symcopy(unsigned grid, hipStream_t st, const FxBlockHdr *hdr, const float2 *sym, float2 *host);
-extern "C" hipError_t fx_launch_upload(hipStream_t st, const void *src, void *dst, size_t bytes, unsigned n_cus);
-extern "C" hipError_t fx_launch_ingest(hipStream_t st, int fmt, const void *src, float2 *dst, size_t n, float scale, unsigned n_cus);   // fx_ingest.hip
-extern "C" hipError_t fx_launch_detwin(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, const uint32_t *stream_base, const FxPayJob *pjobs,
-                                       const FxBlockHdr *hdr, uint32_t first, uint32_t reserved, float2 *out, float2 *out_tail, uint32_t *flag_host, int with_tails,
-                                       int skip_tail);   // fx_detwin.hip
-extern "C" hipError_t fx_launch_copy_u32(hipStream_t st, const uint32_t *src, uint32_t *dst);
-extern "C" hipError_t fx_launch_softdemod(unsigned grid, hipStream_t st, const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr,
-                                          const float2 *framesyms, const uint8_t *hard, uint8_t *soft_arena, const FxTables *T);
+#include "fx_launch.h"
 
 namespace {
 
@@ -371,6 +329,42 @@ int alloc_carry(StreamState &S, int64_t cap)
     }
     S.carry_cap = cap;
     return 0;
+}
+
+// the codes the decode kernel's block decoders take (fxrx_debug_block_decode, fxrx_debug_block_siso)
+bool is_block_fec(unsigned fec)
+{
+    return fec == FX_FEC_HAMMING74 || fec == FX_FEC_HAMMING84 || fec == FX_FEC_HAMMING128 || fec == FX_FEC_GOLAY2412 ||
+           fec == FX_FEC_SECDED2216 || fec == FX_FEC_SECDED3932 || fec == FX_FEC_SECDED7264;
+}
+
+// What the fxrx_debug_* decoders share: tables and input up, launch(d_in, d_out, d_out2, d_tables) on the null stream, outputs
+// back, everything freed on every path.  who: the entry point, for the error message; in_pad: spare bytes behind the input;
+// out2: a second output, or null.
+template <class Launch>
+int debug_decode(const char *who, const uint8_t *in, size_t in_bytes, size_t in_pad, void *out, size_t out_bytes, void *out2, size_t out2_bytes,
+                        Launch launch)
+{
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_err(std::string(who) + ": no usable HIP device"); return FXRX_ERR_NODEVICE; }
+    std::unique_ptr<FxTables> t = make_tables();
+    FxTables *d_t = nullptr; uint8_t *d_in = nullptr, *d_out = nullptr, *d_out2 = nullptr;
+    auto run = [&]() -> int {
+        HIP_OK(hipMalloc((void **)&d_t, sizeof(FxTables)));
+        HIP_OK(hipMalloc((void **)&d_in, in_bytes + in_pad));
+        HIP_OK(hipMalloc((void **)&d_out, out_bytes));
+        if (out2) HIP_OK(hipMalloc((void **)&d_out2, out2_bytes));
+        HIP_OK(hipMemcpy(d_t, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
+        HIP_OK(launch(d_in, d_out, d_out2, d_t));
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+        if (out2) HIP_OK(hipMemcpy(out2, d_out2, out2_bytes, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    const int rc = run();
+    for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out, (void *)d_out2 }) if (p) (void)hipFree(p);
+    return rc;
 }
 
 }  // namespace
@@ -1391,85 +1385,30 @@ int fxrx_debug_fail(fxrx_ctx *c, unsigned int submits, unsigned int collects)
 
 int fxrx_debug_header_decode(int soft, const uint8_t *in, unsigned int n, uint8_t *out20, int *valid)
 {
+    static_assert(sizeof(int) == sizeof(int32_t), "the kernel writes int32_t flags");
     if (!in || !out20 || !valid) return FXRX_ERR_ARG;
     if (n == 0) return 0;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_err("fxrx_debug_header_decode: no usable HIP device"); return FXRX_ERR_NODEVICE; }
-    const size_t in_bytes = (size_t)n * (soft ? 8 * FX_HDR_ENC : FX_HDR_ENC);
-    std::unique_ptr<FxTables> t = make_tables();
-    FxTables *d_t = nullptr; uint8_t *d_in = nullptr, *d_out = nullptr; int32_t *d_valid = nullptr;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void **)&d_t, sizeof(FxTables)));
-        HIP_OK(hipMalloc((void **)&d_in, in_bytes));
-        HIP_OK(hipMalloc((void **)&d_out, (size_t)n * FX_HDR_DEC));
-        HIP_OK(hipMalloc((void **)&d_valid, (size_t)n * sizeof(int32_t)));
-        HIP_OK(hipMemcpy(d_t, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
-        HIP_OK(fx_launch_hdrdec(soft ? 1 : 0, n, nullptr, d_in, d_out, d_valid, d_t));
-        HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipMemcpy(out20, d_out, (size_t)n * FX_HDR_DEC, hipMemcpyDeviceToHost));
-        std::vector<int32_t> v(n);
-        HIP_OK(hipMemcpy(v.data(), d_valid, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (unsigned i = 0; i < n; i++) valid[i] = v[i];
-        return 0;
-    };
-    const int rc = run();
-    for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out, (void *)d_valid }) if (p) (void)hipFree(p);
-    return rc;
+    return debug_decode("fxrx_debug_header_decode", in, (size_t)n * (soft ? 8 * FX_HDR_ENC : FX_HDR_ENC), 0, out20, (size_t)n * FX_HDR_DEC, valid, (size_t)n * sizeof(int32_t),
+                        [&](const uint8_t *d_in, uint8_t *d_out, uint8_t *d_valid, const FxTables *d_t) {
+                            return fx_launch_hdrdec(soft ? 1 : 0, n, nullptr, d_in, d_out, reinterpret_cast<int32_t *>(d_valid), d_t);
+                        });
 }
 
 int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out)
 {
-    const bool block = fec == FX_FEC_HAMMING74 || fec == FX_FEC_HAMMING84 || fec == FX_FEC_HAMMING128 || fec == FX_FEC_GOLAY2412 ||
-                       fec == FX_FEC_SECDED2216 || fec == FX_FEC_SECDED3932 || fec == FX_FEC_SECDED7264;
-    if (!block || !in || !out || n == 0 || n > 65535) { set_err("fxrx_debug_block_decode: bad argument"); return FXRX_ERR_ARG; }
+    if (!is_block_fec(fec) || !in || !out || n == 0 || n > 65535) { set_err("fxrx_debug_block_decode: bad argument"); return FXRX_ERR_ARG; }
     if (count == 0) return 0;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_err("fxrx_debug_block_decode: no usable HIP device"); return FXRX_ERR_NODEVICE; }
-    const size_t el = fx::fec_enc_len(fec, n), in_bytes = (size_t)count * el * (soft ? 8 : 1), out_bytes = (size_t)count * n;
-    std::unique_ptr<FxTables> t = make_tables();
-    FxTables *d_t = nullptr; uint8_t *d_in = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void **)&d_t, sizeof(FxTables)));
-        HIP_OK(hipMalloc((void **)&d_in, in_bytes));
-        HIP_OK(hipMalloc((void **)&d_out, out_bytes));
-        HIP_OK(hipMemcpy(d_t, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
-        HIP_OK(fx_launch_blkdec(soft ? 1 : 0, fec, n, count, nullptr, d_in, d_out, d_t));
-        HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = run();
-    for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out }) if (p) (void)hipFree(p);
-    return rc;
+    return debug_decode("fxrx_debug_block_decode", in, (size_t)count * fx::fec_enc_len(fec, n) * (soft ? 8 : 1), 0, out, (size_t)count * n, nullptr, 0,
+                        [&](const uint8_t *d_in, uint8_t *d_out, uint8_t *, const FxTables *d_t) { return fx_launch_blkdec(soft ? 1 : 0, fec, n, count, nullptr, d_in, d_out, d_t); });
 }
 
 int fxrx_debug_block_siso(unsigned int fec, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out_soft)
 {
-    const bool block = fec == FX_FEC_HAMMING74 || fec == FX_FEC_HAMMING84 || fec == FX_FEC_HAMMING128 || fec == FX_FEC_GOLAY2412 ||
-                       fec == FX_FEC_SECDED2216 || fec == FX_FEC_SECDED3932 || fec == FX_FEC_SECDED7264;
-    if (!block || !in || !out_soft || n == 0 || n > 65535) { set_err("fxrx_debug_block_siso: bad argument"); return FXRX_ERR_ARG; }
+    if (!is_block_fec(fec) || !in || !out_soft || n == 0 || n > 65535) { set_err("fxrx_debug_block_siso: bad argument"); return FXRX_ERR_ARG; }
     if (count == 0) return 0;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { set_err("fxrx_debug_block_siso: no usable HIP device"); return FXRX_ERR_NODEVICE; }
-    const size_t in_bytes = (size_t)count * fx::fec_enc_len(fec, n) * 8, out_bytes = (size_t)count * n * 8;
-    std::unique_ptr<FxTables> t = make_tables();
-    FxTables *d_t = nullptr; uint8_t *d_in = nullptr, *d_out = nullptr;
-    auto run = [&]() -> int {
-        HIP_OK(hipMalloc((void **)&d_t, sizeof(FxTables)));
-        HIP_OK(hipMalloc((void **)&d_in, in_bytes + 16));                // (the decoders load whole words)
-        HIP_OK(hipMalloc((void **)&d_out, out_bytes));
-        HIP_OK(hipMemcpy(d_t, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice));
-        HIP_OK(fx_launch_blksiso(fec, n, count, nullptr, d_in, d_out, d_t));
-        HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipMemcpy(out_soft, d_out, out_bytes, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = run();
-    for (void *p : { (void *)d_t, (void *)d_in, (void *)d_out }) if (p) (void)hipFree(p);
-    return rc;
+    // (16 spare input bytes: the decoders load whole words)
+    return debug_decode("fxrx_debug_block_siso", in, (size_t)count * fx::fec_enc_len(fec, n) * 8, 16, out_soft, (size_t)count * n * 8, nullptr, 0,
+                        [&](const uint8_t *d_in, uint8_t *d_out, uint8_t *, const FxTables *d_t) { return fx_launch_blksiso(fec, n, count, nullptr, d_in, d_out, d_t); });
 }
 
 static int collect_block(fxrx_ctx_s *c)

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstdint>
 #include "../../include/fxrx.h"
+#include "fx_launch.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

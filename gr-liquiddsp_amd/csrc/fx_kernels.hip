@@ -23,11 +23,16 @@
 //                       convolutional inner code, and whatever the batch path hands back.
 //   fx_softdemod_kernel, fx_symcopy_kernel, fx_txgen_kernel, fx_txenc_kernel   optional stage / results / frame generator.
 //
+// One __global__ template per stage: the options are template arguments (fx_walk_kernel and fx_chain_kernel: EQ equaliser, SH soft
+// header; fx_paydec_kernel: SOFT, SB soft block, SC soft chain), and each launcher picks its instance in one place.  The
+// launchers' prototypes are in fx_launch.h.
+//
 // No MFMA anywhere: nothing on this path is a dense contraction.  Taps, windows, spectra and the
 // FFT exchange buffers live in LDS; IQ is read from HBM as coalesced float2.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "fx_device.h"
+#include "fx_launch.h"
 #include "fx_vbclean.h"
 
 // 8 waves: the 49 CFO-sweep transforms of a hop take 7 rounds instead of 13.  The 512-sample window is still
@@ -899,10 +904,6 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
             if (hw >= 0 && locked) {
                 // candidate in the window of grid hop hw: resume the exact detector there (one hop earlier when the
                 // candidate sits at the very start of the window -- the two correlators may disagree by a sample)
-#ifdef FX_EXACT_HOPS_OLD
-                exact_left = 3;
-                if (L.cand[hw] < 8u && hw > 0) { hw--; exact_left = 4; }
-#else
                 // The exact detector accepts a peak at lags below 512 - 156 only, like this one: a candidate well inside that range is
                 // this very hop's detection or nobody's (a false alarm of the cheap correlator costs ONE sweep of 50 transforms, not
                 // three); near either end of the range the two correlators may place it in the neighbouring hop.  Whatever this misjudges,
@@ -910,7 +911,6 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
                 const uint32_t cl_ = L.cand[hw];
                 exact_left = cl_ >= FX_NFFT - FX_S_LEN - 12u ? 2 : 1;
                 if (cl_ < 8u && hw > 0) { hw--; exact_left = 2; }
-#endif
                 hops_cheap -= WALK_WAVES - hw;
                 if (hw > 0) {
                     const float2 w = lo ? L.cw[FX_HOP * hw + tid] : make_float2(0.0f, 0.0f);
@@ -982,11 +982,7 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
             __syncthreads();
             const float cpk = L.f[4]; const uint32_t cl = L.u[8];
             if (cpk > 0.06f * ed * T->td2sum * (float)FX_NFFT * (float)FX_NFFT && ed > 0.0f) {
-#ifdef FX_EXACT_HOPS_OLD
-                if (locked) { coarse_hit = true; exact_left = 3; hops_cheap--; }   // run the exact detector on this very hop
-#else
                 if (locked) { coarse_hit = true; exact_left = cl >= FX_NFFT - FX_S_LEN - 12u ? 2 : 1; hops_cheap--; }   // run the exact detector on this very hop
-#endif
                 else {
                     // candidate preamble at p: the exact detector takes over on the hop whose new half starts at p (see above)
                     const int64_t p = pos - FX_HOP + (int64_t)cl;
@@ -1393,11 +1389,14 @@ __device__ __forceinline__ void walk_any(const FxWalkJob &job, uint32_t job_inde
     else walk_run<MODE, WW, EQ, EXT, SH>(job, job_index, result, frames, runs, run_cap, hdr, T, L, twA, twB, all_jobs, all_results, n_jobs_total);
 }
 
-template <int MODE, int WW, bool EQ, bool EXT = false>
+// SH: the soft-header walker (fxrx_config.soft_header; flex_rx only).  Like EQ and EXT it is a template argument: an instance's code
+// depends on its arguments alone, so the default instances carry none of the variant's.
+template <int MODE, int WW, bool EQ, bool EXT = false, bool SH = false>
 __global__ __launch_bounds__(64 * WW, MODE == FX_MODE_DETECT ? FX_DETECT_OCC : FX_FLEX_OCC) FX_WALK_VGPR_ATTR
 void fx_walk_kernel(const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results, FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap,
                     FxBlockHdr *hdr, const FxTables *T, uint32_t n_jobs_total, const uint32_t *n_list, uint32_t list_cap)
 {
+    static_assert(!SH || MODE == FX_MODE_FLEXRX, "soft header decoding is a flex_rx variant");
     __shared__ typename WalkLdsSel<MODE, WW>::type L;
     const int tid = threadIdx.x, lane = tid & 63;
     if constexpr (EXT) {
@@ -1415,7 +1414,7 @@ void fx_walk_kernel(const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResul
             for (uint32_t i = blockIdx.x; i < nreq; i += gridDim.x) {
                 const uint32_t ji = job_list[i] & 0x7fffffffu;
                 const FxWalkJob job = jobs[ji];
-                walk_any<MODE, WW, EQ, EXT>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
+                walk_any<MODE, WW, EQ, EXT, SH>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
                 __syncthreads();
             }
             return;
@@ -1423,45 +1422,10 @@ void fx_walk_kernel(const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResul
     }
     const uint32_t ji = job_list[blockIdx.x] & 0x7fffffffu;
     const FxWalkJob job = jobs[ji];
-    walk_any<MODE, WW, EQ, EXT>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
-}
-// the soft-header walker (fxrx_config.soft_header; flex_rx only): a kernel of its own, so that the default instances keep their
-// names and their code (the same prologue as fx_walk_kernel's; shared through a function, the detector's repair instance compiled
-// differently)
-template <int WW, bool EQ, bool EXT = false>
-__global__ __launch_bounds__(64 * WW, FX_FLEX_OCC) FX_WALK_VGPR_ATTR
-void fx_walk_sh_kernel(const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results, FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap,
-                       FxBlockHdr *hdr, const FxTables *T, uint32_t n_jobs_total, const uint32_t *n_list, uint32_t list_cap)
-{
-    __shared__ WalkLdsT<WW> L;
-    const int tid = threadIdx.x, lane = tid & 63;
-    if constexpr (EXT) {
-        // (the repair round enqueued with the block, as in fx_walk_kernel)
-        if (n_list && blockIdx.x >= min(*n_list, list_cap)) return;
-    }
-    float2 twA[7], twB[7];
-#pragma unroll
-    for (int r = 1; r < 8; r++) { twA[r - 1] = T->tw[lane * r]; twB[r - 1] = T->tw[8 * (lane & 7) * r]; }
-    for (int i = tid; i < FX_NFFT; i += 64 * WW) L.S[i] = T->S[i];
-    if constexpr (EXT) {
-        if (n_list) {
-            const uint32_t nreq = min(*n_list, list_cap);
-            for (uint32_t i = blockIdx.x; i < nreq; i += gridDim.x) {
-                const uint32_t ji = job_list[i] & 0x7fffffffu;
-                const FxWalkJob job = jobs[ji];
-                walk_any<FX_MODE_FLEXRX, WW, EQ, EXT, true>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
-                __syncthreads();
-            }
-            return;
-        }
-    }
-    const uint32_t ji = job_list[blockIdx.x] & 0x7fffffffu;
-    const FxWalkJob job = jobs[ji];
-    walk_any<FX_MODE_FLEXRX, WW, EQ, EXT, true>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
+    walk_any<MODE, WW, EQ, EXT, SH>(job, ji, results + ji, frames, runs, run_cap, hdr, T, L, twA, twB, jobs, results, n_jobs_total);
 }
 
-
-// (the equaliser stage is a compile-time variant of the flex_rx walker: the default instance carries none of its code)
+// (the equaliser stage and the soft header are compile-time variants of the flex_rx walker: the default instance carries none of their code)
 // ext: the walks of a repair round (they may carry on into the segments behind theirs); n_list (ext only): the number of queued
 // segments is read from there on the device and `njobs` workgroups stride over them (list_cap bounds the count); sh: soft header
 extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, int sh, unsigned njobs, hipStream_t st, const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results,
@@ -1469,18 +1433,15 @@ extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, int sh, unsigned njo
                                      const uint32_t *n_list, uint32_t list_cap)
 {
     if (njobs == 0) return hipSuccess;
-#define FX_WALK_LAUNCH(M, W, E, X) hipLaunchKernelGGL((fx_walk_kernel<M, W, E, X>), dim3(njobs), dim3(64 * W), 0, st, jobs, job_list, results, frames, runs, run_cap, hdr, T, n_jobs_total, n_list, list_cap)
-    if (mode == FX_MODE_DETECT) { if (ext) FX_WALK_LAUNCH(FX_MODE_DETECT, FX_DETECT_WAVES, false, true); else FX_WALK_LAUNCH(FX_MODE_DETECT, FX_DETECT_WAVES, false, false); }
-    else if (sh) {
-#define FX_WALK_SH_LAUNCH(E, X) hipLaunchKernelGGL((fx_walk_sh_kernel<FX_FLEX_WAVES, E, X>), dim3(njobs), dim3(64 * FX_FLEX_WAVES), 0, st, jobs, job_list, results, frames, runs, run_cap, hdr, T, n_jobs_total, n_list, list_cap)
-        if (ext) { if (eq) FX_WALK_SH_LAUNCH(true, true); else FX_WALK_SH_LAUNCH(false, true); }
-        else if (eq) FX_WALK_SH_LAUNCH(true, false);
-        else FX_WALK_SH_LAUNCH(false, false);
-#undef FX_WALK_SH_LAUNCH
-    }
-    else if (ext) { if (eq) FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, true, true); else FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, false, true); }
-    else if (eq) FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, true, false);
-    else FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, false, false);
+#define FX_WALK_LAUNCH(M, W, E, X, S) hipLaunchKernelGGL((fx_walk_kernel<M, W, E, X, S>), dim3(njobs), dim3(64 * W), 0, st, jobs, job_list, results, frames, runs, run_cap, hdr, T, n_jobs_total, n_list, list_cap)
+#define FX_WALK_FLEX(S) do { \
+        if (ext) { if (eq) FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, true, true, S); else FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, false, true, S); } \
+        else if (eq) FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, true, false, S); \
+        else FX_WALK_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, false, false, S); } while (0)
+    if (mode == FX_MODE_DETECT) { if (ext) FX_WALK_LAUNCH(FX_MODE_DETECT, FX_DETECT_WAVES, false, true, false); else FX_WALK_LAUNCH(FX_MODE_DETECT, FX_DETECT_WAVES, false, false, false); }
+    else if (sh) FX_WALK_FLEX(true);
+    else FX_WALK_FLEX(false);
+#undef FX_WALK_FLEX
 #undef FX_WALK_LAUNCH
     return hipGetLastError();
 }
@@ -1865,7 +1826,7 @@ extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, con
 }
 
 // The full-size chain kernel: same fast path, and behind it the general, sequential one that can walk.
-// SH: the repair walks decode headers like the segments' walkers did (fx_walk_sh_kernel), or speculation would not be exact.
+// SH: the repair walks decode headers like the segments' walkers did (fx_walk_kernel's SH instances), or speculation would not be exact.
 template <int MODE, int WW, bool EQ, bool SH>
 __device__ __forceinline__ void chain_kernel_body(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total, FxWalkResult *results,
                                                   FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap,
@@ -1969,47 +1930,29 @@ __device__ __forceinline__ void chain_kernel_body(const FxStreamDesc *streams, c
     chain_finish<NT>(sd, s, st_in, cnt, fin_pos, fin_floor, fin_fresh, chain_count, hdr);
 }
 
-template <int MODE, int WW, bool EQ>
+template <int MODE, int WW, bool EQ, bool SH = false>
 __global__ __launch_bounds__(64 * WW, 1)
 void fx_chain_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total, FxWalkResult *results, FxFrame *frames,
                      FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, uint32_t force_slow,
                      const FxTables *T)
 {
+    static_assert(!SH || MODE == FX_MODE_FLEXRX, "soft header decoding is a flex_rx variant");
     __shared__ typename WalkLdsSel<MODE, WW>::type L;
     __shared__ ChainLds C;
-    chain_kernel_body<MODE, WW, EQ, false>(streams, jobs, n_jobs_total, results, frames, chain, chain_count, runs, run_cap, hdr, force_slow, T, L, C);
-}
-// the soft-header chain kernel (flex_rx only)
-template <int WW, bool EQ>
-__global__ __launch_bounds__(64 * WW, 1)
-void fx_chain_sh_kernel(const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total, FxWalkResult *results, FxFrame *frames,
-                        FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, uint32_t force_slow,
-                        const FxTables *T)
-{
-    __shared__ WalkLdsT<WW> L;
-    __shared__ ChainLds C;
-    chain_kernel_body<FX_MODE_FLEXRX, WW, EQ, true>(streams, jobs, n_jobs_total, results, frames, chain, chain_count, runs, run_cap, hdr, force_slow, T, L, C);
+    chain_kernel_body<MODE, WW, EQ, SH>(streams, jobs, n_jobs_total, results, frames, chain, chain_count, runs, run_cap, hdr, force_slow, T, L, C);
 }
 
 extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, int sh, unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total,
                                       FxWalkResult *results, FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxVerifyRun *runs, uint32_t run_cap,
                                       FxBlockHdr *hdr, uint32_t force_slow, const FxTables *T)
 {
-    if (mode == FX_MODE_DETECT)
-        hipLaunchKernelGGL((fx_chain_kernel<FX_MODE_DETECT, FX_DETECT_WAVES, false>), dim3(nstreams), dim3(64 * FX_DETECT_WAVES), 0, st, streams, jobs, n_jobs_total, results,
-                           frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
-    else if (sh && eq)
-        hipLaunchKernelGGL((fx_chain_sh_kernel<FX_FLEX_WAVES, true>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
-                           frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
-    else if (sh)
-        hipLaunchKernelGGL((fx_chain_sh_kernel<FX_FLEX_WAVES, false>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
-                           frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
-    else if (eq)
-        hipLaunchKernelGGL((fx_chain_kernel<FX_MODE_FLEXRX, FX_FLEX_WAVES, true>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
-                           frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
-    else
-        hipLaunchKernelGGL((fx_chain_kernel<FX_MODE_FLEXRX, FX_FLEX_WAVES, false>), dim3(nstreams), dim3(64 * FX_FLEX_WAVES), 0, st, streams, jobs, n_jobs_total, results,
-                           frames, chain, chain_count, runs, run_cap, hdr, force_slow, T);
+#define FX_CHAIN_LAUNCH(M, W, E, S) hipLaunchKernelGGL((fx_chain_kernel<M, W, E, S>), dim3(nstreams), dim3(64 * W), 0, st, streams, jobs, n_jobs_total, results, frames, chain, chain_count, runs, run_cap, hdr, force_slow, T)
+#define FX_CHAIN_FLEX(S) do { if (eq) FX_CHAIN_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, true, S); else FX_CHAIN_LAUNCH(FX_MODE_FLEXRX, FX_FLEX_WAVES, false, S); } while (0)
+    if (mode == FX_MODE_DETECT) FX_CHAIN_LAUNCH(FX_MODE_DETECT, FX_DETECT_WAVES, false, false);
+    else if (sh) FX_CHAIN_FLEX(true);
+    else FX_CHAIN_FLEX(false);
+#undef FX_CHAIN_FLEX
+#undef FX_CHAIN_LAUNCH
     return hipGetLastError();
 }
 
@@ -3876,12 +3819,17 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
     FX_STAMP(5);
 }
 
-template <bool WITH_RS, bool SOFT>
+// SB: the soft-block variant (fxrx_config.soft_block), soft-input block decoders; SC: the soft-chain variant (fxrx_config.soft_chain),
+// SB with soft-output block decoders in front of a convolutional fec0.  Template arguments of dec_frame: the default instances
+// carry none of their code.
+template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false>
 __global__ __launch_bounds__(WITH_RS ? DEC_THREADS : DEC_THREADS * DEC_MAX_WAVES)
 void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA,
                       uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T,
                       FxBlockHdr *fallback_host)
 {
+    static_assert(!SB || SOFT, "soft-input block decoders need soft decisions");
+    static_assert(!SC || SB, "soft-output block decoders are a variant of the soft-input ones");
     // The list's length is known on the device only.  The lean instance has no loop around its body (a grid-stride loop
     // doubles the register footprint): the host launches it over the list's capacity -- a grid sized from the previous block
     // plus a second, normally idle one for the rest -- and surplus waves leave at once.  The Reed-Solomon instance strides.
@@ -3895,60 +3843,14 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
     if (ji0 >= njobs) return;
     __builtin_amdgcn_s_setprio(2);
     if constexpr (WITH_RS) {
-        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, SOFT>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
+        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, SOFT, SB, SC>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
     } else {
-        dec_frame<false, SOFT>(ji0, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
+        dec_frame<false, SOFT, SB, SC>(ji0, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
     }
 }
 
-// the soft-block variant (fxrx_config.soft_block): fx_paydec_kernel<WITH_RS, true> with soft-input block decoders, in kernels of
-// its own so that the default instances keep their code
-template <bool WITH_RS>
-__global__ __launch_bounds__(WITH_RS ? DEC_THREADS : DEC_THREADS * DEC_MAX_WAVES)
-void fx_paydec_sb_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA,
-                         uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T,
-                         FxBlockHdr *fallback_host)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t Xs[WITH_RS ? 16 : DEC_LDS];
-    uint8_t *X = (!WITH_RS && blockDim.x == 64) ? Xs : nullptr;
-    const uint32_t njobs = WITH_RS ? hdr->n_dec_rs : (fallback_host ? hdr->n_vb_fallback : hdr->n_dec_plain);
-    const uint32_t wpg = blockDim.x >> 6;
-    const int lane = threadIdx.x & 63;
-    const uint32_t ji0 = __builtin_amdgcn_readfirstlane(first_wave + blockIdx.x * wpg + (threadIdx.x >> 6));
-    if (ji0 >= njobs) return;
-    __builtin_amdgcn_s_setprio(2);
-    if constexpr (WITH_RS) {
-        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, true, true>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
-    } else {
-        dec_frame<false, true, true>(ji0, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
-    }
-}
-
-// the soft-chain variant (fxrx_config.soft_chain): fx_paydec_sb_kernel with soft-output block decoders in front of a convolutional
-// fec0, again in kernels of its own
-template <bool WITH_RS>
-__global__ __launch_bounds__(WITH_RS ? DEC_THREADS : DEC_THREADS * DEC_MAX_WAVES)
-void fx_paydec_sc_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA,
-                         uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T,
-                         FxBlockHdr *fallback_host)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t Xs[WITH_RS ? 16 : DEC_LDS];
-    uint8_t *X = (!WITH_RS && blockDim.x == 64) ? Xs : nullptr;
-    const uint32_t njobs = WITH_RS ? hdr->n_dec_rs : (fallback_host ? hdr->n_vb_fallback : hdr->n_dec_plain);
-    const uint32_t wpg = blockDim.x >> 6;
-    const int lane = threadIdx.x & 63;
-    const uint32_t ji0 = __builtin_amdgcn_readfirstlane(first_wave + blockIdx.x * wpg + (threadIdx.x >> 6));
-    if (ji0 >= njobs) return;
-    __builtin_amdgcn_s_setprio(2);
-    if constexpr (WITH_RS) {
-        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, true, true, true>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
-    } else {
-        dec_frame<false, true, true, true>(ji0, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
-    }
-}
-
-// soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input block decoders (fx_paydec_sb_kernel), 3 those with
-// soft-output block decoders in front of a convolutional fec0 (fx_paydec_sc_kernel)
+// soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input block decoders (SB), 3 those with soft-output block
+// decoders in front of a convolutional fec0 (SB and SC)
 extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host)
@@ -3956,15 +3858,11 @@ extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wav
     if (grid_waves == 0) return hipSuccess;
     const unsigned w = with_rs ? 1u : (waves_per_wg < 1u ? 1u : (waves_per_wg > DEC_MAX_WAVES ? DEC_MAX_WAVES : waves_per_wg));
     const dim3 grid((grid_waves + w - 1) / w), block(DEC_THREADS * w);
-#define FX_DEC_LAUNCH(RS, SF) hipLaunchKernelGGL((fx_paydec_kernel<RS, SF>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
-#define FX_DEC_SB_LAUNCH(RS) hipLaunchKernelGGL((fx_paydec_sb_kernel<RS>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
-#define FX_DEC_SC_LAUNCH(RS) hipLaunchKernelGGL((fx_paydec_sc_kernel<RS>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
-    if (soft == 3) { if (with_rs) FX_DEC_SC_LAUNCH(true); else FX_DEC_SC_LAUNCH(false); }
-    else if (soft == 2) { if (with_rs) FX_DEC_SB_LAUNCH(true); else FX_DEC_SB_LAUNCH(false); }
-    else if (with_rs) { if (soft) FX_DEC_LAUNCH(true, true); else FX_DEC_LAUNCH(true, false); }
-    else { if (soft) FX_DEC_LAUNCH(false, true); else FX_DEC_LAUNCH(false, false); }
-#undef FX_DEC_SC_LAUNCH
-#undef FX_DEC_SB_LAUNCH
+#define FX_DEC_LAUNCH(RS, SF, SB, SC) hipLaunchKernelGGL((fx_paydec_kernel<RS, SF, SB, SC>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
+    if (soft == 3) { if (with_rs) FX_DEC_LAUNCH(true, true, true, true); else FX_DEC_LAUNCH(false, true, true, true); }
+    else if (soft == 2) { if (with_rs) FX_DEC_LAUNCH(true, true, true, false); else FX_DEC_LAUNCH(false, true, true, false); }
+    else if (with_rs) { if (soft) FX_DEC_LAUNCH(true, true, false, false); else FX_DEC_LAUNCH(true, false, false, false); }
+    else { if (soft) FX_DEC_LAUNCH(false, true, false, false); else FX_DEC_LAUNCH(false, false, false, false); }
 #undef FX_DEC_LAUNCH
     return hipGetLastError();
 }

@@ -20,14 +20,8 @@
 #include "../../include/fxrx.h"
 #include "fx_common.h"
 #include "fx_codec.hpp"
+#include "fx_launch.h"
 
-extern "C" hipError_t fx_launch_txgen(unsigned ntiles, hipStream_t st, const FxTxJob *jobs, const uint32_t *tile_job, const uint32_t *tile_n0,
-                                      const uint8_t *head_idx, const uint8_t *pay_idx, const FxTxTables *T, float2 *out);
-extern "C" hipError_t fx_launch_txenc(unsigned njobs, hipStream_t st, const FxTxEncJob *jobs, const uint8_t *pay, const uint32_t *perm_arena,
-                                      uint8_t *bufA, uint8_t *bufB, uint8_t *pay_idx, const FxTxTables *T);
-extern "C" hipError_t fx_launch_channel(hipStream_t st, float2 *x, unsigned n_streams, unsigned long long n_per_stream, const FxChannel *chs, const FxTxTables *T);
-extern "C" hipError_t fx_launch_quantize(hipStream_t st, int fmt, const float2 *in, void *out, size_t n, float inv_scale, unsigned long long *saturated,
-                                         unsigned n_cus);          // fx_ingest.hip
 extern "C" void fxrx_set_error(const char *msg);       // fx_host.cpp: thread-local message behind fxrx_last_error()
 
 namespace {

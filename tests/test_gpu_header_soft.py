@@ -235,6 +235,22 @@ def test_soft_header_low_snr_segmentation_and_gain(fx, low_snr_traffic):
     assert s >= SOFT_GAIN_FLOOR * h + 5, counts
 
 
+def test_soft_header_repair_walks_of_the_chain_kernel(fx, low_snr_traffic, monkeypatch):
+    """FXRX_CHAIN_SLOW=1 sends the block through the general path of the full-size chain kernel, whose repair walks must decode
+    headers softly like the segments' walkers did (fx_launch_chain's `sh`): same frames as the one-segment run, and it did walk.
+    Measured on an MI355X at segment_len=4096: 40 walk jobs, repairs 18, 80 frames (2048 and 1024 give the same counts)."""
+    x, _ = low_snr_traffic[2.0]
+    ref = _run(fx, [x], soft_header=True)
+    monkeypatch.setenv("FXRX_CHAIN_SLOW", "1")
+    ctx = fx.RxContext(1, soft_header=True, segment_len=4096)
+    got = sorted(ctx.process([x]), key=lambda f: (f["stream"], f["start"]))
+    tm = ctx.timing()
+    ctx.close()
+    print("repairs", tm["repairs"], "walk jobs", tm["walk_jobs"], "frames", len(got))
+    assert [_key(f) for f in got] == [_key(f) for f in ref]
+    assert tm["repairs"] > 0, "no repair walk ran: the chain kernel's soft-header walker was not exercised"
+
+
 # ---------------------------------------------------------------------------------------------------- (d) the drop-in
 def test_dropin_soft_header_matches_the_batched_context(fx, low_snr_traffic, monkeypatch):
     L = fx.lib()
