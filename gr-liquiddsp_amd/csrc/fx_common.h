@@ -115,7 +115,41 @@ struct FxWalkJob {
     uint32_t verify_per;    // hops per verification run
     uint32_t eq;            // 1: equaliser stage on (fxrx_config.equalizer)
     uint32_t pad_;
+    // pre-lock scan done ahead of the walker (fx_prescan_kernel; speculative flex_rx jobs only, else NULL / 0):
+    uint32_t *prescan;      // this job's chunk words, prescan_words of them, written by the block's own scan launch
+    uint32_t prescan_words; // chunks of FX_PRESCAN_CHUNK hops
+    uint32_t prescan_hops;  // hops of the grid start + 256 h the scan covers: fx_prescan_valid_hops(start, stop, n, K)
 };
+
+// ---- the pre-lock scan's chunk words.  A chunk is FX_PRESCAN_CHUNK consecutive hops of a speculative job's grid; its word
+// is hop << 16 | lag of the lowest hop whose coarse correlator hit (hop counted from the job's start), or FX_PRESCAN_NONE.
+#define FX_PRESCAN_CHUNK 16
+#define FX_PRESCAN_NONE  0xFFFFFFFFu
+#define FX_PRESCAN_MAX_HOPS 4096      /* what a word's hop field is asked to hold at the most (FXRX_PRESCAN_HOPS is clamped to it) */
+__host__ __device__ inline uint32_t fx_prescan_pack(uint32_t hop, uint32_t lag) { return hop << 16 | (lag & 0xFFFFu); }
+// hops h < K the walker itself would scan from `start` before it stops: new half inside the segment and inside the data
+__host__ __device__ inline uint32_t fx_prescan_valid_hops(int64_t start, int64_t stop, int64_t n, uint32_t K)
+{
+    int64_t a = (stop - start + FX_HOP - 1) / FX_HOP, b = (n - start) / FX_HOP;     // start + 256 h < stop; start + 256 h + 256 <= n
+    if (b < a) a = b;
+    if (a < 0) a = 0;
+    return a < (int64_t)K ? (uint32_t)a : K;
+}
+// the walker's entry: the first chunk word with a hit.  true: the candidate preamble starts at *p (the unlocked walker's
+// candidate branch takes over from there); false: no hit, the walker's own scan carries on at *p = start + 256 hops.
+// *scanned: hops to add to the cheap-hop counter.
+__host__ __device__ inline bool fx_prescan_entry(const uint32_t *words, uint32_t n_words, uint32_t hops, int64_t start, int64_t *p, uint32_t *scanned)
+{
+    for (uint32_t i = 0; i < n_words; i++) {
+        const uint32_t w = words[i];
+        if (w == FX_PRESCAN_NONE) continue;
+        const uint32_t h = w >> 16, lag = w & 0xFFFFu;
+        *p = start + (int64_t)FX_HOP * h - FX_HOP + (int64_t)lag; *scanned = h + 1;
+        return true;
+    }
+    *p = start + (int64_t)FX_HOP * hops; *scanned = hops;
+    return false;
+}
 
 struct FxFrameHead {        // 152 bytes: everything the walker keeps in registers while it builds a frame record
     int64_t  start;         // index of aligned sample 0 (may be < floor: zeros there)
@@ -197,7 +231,8 @@ struct FxBlockHdr {                      // device memory, zeroed at submit; mir
     uint32_t vb_ticket;                  // host mirror only: fx_vbfinish_kernel handed frames back to the wave-per-frame decoder (n_vb_fallback on the device says how many)
     uint32_t done;                       // host mirror only: written last
     uint32_t vb_dirty;                   // host mirror only: fx_vbpre_kernel (early tail) met a frame that needs the trellis kernels; zero from the plan stage
-    uint32_t pad_;
+    uint32_t ps_taken;                   // speculative walkers that took their first candidate from the pre-lock scan's table ...
+    uint32_t ps_fallback, pad_;          // ... and those whose table held none: their own scan carried on behind the scanned hops
     uint32_t stamp[8];
 };
 

@@ -4,6 +4,7 @@
 // A block (one fxrx_submit: new samples of every stream) is ONE chain of kernels enqueued on the block's own HIP stream;
 // the host never waits between them:
 //
+//   pre-lock scan (flex_rx)             -- fx_prescan_kernel: the first hops of every speculative segment, all at once
 //   walkers (speculative segments)      -- fx_walk_kernel, launched at once
 //   seek verification, phase 0          -- fx_seekverify_kernel over the runs those walkers emitted (continuing streams only)
 //   [wait: chain kernel of the previous block]   -- an event, on the device; from here to the chain kernel a block of
@@ -157,6 +158,8 @@ struct Slot {
     DevBuf<uint32_t> d_chain_count, d_stream_base, d_mf_job, d_mf_c0, d_pll_list, d_dec_list, d_vb_items;
     DevBuf<uint32_t> d_plan_ws;              // plan kernels: look-back state, list counts and cursors (zero between blocks)
     DevBuf<uint32_t> d_req;                  // repair rounds: segments to be walked again from their true start state
+    DevBuf<uint32_t> d_prescan;              // pre-lock scan: chunk words of the speculative jobs (ps_words each), written by fx_prescan_kernel in front of the walkers
+    uint32_t ps_jobs = 0, ps_words = 0, ps_hops = 0, ps_taken = 0, ps_fallback = 0;   // jobs scanned / chunks and hops per job; fxrx_debug_prescan_stats
     DevBuf<uint32_t> d_cstat;                // in-chain repair round: per stream 1 stitched | 2 pending (segments queued) | 3 left to fxrx_collect
     DevBuf<uint8_t> d_vb_vec;                // batch Viterbi: metric differences at the start and end of every trellis block
     DevBuf<unsigned long long> d_vb_dw;      // its decision words, step-major within the 64 work items of a wave
@@ -254,6 +257,11 @@ struct fxrx_ctx_s {
     // FXRX_TAIL_GANG: tails per gang launch (1: off; at most FX_GANG_MAX).  The PLL and fx_vbpre_kernel hold a hardware queue for as
     // long with one block's frames as with four blocks', and queue time is what bounds the pipeline.
     unsigned tail_gang = 4;
+    // FXRX_PRESCAN=1: the first hops of every speculative segment are scanned by fx_prescan_kernel ahead of the walkers (default 0: the
+    // walkers scan for their first preamble themselves -- measured faster on config 2, the extra launch costs more than the walkers
+    // save).  FXRX_PRESCAN_HOPS: hops scanned per speculative job instead of the traffic's figure (0: none).
+    bool prescan = false; int prescan_hops = -1;
+    uint64_t samples_hint = 0;           // samples of the last collected block (with frames_hint: the mean frame spacing)
     std::vector<Slot *> gang;            // the open gang: blocks in flight whose tails are deferred, oldest first
     uint64_t gang_launches = 0, gang_members = 0;   // fxrx_debug_gang_stats: tail launches that carried more than one block / the blocks they carried
 };
@@ -472,6 +480,8 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_PLAN_GRID")) c->plan_grid = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_DETWIN_RESERVE")) c->detwin_reserve = (uint32_t)std::max(0, std::atoi(e));
     if (const char *e = std::getenv("FXRX_VB_DEBUG")) c->vb_debug = (uint32_t)std::atoi(e);
+    if (const char *e = std::getenv("FXRX_PRESCAN")) c->prescan = std::atoi(e) != 0;
+    if (const char *e = std::getenv("FXRX_PRESCAN_HOPS")) c->prescan_hops = std::min<int>(FX_PRESCAN_MAX_HOPS, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_TAIL_GANG")) c->tail_gang = (unsigned)std::min(FX_GANG_MAX, std::max(1, std::atoi(e)));
     // (a block is at least as long as the warm-up of the next one: 128 steps)
     if (const char *e = std::getenv("FXRX_VB_BLK")) if (std::atoi(e) > 0) c->vb_blk_force = (uint32_t)std::min(4096, std::max(128, (std::atoi(e) + 63) / 64 * 64));
@@ -553,6 +563,17 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     hipStream_t st = sl.st;
     const double tp0 = g_prof_on ? prof_now() : 0.0;
 
+    // hops of every speculative job that fx_prescan_kernel scans ahead of the walkers (0: no such launch): a mean frame spacing
+    // of the last collected block plus two hops -- a segment start falls anywhere in a frame --, whole chunks
+    uint32_t ps_K = 0;
+    if (c->prescan && !detect) {
+        if (c->prescan_hops >= 0) ps_K = (uint32_t)c->prescan_hops;             // (as given: the last chunk may be a short one)
+        else {
+            ps_K = c->frames_hint ? (uint32_t)std::min<uint64_t>(128, std::max<uint64_t>(16, c->samples_hint / c->frames_hint / FX_HOP + 2)) : 64u;
+            ps_K = (ps_K + FX_PRESCAN_CHUNK - 1) / FX_PRESCAN_CHUNK * FX_PRESCAN_CHUNK;
+        }
+    }
+
     // ---- 1. segments ----
     uint64_t seg = c->cfg.segment_len;
     if (seg == 0) {
@@ -566,7 +587,9 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
         // kept busy by the other blocks anyway, so fewer, longer segments: down to one workgroup per two CUs.
         const uint64_t slots = (uint64_t)c->n_cus * c->walk_per_cu;
         // (about three blocks' walkers overlap at any time: keep that many workgroups' worth of segments between them)
-        if (c->depth > 1 && !detect) seg = tot / std::max<uint64_t>(std::max<uint64_t>(1, c->n_cus / 2), std::min<uint64_t>(slots, 3 * slots / c->depth));
+        // (Measured again with the tails ganged, DESIGN.md section 6, pre-scan log: twice as many segments, down to one workgroup per
+        // CU -- 6 x slots / depth, 256 at depth 12 -- give the higher rates on config 2.  Why they do is not established.)
+        if (c->depth > 1 && !detect) seg = tot / std::max<uint64_t>(std::max<uint64_t>(1, c->n_cus), std::min<uint64_t>(slots, 6 * slots / c->depth));
         else if (tot / slots < 131072) seg = tot / (slots - slots / 16);
         else seg = std::max<uint64_t>(tot / (4 * slots), 65536);
         seg = std::max<uint64_t>(seg, 32768); seg = std::min<uint64_t>(seg, 1u << 20);
@@ -675,9 +698,21 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     const double tp1 = g_prof_on ? prof_now() : 0.0;
     // ---- 2. memory ----
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_list = up16(NJ * sizeof(FxWalkJob)), o_streams = o_list + up16(NJ * sizeof(uint32_t)), desc_bytes = o_streams + up16(NS * sizeof(FxStreamDesc));
+    // (the job lists: early | late, NJ entries together, and behind them the speculative jobs the pre-lock scan takes)
+    const size_t o_list = up16(NJ * sizeof(FxWalkJob)), o_streams = o_list + up16(2 * NJ * sizeof(uint32_t)), desc_bytes = o_streams + up16(NS * sizeof(FxStreamDesc));
     sl.o_list = o_list; sl.o_streams = o_streams;
     const uint32_t list_cap = chain_slots + 64 * FX_PLL_CLASSES;
+    std::vector<uint32_t> spec;
+    if (ps_K) for (uint32_t ji : early) if (jobs[ji].prelock && jobs[ji].mode == FX_MODE_FLEXRX) spec.push_back(ji);
+    sl.ps_jobs = (uint32_t)spec.size(); sl.ps_hops = ps_K; sl.ps_words = (ps_K + FX_PRESCAN_CHUNK - 1) / FX_PRESCAN_CHUNK; sl.ps_taken = sl.ps_fallback = 0;
+    if (!spec.empty()) {
+        if (sl.d_prescan.reserve(spec.size() * sl.ps_words)) return FXRX_ERR_HIP;
+        for (size_t i = 0; i < spec.size(); i++) {
+            FxWalkJob &j = jobs[spec[i]];
+            j.prescan = sl.d_prescan.p + i * sl.ps_words; j.prescan_words = sl.ps_words;
+            j.prescan_hops = fx_prescan_valid_hops(j.start, j.stop, j.n, ps_K);
+        }
+    }
     if (sl.hp_desc.reserve(desc_bytes) || sl.d_desc.reserve(desc_bytes) || sl.d_wres.reserve(NJ + NS) || sl.d_frames.reserve(frame_slots) ||
         sl.d_runs.reserve(sl.run_cap) || sl.d_req.reserve(2 * NJ + 16) || sl.d_cstat.reserve(NS) || sl.d_chain.reserve(chain_slots) || sl.d_chain_count.reserve(NS) || sl.d_stream_base.reserve(NS + 1) ||
         sl.d_pjobs.reserve(chain_slots) || sl.h_recs.reserve(chain_slots) || sl.d_mf_job.reserve(sl.mf_cap) || sl.d_mf_c0.reserve(sl.mf_cap) ||
@@ -707,6 +742,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     uint32_t *hl = reinterpret_cast<uint32_t *>(sl.hp_desc.p + o_list);
     if (!early.empty()) std::memcpy(hl, early.data(), early.size() * sizeof(uint32_t));
     if (!late.empty()) std::memcpy(hl + early.size(), late.data(), late.size() * sizeof(uint32_t));
+    if (!spec.empty()) std::memcpy(hl + NJ, spec.data(), spec.size() * sizeof(uint32_t));
     std::memcpy(sl.hp_desc.p + o_streams, sds.data(), NS * sizeof(FxStreamDesc));
     const FxWalkJob *d_jobs = reinterpret_cast<const FxWalkJob *>(sl.d_desc.p);
     const uint32_t *d_list = reinterpret_cast<const uint32_t *>(sl.d_desc.p + o_list);
@@ -728,9 +764,12 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     HIP_OK(fx_launch_upload(st, sl.hp_desc.p, sl.d_desc.p, desc_bytes, (unsigned)c->n_cus));     // (descriptors: our own page-locked buffer)
     const int tl = c->timing_level >= 0 ? c->timing_level : (c->depth > 1 ? 0 : 2);      // stage events: see fxrx_set_timing
     sl.timing_level = tl;
+    // (the speculative jobs' pre-lock scan: part of the walk stage, in front of every walker launch that reads its table)
+    if (c->debug_walk_twice > 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, d_jobs, d_list + NJ, c->d_tables));
     for (int rep = 0; rep < c->debug_walk_twice; rep++)
         HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[0], st));
+    if (c->debug_walk_twice <= 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, d_jobs, d_list + NJ, c->d_tables));
     HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
     // the true walkers of continuing streams read the state the previous block's chain kernel leaves.  What the speculative
     // walkers skipped is verified before that wait -- it does not depend on the state --, so that the chain of dependencies
@@ -1183,6 +1222,7 @@ static int repair_and_replay(fxrx_ctx_s *c, Slot &sl)
             c->repairs_host++; c->inchain_left = 16;
             const FxBlockHdr &h0 = *sl.h_hdr.p;         // the walk-phase counters are zeroed with the first plan kernel: keep them
             sl.kept_hops += h0.hops; sl.kept_cheap += h0.hops_cheap; sl.kept_vhops += h0.verify_hops; sl.kept_vfail += h0.verify_failures;
+            sl.ps_taken += h0.ps_taken; sl.ps_fallback += h0.ps_fallback;
             if (!sl.force_noskip && c->cfg.mode != FXRX_MODE_DETECTOR && c->skip_seek && h0.verify_failures > std::max<uint32_t>(16u, (uint32_t)sl.NJ / 8u)) {
                 // Skipped hops on which the exact detector fires, all over the block (weak preambles, false alarms: low SNR; a
                 // few of them are mended segment by segment in the repair rounds below).  Walk the block
@@ -1367,6 +1407,27 @@ int fxrx_ready(fxrx_ctx *c)
 
 unsigned int fxrx_inflight(const fxrx_ctx *c) { return c ? c->inflight : 0; }
 
+// of the last collected block: speculative jobs whose first hops fx_prescan_kernel scanned | those that took their first
+// candidate from its table | those whose table held none (their own scan carried on behind the scanned hops)
+int fxrx_debug_prescan_stats(const fxrx_ctx *c, uint64_t out[3])
+{
+    if (!c || !c->last || !out) return FXRX_ERR_ARG;
+    out[0] = c->last->ps_jobs; out[1] = c->last->ps_taken; out[2] = c->last->ps_fallback;
+    return 0;
+}
+
+// tests, no device: what a speculative walker makes of `words` (fx_common.h: fx_prescan_valid_hops, fx_prescan_entry).  Returns 1
+// when a chunk word holds a hit; out[0] = where the walk goes on, out[1] = hops added to the cheap-hop counter, out[2] = hops scanned
+int fxrx_debug_prescan_words(const uint32_t *words, uint32_t n_words, uint32_t K, int64_t start, int64_t stop, int64_t n, int64_t out[3])
+{
+    if (!out || (n_words && !words)) return FXRX_ERR_ARG;
+    const uint32_t hops = fx_prescan_valid_hops(start, stop, n, K);
+    int64_t p = 0; uint32_t scanned = 0;
+    const bool took = fx_prescan_entry(words, n_words, hops, start, &p, &scanned);
+    out[0] = p; out[1] = scanned; out[2] = hops;
+    return took ? 1 : 0;
+}
+
 int fxrx_debug_gang_stats(const fxrx_ctx *c, uint64_t out[2])
 {
     if (!c || !out) return FXRX_ERR_ARG;
@@ -1491,6 +1552,8 @@ static int collect_block(fxrx_ctx_s *c)
         if (!S.fresh_start && S.total >= end_total)
             S.carry_bound = std::min<int64_t>(S.carry_bound, std::min<int64_t>(S.carry_cap, hs[s].carry_len + (S.total - end_total)));
     }
+    { uint64_t tot = 0; for (unsigned s = 0; s < NS; s++) tot += sl.n[s]; c->samples_hint = tot; }
+    sl.ps_taken += h.ps_taken; sl.ps_fallback += h.ps_fallback;
     c->frames_hint = h.n_frames; c->plain_hint = h.n_dec_plain; c->batch_hint = h.n_dec_batch; c->vb_items_hint = h.n_vb_items;
     if (sl.vb_early && h.n_dec_batch > vb_clean) c->trellis_left = kTrellisHold;     // frames that were not clean: the trellis kernels stay in the chain for a while
     c->fb_hint = h.n_vb_fallback; c->vbfix_hint = h.n_vb_fallback + vb_rep; c->mf_items_hint = h.n_mfblk; c->vb_want_hint = h.vb_want; c->vb_steps_hint = (uint64_t)h.vb_want * (h.vb_blk ? h.vb_blk : 1u); c->first_block = false;

@@ -9,6 +9,7 @@
 //                       (qdetector SEEK), ALIGN estimates (tau, gamma, dphi, phi), then -- flex_rx mode --
 //                       NCO mix + polyphase MF of the preamble/header span, pilot sync, header decode.
 //                       Emits one FxFrame per detection, the hand-off to the next segment, and the runs of hops it skipped.
+//   fx_prescan_kernel   (FXRX_PRESCAN=1) the speculative walkers' pre-lock coarse scan, ahead of them: a workgroup per 16 hops.
 //   fx_seekverify_kernel  the exact detector on every skipped hop (thousands of independent workgroups).
 //   fx_chainfast_kernel   stitches the segments' lists into the sequential machine's list; resume state, carried tail
 //                       (fx_chain_kernel: the full-size fallback that can walk by itself).
@@ -748,6 +749,44 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
 #ifndef FX_FLEX_OCC
 #define FX_FLEX_OCC 2        // same for the flex_rx instance
 #endif
+// One hop of the coarse scan, by one wave: the CFO-blind differential correlator d[i] = w[i+1] conj(w[i]) of the 512-sample
+// window w (LDS, published) against the zero-mean differential template T->TD, two transforms through the wave's exchange buffer
+// scr.  The energy of d is taken about its mean (oversampled signals give d a large DC term that is not information).  Returns
+// whether the largest peak at a lag below 512 - 156 passes the test, and that lag.  Shared by the walker's four-hop round and
+// fx_prescan_kernel, so that both take bit-identical decisions.
+__device__ __forceinline__ bool coarse_hop(const float2 *w, float2 *scr, const FxTables *T, int lane, const float2 (&twA)[7], const float2 (&twB)[7], uint32_t &lag)
+{
+    float2 a[8]; float e = 0.0f; float2 sm = make_float2(0.0f, 0.0f);
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int i = lane + 64 * q;
+        a[q] = (i < FX_NFFT - 1) ? cmulc(w[i + 1], w[i]) : make_float2(0.0f, 0.0f);
+        e += cm2(a[q]); sm = cadd(sm, a[q]);
+    }
+    e = wave_sum(e); sm.x = wave_sum(sm.x); sm.y = wave_sum(sm.y);
+    e -= cm2(sm) * (1.0f / (float)FX_NFFT);
+    fft512_wave(a, scr, lane, twA, twB);
+    const int kb = (lane >> 3) + 8 * (lane & 7);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < 8; t++) { float2 y = cmulc(a[t], T->TD[kb + 64 * t]); scr[kb + 64 * t] = make_float2(y.y, y.x); }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < 8; q++) a[q] = scr[lane + 64 * q];
+    __builtin_amdgcn_wave_barrier();
+    fft512_wave(a, scr, lane, twA, twB);
+    float bv = -1.0f; uint32_t bk = 0;
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const uint32_t k = (uint32_t)kb + 64 * t;
+        const float m = cm2(a[t]);
+        if (k < FX_NFFT - FX_S_LEN && m > bv) { bv = m; bk = k; }
+    }
+    wave_argmax(bv, bk);
+    lag = bk;
+    return e > 0.0f && bv > 0.06f * e * T->td2sum * (float)FX_NFFT * (float)FX_NFFT;
+}
+
 // One walk: the synchroniser's state machine from (start, floor, fresh) of `job` until the job's stop / hand-off / end of
 // data.  Called by the whole workgroup (fx_walk_kernel: once; fx_chain_kernel: for every repair).  L.S (template spectrum)
 // must be loaded; the result record and the frames go to global memory (thread 0), verification runs to `runs`.
@@ -821,6 +860,19 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
     const float s2sum = T->s2sum;
     const float2 *sc = T->sc;
 
+    // A speculative walker whose first hops fx_prescan_kernel has scanned already (same correlator, same grid, floor = start):
+    // the first chunk word with a hit is what the unlocked candidate branch below would have found -- the exact detector takes
+    // over on the hop whose new half starts at the candidate, behind a reset one hop earlier --; no hit, and the walker's own
+    // scan carries on behind the scanned hops.  Nothing found before the lock is ever spliced, so either way the result is exact.
+    if (MODE == FX_MODE_FLEXRX && !EXT && job.prelock && job.prescan && !job.state_in) {
+        int64_t p; uint32_t scanned;
+        const bool took = fx_prescan_entry(job.prescan, job.prescan_words, job.prescan_hops, job.start, &p, &scanned);
+        if (took) { pos = p; floor_ = p - FX_HOP; fresh = false; exact_left = 2; }
+        else if (scanned) { pos = p; fresh = false; }
+        hops_cheap += scanned;
+        if (tid == 0) atomicAdd(took ? &hdr->ps_taken : &hdr->ps_fallback, 1u);
+    }
+
     const bool lo = tid < HALF;            // threads that own one sample of a 256-sample half
     __syncthreads();
     if (fresh) { if (lo) L.win[tid] = make_float2(0.0f, 0.0f); }
@@ -866,35 +918,8 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
             __syncthreads();
             hops_cheap += WALK_WAVES;
             {
-                const float2 *w = L.cw + FX_HOP * wave;               // this wave's 512-sample window
-                float2 a[8]; float e = 0.0f; float2 sm = make_float2(0.0f, 0.0f);
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int i = lane + 64 * q;
-                    a[q] = (i < FX_NFFT - 1) ? cmulc(w[i + 1], w[i]) : make_float2(0.0f, 0.0f);
-                    e += cm2(a[q]); sm = cadd(sm, a[q]);
-                }
-                e = wave_sum(e); sm.x = wave_sum(sm.x); sm.y = wave_sum(sm.y);
-                e -= cm2(sm) * (1.0f / (float)FX_NFFT);
-                fft512_wave(a, L.scr[wave], lane, twA, twB);
-                const int kb = (lane >> 3) + 8 * (lane & 7);
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int t = 0; t < 8; t++) { float2 y = cmulc(a[t], T->TD[kb + 64 * t]); L.scr[wave][kb + 64 * t] = make_float2(y.y, y.x); }
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int q = 0; q < 8; q++) a[q] = L.scr[wave][lane + 64 * q];
-                __builtin_amdgcn_wave_barrier();
-                fft512_wave(a, L.scr[wave], lane, twA, twB);
-                float bv = -1.0f; uint32_t bk = 0;
-#pragma unroll
-                for (int t = 0; t < 8; t++) {
-                    const uint32_t k = (uint32_t)kb + 64 * t;
-                    const float m = cm2(a[t]);
-                    if (k < FX_NFFT - FX_S_LEN && m > bv) { bv = m; bk = k; }
-                }
-                wave_argmax(bv, bk);
-                const bool hit = e > 0.0f && bv > 0.06f * e * T->td2sum * (float)FX_NFFT * (float)FX_NFFT;
+                uint32_t bk;
+                const bool hit = coarse_hop(L.cw + FX_HOP * wave, L.scr[wave], T, lane, twA, twB, bk);   // this wave's 512-sample window
                 if (lane == 0) L.cand[wave] = hit ? bk : 0xFFFFFFFFu;
             }
             __syncthreads();
@@ -1443,6 +1468,68 @@ extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, int sh, unsigned njo
     else FX_WALK_FLEX(false);
 #undef FX_WALK_FLEX
 #undef FX_WALK_LAUNCH
+    return hipGetLastError();
+}
+
+// ===================================================================== pre-lock scan
+// What a speculative flex_rx walker does before its first candidate -- the coarse correlator over the hops start + 256 h, floor =
+// start, four hops a round -- depends on nothing but the samples, so it is taken off the walker's serial chain: one workgroup
+// per chunk of FX_PRESCAN_CHUNK hops of a job, all chunks of all jobs of the block at once.  A chunk stops at its first round
+// with a hit and writes its one word (fx_common.h) unconditionally: every word a walker reads was written by this launch.  Hops
+// at or beyond job.prescan_hops (new half beyond the segment end or the data) are not scanned.  No atomics, no waiting.
+#define PRESCAN_WAVES 4
+struct PrescanLds {
+    float2 cw[(PRESCAN_WAVES + 1) * FX_HOP + 8];   // overlap half + one new hop per wave
+    float2 scr[PRESCAN_WAVES][576];
+    uint32_t cand[PRESCAN_WAVES];
+};
+__global__ __launch_bounds__(64 * PRESCAN_WAVES)
+void fx_prescan_kernel(const FxWalkJob *jobs, const uint32_t *spec_list, uint32_t words_per_job, const FxTables *T)
+{
+    constexpr int THREADS = 64 * PRESCAN_WAVES;
+    __shared__ PrescanLds L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t ji = spec_list[blockIdx.x / words_per_job], chunk = blockIdx.x % words_per_job;
+    const FxWalkJob job = jobs[ji];
+    if (!job.prescan || chunk >= job.prescan_words) return;
+    float2 twA[7], twB[7];
+#pragma unroll
+    for (int r = 1; r < 8; r++) { twA[r - 1] = T->tw[lane * r]; twB[r - 1] = T->tw[8 * (lane & 7) * r]; }
+    const XSrc xs = make_xsrc(job.x, job.xa_end, job.n);
+    const int64_t floor_ = job.start;
+    const uint32_t nvalid = job.prescan_hops;
+    uint32_t word = FX_PRESCAN_NONE;
+    for (uint32_t r = 0; r < FX_PRESCAN_CHUNK / PRESCAN_WAVES; r++) {
+        const uint32_t h0 = chunk * FX_PRESCAN_CHUNK + r * PRESCAN_WAVES;
+        if (h0 >= nvalid) break;
+        const int64_t pos = job.start + (int64_t)FX_HOP * h0;
+        __syncthreads();
+        {   // (all of a thread's loads in flight at once, as in the walker's round; xv() reads zeros beyond the data)
+            constexpr int NLD = ((PRESCAN_WAVES + 1) * FX_HOP + THREADS - 1) / THREADS;
+            float2 ld[NLD];
+#pragma unroll
+            for (int k = 0; k < NLD; k++) { const int i = tid + THREADS * k; ld[k] = i < (PRESCAN_WAVES + 1) * FX_HOP ? xv(xs, pos - FX_HOP + i, floor_) : make_float2(0.0f, 0.0f); }
+#pragma unroll
+            for (int k = 0; k < NLD; k++) { const int i = tid + THREADS * k; if (i < (PRESCAN_WAVES + 1) * FX_HOP) L.cw[i] = ld[k]; }
+        }
+        __syncthreads();
+        {
+            uint32_t bk;
+            const bool hit = coarse_hop(L.cw + FX_HOP * wave, L.scr[wave], T, lane, twA, twB, bk);
+            if (lane == 0) L.cand[wave] = (hit && h0 + (uint32_t)wave < nvalid) ? bk : FX_PRESCAN_NONE;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int w = PRESCAN_WAVES - 1; w >= 0; w--) if (L.cand[w] != FX_PRESCAN_NONE) word = fx_prescan_pack(h0 + (uint32_t)w, L.cand[w]);
+        if (word != FX_PRESCAN_NONE) break;
+    }
+    if (tid == 0) job.prescan[chunk] = word;
+}
+
+extern "C" hipError_t fx_launch_prescan(hipStream_t st, unsigned n_spec, unsigned words_per_job, const FxWalkJob *jobs, const uint32_t *spec_list, const FxTables *T)
+{
+    if (n_spec == 0 || words_per_job == 0) return hipSuccess;
+    hipLaunchKernelGGL(fx_prescan_kernel, dim3(n_spec * words_per_job), dim3(64 * PRESCAN_WAVES), 0, st, jobs, spec_list, words_per_job, T);
     return hipGetLastError();
 }
 

@@ -11,6 +11,8 @@ struct FxTables;   // fx_device.h
 extern "C" hipError_t fx_launch_walk(unsigned mode, int eq, int sh, unsigned njobs, hipStream_t st, const FxWalkJob *jobs, const uint32_t *job_list, FxWalkResult *results,
                                      FxFrame *frames, FxVerifyRun *runs, uint32_t run_cap, FxBlockHdr *hdr, const FxTables *T, int ext, uint32_t n_jobs_total,
                                      const uint32_t *n_list, uint32_t list_cap);
+// (the pre-lock scan of the n_spec speculative jobs listed in spec_list: words_per_job chunks each, a workgroup per chunk)
+extern "C" hipError_t fx_launch_prescan(hipStream_t st, unsigned n_spec, unsigned words_per_job, const FxWalkJob *jobs, const uint32_t *spec_list, const FxTables *T);
 extern "C" hipError_t fx_launch_seekverify(unsigned grid, hipStream_t st, const FxVerifyRun *runs, uint32_t run_cap, const FxWalkJob *jobs, FxWalkResult *results,
                                            FxFrame *frames, FxBlockHdr *hdr, const FxTables *T, uint32_t phase);
 extern "C" hipError_t fx_launch_chain(unsigned mode, int eq, int sh, unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, uint32_t n_jobs_total,

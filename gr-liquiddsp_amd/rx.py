@@ -129,6 +129,14 @@ class RxContext:
         if self.L.fxrx_set_timing(self.h, int(level)) != 0:
             raise RxError("fxrx_set_timing: bad level")
 
+    def prescan_stats(self):
+        """Of the last collected block: (speculative segments pre-scanned, those that took a candidate from the table, those that
+        fell back to their own scan): see fxrx_debug_prescan_stats."""
+        out = (C.c_uint64 * 3)()
+        if self.L.fxrx_debug_prescan_stats(self.h, C.byref(out)) != 0:
+            raise RxError("fxrx_debug_prescan_stats failed")
+        return int(out[0]), int(out[1]), int(out[2])
+
     def gang_stats(self):
         """(tail launches so far that served more than one block in flight, blocks they carried): see fxrx_debug_gang_stats."""
         out = (C.c_uint64 * 2)()

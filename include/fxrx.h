@@ -303,6 +303,15 @@ int fxrx_debug_fail(fxrx_ctx *c, unsigned int submits, unsigned int collects);
 /* tests: out[0] = tail launches so far that served more than one block in flight (the payload PLL and the decode front of up to four
  * blocks in one launch each: FXRX_TAIL_GANG, 1 = off; only with fxrx_set_depth >= 4), out[1] = the blocks they carried */
 int fxrx_debug_gang_stats(const fxrx_ctx *c, uint64_t out[2]);
+/* tests: of the last collected block -- out[0] = speculative segments whose first hops the pre-lock scan (fx_prescan_kernel) took
+ * off their walkers (FXRX_PRESCAN=1; off by default; FXRX_PRESCAN_HOPS = hops scanned per segment, 0 = none), out[1] = those whose walker took its
+ * first candidate preamble from the scan's table, out[2] = those whose table held none: their own scan carried on behind it */
+int fxrx_debug_prescan_stats(const fxrx_ctx *c, uint64_t out[3]);
+/* tests, no device needed: the walker's reading of a pre-lock scan table.  words: n_words chunk words (16 hops each; hop << 16 | lag of
+ * the chunk's lowest hitting hop, or 0xFFFFFFFF); K: hops asked for; start / stop / n: the segment and the data.  Returns 1 when a word
+ * holds a hit, 0 when none does; out[0] = position the walk goes on from, out[1] = hops added to the cheap-hop counter, out[2] = hops the
+ * scan covers (new half inside the segment and the data, at most K) */
+int fxrx_debug_prescan_words(const uint32_t *words, uint32_t n_words, uint32_t K, int64_t start, int64_t stop, int64_t n, int64_t out[3]);
 /* tests: blocks in flight whose tails are deferred at this moment (the open gang's members; 0 .. 3) */
 int fxrx_debug_gang_open(const fxrx_ctx *c);
 /* tests: run the walker's header decoder on the GPU over n headers given in host memory.  soft != 0: `in` holds 432 soft values per
