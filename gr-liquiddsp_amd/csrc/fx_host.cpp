@@ -137,10 +137,18 @@ struct StreamSnap { int64_t tot0 = 0; bool fresh_start = true; int64_t carry_bou
 
 struct Out { fxrx_frame f; };
 
+// Slot::ev, the stage events of a block.  Start (in front of the walkers), Walk, Verify, Plan and Dec are recorded at timing level 2 only, Pll from level 1 on
+// (fxrx_set_timing: the stage times are their differences); the others always.  Chain, behind the chain kernel: the next block's chain kernel waits for it
+// (prev_chain).  Mf, behind the payload matched filter (detector mode: the window kernel), the last reader of the carried tail: the chain kernel of the next block
+// but one waits for it (carry_reader), and so does the gang that holds the block's tail.  Done: the block's last event, which fxrx_collect waits for (not recorded
+// while the tail is deferred).  Handover, behind the speculative walkers of a block with continuing streams: the context's high-priority chain stream waits for it.
+enum StageEv { kEvStart = 0, kEvWalk, kEvVerify, kEvChain, kEvPlan, kEvMf, kEvPll, kEvDec, kEvDone, kEvHandover, kEvCount };
+enum DecList { kDecPlain = 0, kDecRs, kDecBatch, kDecFallback, kDecLists };     // the four quarters of Slot::d_dec_list, list_cap() entries each
+
 // One block in flight: descriptors, device tables, arenas, result buffers and its own HIP stream.
 struct Slot {
     hipStream_t st = nullptr;
-    hipEvent_t ev[10] = {};                  // 0 start | 1 walk | 2 verify | 3 chain | 4 plan | 5 mf | 6 pll | 7 dec | 8 done
+    hipEvent_t ev[kEvCount] = {};            // indexed by StageEv
     unsigned index = 0;
     bool busy = false;
     uint64_t seq = 0;                        // block number since context creation
@@ -191,11 +199,22 @@ struct Slot {
     int timing_level = 0;                    // which stage events this block recorded (fxrx_set_timing)
     bool inchain = false;                    // the repair round within the chain was enqueued with it
     uint32_t kept_hops = 0, kept_cheap = 0, kept_vhops = 0, kept_vfail = 0, kept_repairs = 0;   // walk-phase counters of a block whose back part was run again
-    // the block's tail -- everything behind the payload matched filter: PLL, decode launches, symbol copy, ev[6..8] --, whose grids are
+    // the block's tail -- everything behind the payload matched filter: PLL, decode launches, symbol copy, ev[kEvPll .. kEvDone] --, whose grids are
     // fixed when the block is submitted; the launches themselves may wait in the context's open gang (launch_tails)
     unsigned tail_pll_waves = 0, tail_mf_grid = 0; int tail_vb_packed = 0, tail_with_fix = 0;
-    bool tail_launched = true;               // false: deferred -- ev[8] has not been recorded for this block, nobody may wait for it
+    bool tail_launched = true;               // false: deferred -- ev[kEvDone] has not been recorded for this block, nobody may wait for it
     hipStream_t tail_st = nullptr;           // the stream the tail went to (a gang's: its last member's)
+    // views of the arenas: nothing is allocated or kept (jobs_rw: the chain kernel rewrites the jobs of the segments it queues for repair)
+    uint32_t list_cap() const { return chain_cap + 64 * FX_PLL_CLASSES; }      // entries of d_pll_list and of each quarter of d_dec_list
+    uint32_t *dec_list(DecList which) const { return d_dec_list.p + (size_t)which * list_cap(); }
+    FxBlockHdr *hdr_walk() const { return d_hdr.p; } FxBlockHdr *hdr_pay() const { return d_hdr.p + 1; }
+    const FxWalkJob *jobs() const { return reinterpret_cast<const FxWalkJob *>(d_desc.p); } FxWalkJob *jobs_rw() const { return reinterpret_cast<FxWalkJob *>(d_desc.p); }
+    const uint32_t *job_list() const { return reinterpret_cast<const uint32_t *>(d_desc.p + o_list); } const FxStreamDesc *streams() const { return reinterpret_cast<const FxStreamDesc *>(d_desc.p + o_streams); }
+#ifdef FX_STAMPS
+    FxPayResult *pres() const { return d_pres.p; }      // decode-phase clocks per frame: diagnostic builds only
+#else
+    FxPayResult *pres() const { return nullptr; }
+#endif
 };
 
 struct fxrx_ctx_s {
@@ -551,6 +570,63 @@ const void *fxrx_device_framesyms(const fxrx_ctx *c, uint64_t *n)
     return c->last->n_syms ? c->last->d_symraw.p : nullptr;
 }
 
+// ---- launch helpers: a kernel launched from more than one place has its arguments named here, once; a helper takes what differs between its call sites
+// walker.  kWalkList: the njobs entries of `list`; kWalkRequests: `list` holds njobs repair requests (repair_rounds); kWalkRequestsInChain:
+// repair requests whose number is read on the device, njobs workgroups stride over them (the repair round within the chain)
+enum WalkForm { kWalkList, kWalkRequests, kWalkRequestsInChain };
+static inline hipError_t launch_walk(const fxrx_ctx_s *c, const Slot &sl, hipStream_t st, const uint32_t *list, unsigned njobs, WalkForm form = kWalkList)
+{
+    return fx_launch_walk(c->cfg.mode == FXRX_MODE_DETECTOR ? FX_MODE_DETECT : FX_MODE_FLEXRX, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, njobs, st, sl.jobs(), list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p,
+                          sl.run_cap, sl.hdr_walk(), c->d_tables, form == kWalkList ? 0 : 1, (uint32_t)sl.NJ, form == kWalkRequestsInChain ? &sl.hdr_walk()->n_repair_req : nullptr, form == kWalkRequestsInChain ? (uint32_t)(2 * sl.NJ + 16) : 0u);
+}
+static inline hipError_t launch_seekverify(const fxrx_ctx_s *c, const Slot &sl, hipStream_t st, unsigned grid, uint32_t phase)
+{
+    return fx_launch_seekverify(grid, st, sl.d_runs.p, sl.run_cap, sl.jobs(), sl.d_wres.p, sl.d_frames.p, sl.hdr_walk(), c->d_tables, phase);
+}
+// lean chain kernel.  kStitch: stitch, nothing else (FXRX_CHAIN_SLOW: flag everything for repair); kStitchQueue: and rewrite and list in d_req the segments to walk again
+// (repair_rounds); kStitchPass1 / 2: the repair round within the chain -- pass 1 queues likewise and notes every stream's state in d_cstat, pass 2, behind the walk, stitches again
+enum ChainForm { kStitch, kStitchQueue, kStitchPass1, kStitchPass2 };
+static inline hipError_t launch_chainfast(const fxrx_ctx_s *c, const Slot &sl, hipStream_t st, ChainForm form)
+{
+    const bool queue = form == kStitchQueue || form == kStitchPass1;
+    return fx_launch_chainfast(c->cfg.n_streams, st, sl.streams(), sl.jobs(), sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, sl.hdr_walk(), form == kStitch && c->chain_slow ? 1u : 0u,
+                               queue ? sl.jobs_rw() : nullptr, queue ? sl.d_req.p : nullptr, form >= kStitchPass1 ? sl.d_cstat.p : nullptr, form == kStitchPass1 ? 1u : form == kStitchPass2 ? 2u : 0u);
+}
+// wave-per-frame decoder over the frames [first_wave, first_wave + n_waves) of one list (no waves: no launch).  The Reed-Solomon list takes the
+// Reed-Solomon instance; the fallback list holds frames of the batch path -- hard decisions -- and its launch reports to the host's header
+static inline int soft_level(const fxrx_config &cfg) { return cfg.soft_decision ? (cfg.soft_block ? (cfg.soft_chain ? 3 : 2) : 1) : 0; }
+static inline hipError_t launch_paydec(const fxrx_ctx_s *c, const Slot &sl, hipStream_t st, DecList which, unsigned first_wave, unsigned n_waves, unsigned waves_per_wg)
+{
+    return fx_launch_paydec(which == kDecRs ? 1 : 0, which == kDecFallback ? 0 : soft_level(c->cfg), first_wave, n_waves, waves_per_wg, st, sl.d_pjobs.p, sl.dec_list(which), sl.hdr_pay(), sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
+                            sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, sl.pres(), c->d_tables, which == kDecFallback ? sl.h_hdr.p : nullptr);
+}
+// decode, one wave per frame: the lean instance, then the Reed-Solomon instance (which strides)
+static inline hipError_t launch_decoders(const fxrx_ctx_s *c, const Slot &sl, hipStream_t st, unsigned first_plain, unsigned n_plain, unsigned n_rs)
+{
+    const hipError_t e = launch_paydec(c, sl, st, kDecPlain, first_plain, n_plain, c->dec_waves);
+    return e != hipSuccess ? e : launch_paydec(c, sl, st, kDecRs, 0u, n_rs, 1u);
+}
+// batch Viterbi path: the trellis kernels over the first n_items work items, the back part for the first n_fin frames, fb_waves of the fallback decoder for what it hands back
+static inline hipError_t launch_trellis(const fxrx_ctx_s *c, const Slot &sl, hipStream_t st, unsigned n_items, int packed, int with_fix, unsigned n_fin, unsigned fb_waves)
+{
+    hipError_t e = fx_launch_vbitems(0, n_items, st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, sl.hdr_pay(), sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, c->vb_debug, packed, with_fix);
+    if (e == hipSuccess) e = fx_launch_vbfinish(0, n_fin, st, sl.d_pjobs.p, sl.dec_list(kDecBatch), sl.hdr_pay(), sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, sl.dec_list(kDecFallback),
+                                                sl.list_cap(), sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0);
+    return e != hipSuccess ? e : launch_paydec(c, sl, st, kDecFallback, 0u, fb_waves, 1u);
+}
+// detector windows of the records [first, last), on the block's stream; late: at collect (windows that start in the carried tail are not written again)
+static inline hipError_t launch_detwin(const fxrx_ctx_s *c, const Slot &sl, uint32_t first, uint32_t last, bool late)
+{
+    return fx_launch_detwin(sl.st, std::min<unsigned>(std::max<unsigned>(last - first, 1u), 4u * (unsigned)c->n_cus), sl.streams(), c->cfg.n_streams, sl.d_stream_base.p, sl.d_pjobs.p, sl.hdr_pay(), first, last,
+                            sl.h_win.p, sl.h_wintail.p, sl.h_winflag.p, late ? 0 : 1, late ? 1 : 0);
+}
+// streams in which a skipped hop fired (req: the block's repair requests, copied from d_req): their next blocks are walked with the exact detector on every hop
+static void mark_noskip(fxrx_ctx_s *c, const Slot &sl, const std::vector<uint32_t> &req)
+{
+    const FxWalkJob *hj = reinterpret_cast<const FxWalkJob *>(sl.hp_desc.p);
+    for (uint32_t r : req) if ((r & 0x80000000u) && (r & 0x7fffffffu) < sl.NJ) c->st[hj[r & 0x7fffffffu].stream].noskip_left = 32;
+}
+
 enum { kChainFast = 0, kChainFull = 1, kChainDone = 2 };
 static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t chain_st = nullptr, bool may_defer = false);
 
@@ -701,7 +777,6 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     // (the job lists: early | late, NJ entries together, and behind them the speculative jobs the pre-lock scan takes)
     const size_t o_list = up16(NJ * sizeof(FxWalkJob)), o_streams = o_list + up16(2 * NJ * sizeof(uint32_t)), desc_bytes = o_streams + up16(NS * sizeof(FxStreamDesc));
     sl.o_list = o_list; sl.o_streams = o_streams;
-    const uint32_t list_cap = chain_slots + 64 * FX_PLL_CLASSES;
     std::vector<uint32_t> spec;
     if (ps_K) for (uint32_t ji : early) if (jobs[ji].prelock && jobs[ji].mode == FX_MODE_FLEXRX) spec.push_back(ji);
     sl.ps_jobs = (uint32_t)spec.size(); sl.ps_hops = ps_K; sl.ps_words = (ps_K + FX_PRESCAN_CHUNK - 1) / FX_PRESCAN_CHUNK; sl.ps_taken = sl.ps_fallback = 0;
@@ -716,7 +791,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     if (sl.hp_desc.reserve(desc_bytes) || sl.d_desc.reserve(desc_bytes) || sl.d_wres.reserve(NJ + NS) || sl.d_frames.reserve(frame_slots) ||
         sl.d_runs.reserve(sl.run_cap) || sl.d_req.reserve(2 * NJ + 16) || sl.d_cstat.reserve(NS) || sl.d_chain.reserve(chain_slots) || sl.d_chain_count.reserve(NS) || sl.d_stream_base.reserve(NS + 1) ||
         sl.d_pjobs.reserve(chain_slots) || sl.h_recs.reserve(chain_slots) || sl.d_mf_job.reserve(sl.mf_cap) || sl.d_mf_c0.reserve(sl.mf_cap) ||
-        sl.d_pll_list.reserve(list_cap) || sl.d_dec_list.reserve(4 * (size_t)list_cap)) return FXRX_ERR_HIP;
+        sl.d_pll_list.reserve(sl.list_cap()) || sl.d_dec_list.reserve(kDecLists * (size_t)sl.list_cap())) return FXRX_ERR_HIP;
     if (!detect && (sl.d_symraw.reserve(sl.sym_cap) || sl.d_hard.reserve(sl.sym_cap + 64) ||
                     sl.d_bufA.reserve(sl.byte_cap + 256) || sl.d_bufB.reserve(sl.byte_cap + 256) || sl.d_dw.reserve(sl.dw_cap) || sl.h_out.reserve(sl.out_cap))) return FXRX_ERR_HIP;
     if (!detect && c->cfg.want_framesyms && sl.h_framesyms.reserve(sl.sym_cap)) return FXRX_ERR_HIP;
@@ -744,9 +819,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     if (!late.empty()) std::memcpy(hl + early.size(), late.data(), late.size() * sizeof(uint32_t));
     if (!spec.empty()) std::memcpy(hl + NJ, spec.data(), spec.size() * sizeof(uint32_t));
     std::memcpy(sl.hp_desc.p + o_streams, sds.data(), NS * sizeof(FxStreamDesc));
-    const FxWalkJob *d_jobs = reinterpret_cast<const FxWalkJob *>(sl.d_desc.p);
-    const uint32_t *d_list = reinterpret_cast<const uint32_t *>(sl.d_desc.p + o_list);
-    const unsigned mode = detect ? FX_MODE_DETECT : FX_MODE_FLEXRX;
+    const uint32_t *d_list = sl.job_list();
 
     const double tp2 = g_prof_on ? prof_now() : 0.0;
     // ---- 3. the chain, front part: walkers and seek verification ----
@@ -765,12 +838,11 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     const int tl = c->timing_level >= 0 ? c->timing_level : (c->depth > 1 ? 0 : 2);      // stage events: see fxrx_set_timing
     sl.timing_level = tl;
     // (the speculative jobs' pre-lock scan: part of the walk stage, in front of every walker launch that reads its table)
-    if (c->debug_walk_twice > 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, d_jobs, d_list + NJ, c->d_tables));
-    for (int rep = 0; rep < c->debug_walk_twice; rep++)
-        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
-    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[0], st));
-    if (c->debug_walk_twice <= 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, d_jobs, d_list + NJ, c->d_tables));
-    HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)early.size(), st, d_jobs, d_list, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
+    if (c->debug_walk_twice > 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, sl.jobs(), d_list + NJ, c->d_tables));
+    for (int rep = 0; rep < c->debug_walk_twice; rep++) HIP_OK(launch_walk(c, sl, st, d_list, (unsigned)early.size()));
+    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvStart], st));
+    if (c->debug_walk_twice <= 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, sl.jobs(), d_list + NJ, c->d_tables));
+    HIP_OK(launch_walk(c, sl, st, d_list, (unsigned)early.size()));
     // the true walkers of continuing streams read the state the previous block's chain kernel leaves.  What the speculative
     // walkers skipped is verified before that wait -- it does not depend on the state --, so that the chain of dependencies
     // from one block's chain kernel to the next one's is just: true walkers, their few verification runs, chain kernel
@@ -778,8 +850,8 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     hipStream_t cst = st;                                     // the stream the rest of the front part and the chain kernel go to
     if (!late.empty()) {
         if (verify) {
-            HIP_OK(fx_launch_copy_u32(st, &sl.d_hdr.p->n_runs, &sl.d_hdr.p->runs_done));
-            HIP_OK(fx_launch_seekverify(c->verify_per_cu * (unsigned)c->n_cus, st, sl.d_runs.p, sl.run_cap, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_hdr.p, c->d_tables, 0u));
+            HIP_OK(fx_launch_copy_u32(st, &sl.hdr_walk()->n_runs, &sl.hdr_walk()->runs_done));
+            HIP_OK(launch_seekverify(c, sl, st, c->verify_per_cu * (unsigned)c->n_cus, 0u));
         }
         // (from here to the chain kernel the block is on the chain of dependencies that runs through all blocks of a continuing
         // stream: a single workgroup or two that must not queue behind the chip-filling kernels of the other blocks in flight
@@ -789,17 +861,16 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
             HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));
             HIP_OK(hipStreamCreateWithPriority(&c->st_chain, hipStreamNonBlocking, hi));
         }
-        HIP_OK(hipEventRecord(sl.ev[9], st));
+        HIP_OK(hipEventRecord(sl.ev[kEvHandover], st));
         cst = c->st_chain;
-        HIP_OK(hipStreamWaitEvent(cst, sl.ev[9], 0));
+        HIP_OK(hipStreamWaitEvent(cst, sl.ev[kEvHandover], 0));
         if (c->prev_chain) HIP_OK(hipStreamWaitEvent(cst, c->prev_chain, 0));
-        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)late.size(), cst, d_jobs, d_list + early.size(), sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, sl.d_hdr.p, c->d_tables, 0, (uint32_t)NJ, nullptr, 0u));
+        HIP_OK(launch_walk(c, sl, cst, d_list + early.size(), (unsigned)late.size()));
     }
-    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[1], cst));
+    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvWalk], cst));
     if (verify)
-        HIP_OK(fx_launch_seekverify(late.empty() ? c->verify_per_cu * (unsigned)c->n_cus : (unsigned)std::min<size_t>((size_t)c->verify_per_cu * (size_t)c->n_cus, std::max<size_t>(64, 16 * late.size())), cst, sl.d_runs.p,
-                                    sl.run_cap, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_hdr.p, c->d_tables, 1u));
-    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[2], cst));
+        HIP_OK(launch_seekverify(c, sl, cst, late.empty() ? c->verify_per_cu * (unsigned)c->n_cus : (unsigned)std::min<size_t>((size_t)c->verify_per_cu * (size_t)c->n_cus, std::max<size_t>(64, 16 * late.size())), 1u));
+    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvVerify], cst));
     // chain kernels run in block order in any case (they write the carry buffers in rotation); this one writes
     // carry[(b + 1) % 3], which the payload MF of block b - 2 may still be reading
     if (late.empty() && c->prev_chain) HIP_OK(hipStreamWaitEvent(cst, c->prev_chain, 0));
@@ -812,54 +883,36 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
 
 static FxVbpreMember vbpre_member(Slot &sl, uint32_t first_wave, uint32_t n_waves)
 {
-    const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
-    return FxVbpreMember{ sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, sl.d_hdr.p + 1, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p,
-                          first_wave, n_waves };
+    return FxVbpreMember{ sl.d_pjobs.p, sl.dec_list(kDecBatch), sl.hdr_pay(), sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, first_wave, n_waves };
 }
 // ---- the tails of n blocks (n <= FX_GANG_MAX; n = 1: a block's own tail, on its own stream), on the last one's stream: one PLL
 // launch for all, each block's own decode launches where it has any, one fx_vbpre_kernel launch for all, each block's trellis
-// kernels / fallback decoder / symbol copy, and every block's ev[8] ----
+// kernels / fallback decoder / symbol copy, and every block's ev[kEvDone] ----
 static int launch_tails(fxrx_ctx_s *c, Slot *const *m, unsigned n)
 {
     hipStream_t st = m[n - 1]->st;
-    for (unsigned i = 0; i + 1 < n; i++) HIP_OK(hipStreamWaitEvent(st, m[i]->ev[5], 0));      // (the other members' matched filters)
-    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? (c->cfg.soft_chain ? 3 : 2) : 1) : 0;     // (fx_launch_paydec)
+    for (unsigned i = 0; i + 1 < n; i++) HIP_OK(hipStreamWaitEvent(st, m[i]->ev[kEvMf], 0));      // (the other members' matched filters)
     auto done = [&]() -> int {
-        for (unsigned i = 0; i < n; i++) { HIP_OK(hipEventRecord(m[i]->ev[8], st)); m[i]->tail_launched = true; m[i]->tail_st = st; }
+        for (unsigned i = 0; i < n; i++) { HIP_OK(hipEventRecord(m[i]->ev[kEvDone], st)); m[i]->tail_launched = true; m[i]->tail_st = st; }
         if (n > 1) { c->gang_launches++; c->gang_members += n; }
         return 0;
     };
     {
-        FxPllGang g; unsigned waves[FX_GANG_MAX];
-        g.n = n;
-        for (unsigned i = 0; i < n; i++) {
-            Slot &sl = *m[i];
-            g.m[i] = FxPllMember{ sl.d_pjobs.p, sl.d_pll_list.p, sl.d_hdr.p + 1, sl.d_symraw.p, sl.d_symraw.p, sl.d_hard.p, sl.h_recs.p };
-            waves[i] = sl.tail_pll_waves;
-        }
+        FxPllGang g; unsigned waves[FX_GANG_MAX]; g.n = n;
+        for (unsigned i = 0; i < n; i++) { const Slot &sl = *m[i]; g.m[i] = FxPllMember{ sl.d_pjobs.p, sl.d_pll_list.p, sl.hdr_pay(), sl.d_symraw.p, sl.d_symraw.p, sl.d_hard.p, sl.h_recs.p }; waves[i] = sl.tail_pll_waves; }
         HIP_OK(fx_launch_paypll(&g, waves, c->pll_waves, st, c->d_tables));
     }
-    for (unsigned i = 0; i < n; i++) if (m[i]->timing_level >= 1) HIP_OK(hipEventRecord(m[i]->ev[6], st));
+    for (unsigned i = 0; i < n; i++) if (m[i]->timing_level >= 1) HIP_OK(hipEventRecord(m[i]->ev[kEvPll], st));
     if (c->debug_stop_after == 6) return done();
     for (unsigned i = 0; i < n; i++) {
         Slot &sl = *m[i];
-        const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
-        FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
-        FxPayResult *pres = nullptr;
-#ifdef FX_STAMPS
-        pres = sl.d_pres.p;
-#endif
-        if (soft) {
+        if (c->cfg.soft_decision) {
             // per-bit soft values from the carrier-recovered symbols (data parallel, off the PLL's recurrence); the decoder
             // de-interleaves them in place, so a caller that wants to see them gets a copy first
-            HIP_OK(fx_launch_softdemod(sl.tail_mf_grid, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, hdr_pay, sl.d_symraw.p, sl.d_hard.p, sl.d_soft.p, c->d_tables));
+            HIP_OK(fx_launch_softdemod(sl.tail_mf_grid, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.hdr_pay(), sl.d_symraw.p, sl.d_hard.p, sl.d_soft.p, c->d_tables));
             if (c->cfg.want_framesyms) HIP_OK(hipMemcpyAsync(sl.h_soft.p, sl.d_soft.p, 8 * sl.byte_cap, hipMemcpyDeviceToHost, st));
         }
-        // decode, one wave per frame: the lean instance, then the Reed-Solomon instance (which strides)
-        HIP_OK(fx_launch_paydec(0, soft, 0, sl.dec_launched, c->dec_waves, st, sl.d_pjobs.p, sl.d_dec_list.p, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.d_soft.p,
-                                sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
-        HIP_OK(fx_launch_paydec(1, soft, 0, sl.rs_launched, 1u, st, sl.d_pjobs.p, sl.d_dec_list.p + list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p,
-                                sl.d_bufB.p, sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
+        HIP_OK(launch_decoders(c, sl, st, 0u, sl.dec_launched, sl.rs_launched));
     }
     {
         FxVbpreGang g; g.n = n;
@@ -868,32 +921,18 @@ static int launch_tails(fxrx_ctx_s *c, Slot *const *m, unsigned n)
     }
     for (unsigned i = 0; i < n; i++) {
         Slot &sl = *m[i];
-        const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
-        FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
-        FxPayResult *pres = nullptr;
-#ifdef FX_STAMPS
-        pres = sl.d_pres.p;
-#endif
-        if (sl.vb_blk) {
-            HIP_OK(fx_launch_vbitems(0, sl.vb_items_launched, st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p,
-                                     sl.d_vb_st.p, c->vb_debug, sl.tail_vb_packed, sl.tail_with_fix));
-            HIP_OK(fx_launch_vbfinish(0, sl.vb_fin_launched, st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
-                                      sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0));
-            HIP_OK(fx_launch_paydec(0, 0, 0, sl.fb_launched, 1u, st, sl.d_pjobs.p, sl.d_dec_list.p + 3 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
-                                    sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, sl.h_hdr.p));
-        }
-        if (sl.timing_level >= 2) HIP_OK(hipEventRecord(sl.ev[7], st));
+        if (sl.vb_blk) HIP_OK(launch_trellis(c, sl, st, sl.vb_items_launched, sl.tail_vb_packed, sl.tail_with_fix, sl.vb_fin_launched, sl.fb_launched));
+        if (sl.timing_level >= 2) HIP_OK(hipEventRecord(sl.ev[kEvDec], st));
         // (a copy kernel: it knows how many symbols the block really holds)
-        if (c->cfg.want_framesyms)
-            HIP_OK(fx_launch_symcopy(2u * (unsigned)c->n_cus, st, hdr_pay, sl.d_symraw.p, sl.h_framesyms.p));
+        if (c->cfg.want_framesyms) HIP_OK(fx_launch_symcopy(2u * (unsigned)c->n_cus, st, sl.hdr_pay(), sl.d_symraw.p, sl.h_framesyms.p));
     }
     return done();
 }
 
 // launch what the open gang holds (nothing: no-op).  Called when the gang is full, and before anything that waits for a member's
-// ev[8], moves what the members read, or changes what a submit means.
+// ev[kEvDone], moves what the members read, or changes what a submit means.
 // If a launch fails part-way the gang is empty all the same and its members stay without a tail (tail_launched false: nobody
-// waits on their ev[8]).  The HIP error goes up to the caller; fxrx_collect, when it reaches such a member, reports a block
+// waits on their ev[kEvDone]).  The HIP error goes up to the caller; fxrx_collect, when it reaches such a member, reports a block
 // without a tail and drops everything in flight (discard_inflight).  Not mended further: a HIP error at launch is fatal to
 // the context, every later call fails the same way.
 static int close_gang(fxrx_ctx_s *c)
@@ -910,49 +949,38 @@ static int close_gang(fxrx_ctx_s *c)
 // (fxrx_collect runs it for a block whose lean chain kernel reported FX_BLK_NEEDS_REPAIR) ----
 static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t chain_st, bool may_defer)
 {
-    const unsigned NS = c->cfg.n_streams;
-    const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR;
-    const unsigned mode = detect ? FX_MODE_DETECT : FX_MODE_FLEXRX;
-    const uint64_t b = sl.seq;
-    hipStream_t st = sl.st;
-    const FxWalkJob *d_jobs = reinterpret_cast<const FxWalkJob *>(sl.d_desc.p);
-    const FxStreamDesc *d_streams = reinterpret_cast<const FxStreamDesc *>(sl.d_desc.p + sl.o_streams);
-    const uint32_t chain_slots = sl.chain_cap, list_cap = chain_slots + 64 * FX_PLL_CLASSES;
-    FxBlockHdr *hdr = sl.d_hdr.p, *hdr_pay = sl.d_hdr.p + 1;
+    const unsigned NS = c->cfg.n_streams; const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR;
+    const uint64_t b = sl.seq; const uint32_t chain_slots = sl.chain_cap; hipStream_t st = sl.st;
     sl.tail_launched = true; sl.tail_st = st;
     if (chain_mode == kChainFull)
-        HIP_OK(fx_launch_chain(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, NS, st, d_streams, d_jobs, (uint32_t)sl.NJ, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, sl.d_runs.p, sl.run_cap,
-                               hdr, c->chain_slow ? 1u : 0u, c->d_tables));
+        HIP_OK(fx_launch_chain(detect ? FX_MODE_DETECT : FX_MODE_FLEXRX, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, NS, st, sl.streams(), sl.jobs(), (uint32_t)sl.NJ, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p,
+                               sl.d_chain_count.p, sl.d_runs.p, sl.run_cap, sl.hdr_walk(), c->chain_slow ? 1u : 0u, c->d_tables));
     else if (chain_mode == kChainFast) {
         // stitch; one repair round within the chain for what only takes a walk from a hand-off state (a hand-off target missing
         // from the next list, a skipped hop on which the exact detector fires): its walkers read the number of queued segments
         // on the device -- normally none: two launches that leave at once --; stitch the streams concerned again.  Whatever
         // is still open after that is flagged and mended when the block is collected (repair_and_replay).
         hipStream_t cs = chain_st ? chain_st : st;
-        FxWalkJob *d_jobs_rw = reinterpret_cast<FxWalkJob *>(sl.d_desc.p);
-        const uint32_t req_cap = (uint32_t)(2 * sl.NJ + 16);
         sl.inchain = !c->chain_slow && (c->inchain_repair == 2 || (c->inchain_repair == 1 && c->inchain_left > 0));
         if (c->inchain_left) c->inchain_left--;
-        if (!sl.inchain)
-            HIP_OK(fx_launch_chainfast(NS, cs, d_streams, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, hdr, c->chain_slow ? 1u : 0u, nullptr, nullptr, nullptr, 0u));
+        if (!sl.inchain) HIP_OK(launch_chainfast(c, sl, cs, kStitch));
         else {
-            HIP_OK(fx_launch_chainfast(NS, cs, d_streams, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, hdr, 0u, d_jobs_rw, sl.d_req.p, sl.d_cstat.p, 1u));
-            HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, (unsigned)std::min<size_t>(2 * sl.NJ, 64), cs, d_jobs, sl.d_req.p, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, hdr,
-                                  c->d_tables, 1, (uint32_t)sl.NJ, &hdr->n_repair_req, req_cap));
-            HIP_OK(fx_launch_chainfast(NS, cs, d_streams, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, hdr, 0u, nullptr, nullptr, sl.d_cstat.p, 2u));
+            HIP_OK(launch_chainfast(c, sl, cs, kStitchPass1));
+            HIP_OK(launch_walk(c, sl, cs, sl.d_req.p, (unsigned)std::min<size_t>(2 * sl.NJ, 64), kWalkRequestsInChain));
+            HIP_OK(launch_chainfast(c, sl, cs, kStitchPass2));
         }
     }
     // (kChainDone: the repair rounds have stitched the block already)
-    HIP_OK(hipEventRecord(sl.ev[3], chain_mode == kChainFast && chain_st ? chain_st : st));
-    if (chain_mode == kChainFast && chain_st && chain_st != st) HIP_OK(hipStreamWaitEvent(st, sl.ev[3], 0));   // back onto the block's own stream
-    c->prev_chain = sl.ev[3];
+    HIP_OK(hipEventRecord(sl.ev[kEvChain], chain_mode == kChainFast && chain_st ? chain_st : st));
+    if (chain_mode == kChainFast && chain_st && chain_st != st) HIP_OK(hipStreamWaitEvent(st, sl.ev[kEvChain], 0));   // back onto the block's own stream
+    c->prev_chain = sl.ev[kEvChain];
     // (the plan kernels' workgroups take contiguous ranges of the chain's frames: about 2048 each, from the last block's count)
-    HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->frames_hint / 2048 + 1), d_streams, NS, detect ? 1u : 0u, c->cfg.equalizer ? 1u : 0u, sl.vb_blk, sl.d_chain.p,
-                          sl.d_chain_count.p, sl.d_stream_base.p, sl.d_pjobs.p, sl.h_recs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.mf_cap, sl.d_pll_list.p, sl.d_dec_list.p, list_cap,
-                          sl.d_vb_items.p, sl.vb_cap, hdr, hdr_pay, sl.h_hdr.p, sl.d_plan_ws.p, c->plan_fused ? 1 : 0));
+    HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->frames_hint / 2048 + 1), sl.streams(), NS, detect ? 1u : 0u, c->cfg.equalizer ? 1u : 0u, sl.vb_blk, sl.d_chain.p,
+                          sl.d_chain_count.p, sl.d_stream_base.p, sl.d_pjobs.p, sl.h_recs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.mf_cap, sl.d_pll_list.p, sl.dec_list(kDecPlain), sl.list_cap(), sl.d_vb_items.p, sl.vb_cap,
+                          sl.hdr_walk(), sl.hdr_pay(), sl.h_hdr.p, sl.d_plan_ws.p, c->plan_fused ? 1 : 0));
     const int tl = sl.timing_level;
-    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[4], st));
-    if (c->debug_stop_after == 4) { c->carry_reader[b % 3] = nullptr; HIP_OK(hipEventRecord(sl.ev[8], st)); return 0; }
+    if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvPlan], st));
+    if (c->debug_stop_after == 4) { c->carry_reader[b % 3] = nullptr; HIP_OK(hipEventRecord(sl.ev[kEvDone], st)); return 0; }
     if (!detect) {
         // grids stride over lists whose lengths only the device knows; size them from what the last block held
         const uint64_t fh = c->frames_hint ? std::min<uint64_t>(chain_slots, c->frames_hint + c->frames_hint / 2 + 64) : chain_slots;
@@ -960,10 +988,10 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         // fewer workgroups striding over the items: 8 per CU 34.3, 18: 35.1, one per item (36 per CU on config 2): 35.3 Gsamples/s)
         const unsigned mf_grid = (unsigned)std::min<uint64_t>(sl.mf_cap, c->mf_per_cu ? (uint64_t)c->mf_per_cu * (uint64_t)c->n_cus
                                                                                      : std::max<uint64_t>(8ull * (uint64_t)c->n_cus, c->mf_items_hint + c->mf_items_hint / 8 + 64));
-        HIP_OK(fx_launch_paymf(mf_grid, c->cfg.equalizer ? 1 : 0, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, hdr_pay, sl.d_chain.p, sl.d_symraw.p, c->d_tables));
-        HIP_OK(hipEventRecord(sl.ev[5], st));
-        c->carry_reader[b % 3] = sl.ev[5];
-        if (c->debug_stop_after == 5) { HIP_OK(hipEventRecord(sl.ev[8], st)); return 0; }
+        HIP_OK(fx_launch_paymf(mf_grid, c->cfg.equalizer ? 1 : 0, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.hdr_pay(), sl.d_chain.p, sl.d_symraw.p, c->d_tables));
+        HIP_OK(hipEventRecord(sl.ev[kEvMf], st));
+        c->carry_reader[b % 3] = sl.ev[kEvMf];
+        if (c->debug_stop_after == 5) { HIP_OK(hipEventRecord(sl.ev[kEvDone], st)); return 0; }
         // ---- the block's tail: its grids now (they stride over lists whose lengths only the device knows, sized from what the last
         // collected block held), its launches now or with the gang (launch_tails) ----
         sl.tail_pll_waves = (unsigned)(fh / 64 + FX_PLL_CLASSES); sl.tail_mf_grid = mf_grid;
@@ -1008,15 +1036,13 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         return launch_tails(c, &one, 1u);
     } else {
         // (in front of the event the next-but-one block's chain kernel waits for before it writes over the carried tail this one reads)
-        if (c->cfg.want_framesyms)
-            HIP_OK(fx_launch_detwin(st, std::min<unsigned>(std::max<unsigned>(sl.win_reserved, 1u), 4u * (unsigned)c->n_cus), d_streams, NS, sl.d_stream_base.p, sl.d_pjobs.p, hdr_pay, 0u,
-                                    sl.win_reserved, sl.h_win.p, sl.h_wintail.p, sl.h_winflag.p, 1, 0));
-        HIP_OK(hipEventRecord(sl.ev[5], st));
-        if (tl >= 1) HIP_OK(hipEventRecord(sl.ev[6], st));
-        if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[7], st));
-        c->carry_reader[b % 3] = sl.ev[5];
+        if (c->cfg.want_framesyms) HIP_OK(launch_detwin(c, sl, 0u, sl.win_reserved, false));
+        HIP_OK(hipEventRecord(sl.ev[kEvMf], st));
+        if (tl >= 1) HIP_OK(hipEventRecord(sl.ev[kEvPll], st));
+        if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvDec], st));
+        c->carry_reader[b % 3] = sl.ev[kEvMf];
     }
-    HIP_OK(hipEventRecord(sl.ev[8], st));
+    HIP_OK(hipEventRecord(sl.ev[kEvDone], st));
     return 0;
 }
 
@@ -1157,15 +1183,10 @@ int fxrx_iq_convert_host(int fmt, float scale, const void *in, uint64_t n_sample
 static int repair_rounds(fxrx_ctx_s *c, Slot &sl)
 {
     if (c->chain_slow) return 1;
-    const unsigned NS = c->cfg.n_streams;
-    const unsigned mode = c->cfg.mode == FXRX_MODE_DETECTOR ? FX_MODE_DETECT : FX_MODE_FLEXRX;
-    hipStream_t st = sl.st;
-    FxWalkJob *d_jobs = reinterpret_cast<FxWalkJob *>(sl.d_desc.p);
-    const FxStreamDesc *d_streams = reinterpret_cast<const FxStreamDesc *>(sl.d_desc.p + sl.o_streams);
-    FxBlockHdr *hdr = sl.d_hdr.p;
+    hipStream_t st = sl.st; FxBlockHdr *hdr = sl.hdr_walk();
     for (int round = 0; round < 64; round++) {
         HIP_OK(hipMemsetAsync(hdr, 0, sizeof(FxBlockHdr), st));
-        HIP_OK(fx_launch_chainfast(NS, st, d_streams, d_jobs, sl.d_wres.p, sl.d_frames.p, sl.d_chain.p, sl.d_chain_count.p, hdr, 0u, d_jobs, sl.d_req.p, nullptr, 0u));
+        HIP_OK(launch_chainfast(c, sl, st, kStitchQueue));
         FxBlockHdr hh;
         HIP_OK(hipMemcpyAsync(&hh, hdr, sizeof hh, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
@@ -1176,11 +1197,10 @@ static int repair_rounds(fxrx_ctx_s *c, Slot &sl)
             std::vector<uint32_t> req(hh.n_repair_req);
             HIP_OK(hipMemcpyAsync(req.data(), sl.d_req.p, req.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
-            const FxWalkJob *hj = reinterpret_cast<const FxWalkJob *>(sl.hp_desc.p);
-            for (uint32_t r : req) if ((r & 0x80000000u) && (r & 0x7fffffffu) < sl.NJ) c->st[hj[r & 0x7fffffffu].stream].noskip_left = 32;
+            mark_noskip(c, sl, req);
         }
         HIP_OK(hipMemsetAsync(hdr, 0, sizeof(FxBlockHdr), st));
-        HIP_OK(fx_launch_walk(mode, c->cfg.equalizer ? 1 : 0, c->cfg.soft_header ? 1 : 0, hh.n_repair_req, st, d_jobs, sl.d_req.p, sl.d_wres.p, sl.d_frames.p, sl.d_runs.p, sl.run_cap, hdr, c->d_tables, 1, (uint32_t)sl.NJ, nullptr, 0u));
+        HIP_OK(launch_walk(c, sl, st, sl.d_req.p, hh.n_repair_req, kWalkRequests));
         HIP_OK(hipMemcpyAsync(&hh, hdr, sizeof hh, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         sl.kept_hops += hh.hops; sl.kept_cheap += hh.hops_cheap; sl.kept_repairs += hh.walk_jobs_run ? hh.walk_jobs_run : 0;
@@ -1268,7 +1288,7 @@ static int repair_and_replay(fxrx_ctx_s *c, Slot &sl)
     if (sl.h_hdr.p->flags & (FX_BLK_NEEDS_REPAIR | FX_BLK_CARRY_OVERFLOW)) { set_err("fxrx_collect: block could not be repaired"); return FXRX_ERR_STATE; }
     if (sl.h_hdr.p->flags & FX_BLK_CHAIN_FULL) { set_err("fxrx_collect: chain table overflow (internal sizing error)"); return FXRX_ERR_STATE; }
     // the blocks behind it, oldest first (descriptors are rebuilt: carry buffers may have moved)
-    c->prev_chain = sl.ev[3];
+    c->prev_chain = sl.ev[kEvChain];
     const unsigned n_replay = carry_moved ? c->inflight - 1 : n_dep;
     for (unsigned k = 1; k <= n_replay; k++) {
         Slot &nx = *c->slots[(c->tail + k) % nslots];
@@ -1285,11 +1305,10 @@ static int repair_and_replay(fxrx_ctx_s *c, Slot &sl)
 // Reed-Solomon frames turning up unannounced): decode them now, on the block's stream, and wait
 static int finish_decode(fxrx_ctx_s *c, Slot &sl)
 {
-    if (sl.vb_blk && sl.h_hdr.p->vb_ticket) {          // frames were handed back: how many (the block is done: a plain copy)
-        uint32_t n_fb = 0;
-        HIP_OK(hipMemcpy(&n_fb, &(sl.d_hdr.p + 1)->n_vb_fallback, sizeof n_fb, hipMemcpyDeviceToHost));
-        sl.h_hdr.p->n_vb_fallback = n_fb; sl.h_hdr.p->vb_ticket = 0;
-    }
+    FxBlockHdr *hdr_pay = sl.hdr_pay();
+    // frames the batch path handed back: how many (the block is done: a plain copy)
+    auto fetch_fb = [&]() -> int { uint32_t nfb = 0; HIP_OK(hipMemcpy(&nfb, &hdr_pay->n_vb_fallback, sizeof nfb, hipMemcpyDeviceToHost)); sl.h_hdr.p->n_vb_fallback = nfb; sl.h_hdr.p->vb_ticket = 0; return 0; };
+    if (sl.vb_blk && sl.h_hdr.p->vb_ticket && fetch_fb()) return FXRX_ERR_HIP;
     const FxBlockHdr &h = *sl.h_hdr.p;
     const bool more_plain = h.n_dec_plain > sl.dec_launched, more_rs = h.n_dec_rs > 0 && sl.rs_launched == 0;   // (the Reed-Solomon instance strides: any launch covers all)
     const bool no_trellis = sl.vb_blk && sl.vb_fin_launched == 0;              // (left out of the chain: see fxrx_ctx_s.vb_early_tail)
@@ -1299,39 +1318,21 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     const bool late_trellis = no_trellis && !more_batch && *(volatile const uint32_t *)&sl.h_hdr.p->vb_dirty != 0u;
     const bool more_fb = sl.vb_blk && h.n_vb_fallback > sl.fb_launched;
     if (!more_plain && !more_rs && !more_batch && !more_fb && !late_trellis) return 0;
-    const uint32_t list_cap = sl.chain_cap + 64 * FX_PLL_CLASSES;
-    FxBlockHdr *hdr_pay = sl.d_hdr.p + 1;
-    const int soft = c->cfg.soft_decision ? (c->cfg.soft_block ? (c->cfg.soft_chain ? 3 : 2) : 1) : 0;     // (fx_launch_paydec)
-    FxPayResult *pres = nullptr;
-#ifdef FX_STAMPS
-    pres = sl.d_pres.p;
-#endif
-    if (more_plain)
-        HIP_OK(fx_launch_paydec(0, soft, sl.dec_launched, h.n_dec_plain - sl.dec_launched, c->dec_waves, sl.st, sl.d_pjobs.p, sl.d_dec_list.p, hdr_pay, sl.d_hard.p,
-                                sl.d_bufA.p, sl.d_bufB.p, sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
-    if (more_rs)
-        HIP_OK(fx_launch_paydec(1, soft, 0, h.n_dec_rs, 1u, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
-                                sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, nullptr));
+    HIP_OK(launch_decoders(c, sl, sl.st, sl.dec_launched, more_plain ? h.n_dec_plain - sl.dec_launched : 0u, more_rs ? h.n_dec_rs : 0u));
     if (more_batch || late_trellis) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
         HIP_OK(hipMemsetAsync(&hdr_pay->n_vb_fallback, 0, sizeof(uint32_t), sl.st));
-        if (more_batch)
-        {
+        if (more_batch) {
             FxVbpreGang g; g.n = 1; g.m[0] = vbpre_member(sl, 0u, h.n_dec_batch);
             HIP_OK(fx_launch_vbpre(&g, sl.st, c->d_tables, c->vb_clean ? 1 : 0, sl.vb_early ? 1 : 0));
         }
-        HIP_OK(fx_launch_vbitems(0, h.n_vb_items, sl.st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, c->vb_debug, 1, 1));
-        HIP_OK(fx_launch_vbfinish(0, h.n_dec_batch, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 2 * (size_t)list_cap, hdr_pay, sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p,
-                                  sl.d_vb_vec.p, sl.d_vb_st.p, sl.d_dec_list.p + 3 * (size_t)list_cap, list_cap, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0));
-        HIP_OK(fx_launch_paydec(0, 0, 0, kFallbackWaves, 1u, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 3 * (size_t)list_cap, hdr_pay, sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
-                                sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, sl.h_hdr.p));
+        HIP_OK(launch_trellis(c, sl, sl.st, h.n_vb_items, 1, 1, h.n_dec_batch, kFallbackWaves));
         sl.vb_pre_launched = sl.vb_fin_launched = h.n_dec_batch; sl.vb_items_launched = h.n_vb_items; sl.fb_launched = kFallbackWaves;
         HIP_OK(hipStreamSynchronize(sl.st));
-        { uint32_t nfb = 0; HIP_OK(hipMemcpy(&nfb, &hdr_pay->n_vb_fallback, sizeof nfb, hipMemcpyDeviceToHost)); sl.h_hdr.p->n_vb_fallback = nfb; sl.h_hdr.p->vb_ticket = 0; }
+        if (fetch_fb()) return FXRX_ERR_HIP;
     }
     const uint32_t n_fb = *(volatile const uint32_t *)&sl.h_hdr.p->n_vb_fallback;
     if (sl.vb_blk && n_fb > sl.fb_launched) {
-        HIP_OK(fx_launch_paydec(0, 0, sl.fb_launched, n_fb - sl.fb_launched, c->dec_waves, sl.st, sl.d_pjobs.p, sl.d_dec_list.p + 3 * (size_t)list_cap, hdr_pay,
-                                sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, pres, c->d_tables, sl.h_hdr.p));
+        HIP_OK(launch_paydec(c, sl, sl.st, kDecFallback, sl.fb_launched, n_fb - sl.fb_launched, c->dec_waves));
         sl.fb_launched = n_fb;
     }
     HIP_OK(hipStreamSynchronize(sl.st));
@@ -1349,9 +1350,7 @@ static int finish_windows(fxrx_ctx_s *c, Slot &sl)
     const uint32_t n = sl.h_hdr.p->n_frames;
     if (n <= sl.win_reserved) return 0;
     { const int r = sl.h_win.grow_keep((size_t)n * FX_NFFT, (size_t)sl.win_reserved * FX_NFFT); if (r) return r; }     // (n > win_reserved: every reserved slot was written)
-    const FxStreamDesc *d_streams = reinterpret_cast<const FxStreamDesc *>(sl.d_desc.p + sl.o_streams);
-    HIP_OK(fx_launch_detwin(sl.st, std::min<unsigned>(n - sl.win_reserved, 4u * (unsigned)c->n_cus), d_streams, c->cfg.n_streams, sl.d_stream_base.p, sl.d_pjobs.p, sl.d_hdr.p + 1,
-                            sl.win_reserved, n, sl.h_win.p, sl.h_wintail.p, sl.h_winflag.p, 0, 1));
+    HIP_OK(launch_detwin(c, sl, sl.win_reserved, n, true));
     HIP_OK(hipStreamSynchronize(sl.st));
     c->late_windows++;
     return 0;
@@ -1401,7 +1400,7 @@ int fxrx_ready(fxrx_ctx *c)
     if (!c->slots[c->tail]->tail_launched) {                   // still in the open gang: out with it, or a caller that polls would wait for ever
         if (hipSetDevice(c->cfg.device) != hipSuccess || close_gang(c)) return FXRX_ERR_HIP;
     }
-    const hipError_t e = hipEventQuery(c->slots[c->tail]->ev[8]);
+    const hipError_t e = hipEventQuery(c->slots[c->tail]->ev[kEvDone]);
     return e == hipSuccess ? 1 : (e == hipErrorNotReady ? 0 : FXRX_ERR_HIP);
 }
 
@@ -1479,12 +1478,12 @@ static int collect_block(fxrx_ctx_s *c)
     const unsigned nslots = c->depth + 1;
     Slot &sl = *c->slots[c->tail];
     const auto tw = std::chrono::steady_clock::now();
-    // (a block whose tail is still deferred has no ev[8] to wait for: waiting on the event as an earlier use left it would return at once)
+    // (a block whose tail is still deferred has no ev[kEvDone] to wait for: waiting on the event as an earlier use left it would return at once)
     if (!sl.tail_launched) { const int r = close_gang(c); if (r) return r; }
     if (!sl.tail_launched) { set_err("fxrx_collect: block without a tail (internal error)"); return FXRX_ERR_STATE; }
-    HIP_OK(hipEventSynchronize(sl.ev[8]));
+    HIP_OK(hipEventSynchronize(sl.ev[kEvDone]));
     // what collect still enqueues for this block goes to its own stream: behind the tail, wherever that ran
-    if (sl.tail_st != sl.st) { HIP_OK(hipStreamWaitEvent(sl.st, sl.ev[8], 0)); sl.tail_st = sl.st; }
+    if (sl.tail_st != sl.st) { HIP_OK(hipStreamWaitEvent(sl.st, sl.ev[kEvDone], 0)); sl.tail_st = sl.st; }
     if (c->debug_fail_collect) { c->debug_fail_collect--; set_err("fxrx_collect: injected failure (fxrx_debug_fail)"); return FXRX_ERR_STATE; }
     {
         const uint32_t flags = sl.h_hdr.p->flags;
@@ -1494,18 +1493,16 @@ static int collect_block(fxrx_ctx_s *c)
         if (flags & (FX_BLK_CARRY_OVERFLOW | FX_BLK_NEEDS_REPAIR)) { int r = repair_and_replay(c, sl); if (r) return r; }
     }
     sl.dbg_collect_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - c->ref_host_ms;
-    if (sl.timing_level >= 2 && c->ref_event) { float m = 0; (void)hipEventElapsedTime(&m, c->ref_event, sl.ev[0]); sl.dbg_gpu_start_ms = m; (void)hipEventElapsedTime(&m, c->ref_event, sl.ev[8]); sl.dbg_gpu_done_ms = m; }
+    if (sl.timing_level >= 2 && c->ref_event) { float m = 0; (void)hipEventElapsedTime(&m, c->ref_event, sl.ev[kEvStart]); sl.dbg_gpu_start_ms = m; (void)hipEventElapsedTime(&m, c->ref_event, sl.ev[kEvDone]); sl.dbg_gpu_done_ms = m; }
     if (c->debug_stop_after) { sl.out.clear(); sl.busy = false; c->last = &sl; c->tail = (c->tail + 1) % nslots; c->inflight--; return 0; }
     if (c->cfg.mode != FXRX_MODE_DETECTOR) { int r = finish_decode(c, sl); if (r) return r; }
     else if (c->cfg.want_framesyms) { int r = finish_windows(c, sl); if (r) return r; }
     if (sl.h_hdr.p->n_repair_req) c->inchain_left = 16;
     if (sl.h_hdr.p->n_repair_req && sl.h_hdr.p->verify_failures) {
-        // the chain mended something by itself: streams in which a skipped hop fired are walked with the exact detector on every
-        // hop for their next blocks (the list says which; a rare, small copy)
+        // the chain mended something by itself; the list says in which streams a skipped hop fired (a rare, small copy)
         std::vector<uint32_t> req(std::min<size_t>(sl.h_hdr.p->n_repair_req, 2 * sl.NJ + 16));
         HIP_OK(hipMemcpy(req.data(), sl.d_req.p, req.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        const FxWalkJob *hj = reinterpret_cast<const FxWalkJob *>(sl.hp_desc.p);
-        for (uint32_t r : req) if ((r & 0x80000000u) && (r & 0x7fffffffu) < sl.NJ) c->st[hj[r & 0x7fffffffu].stream].noskip_left = 32;
+        mark_noskip(c, sl, req);
     }
     sl.timing.host_collectwait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count();
     const FxBlockHdr &h = *sl.h_hdr.p;
@@ -1562,15 +1559,15 @@ static int collect_block(fxrx_ctx_s *c)
     fxrx_timing &t = sl.timing;
     float ms = 0;
     if (sl.timing_level >= 2) {
-        (void)hipEventElapsedTime(&ms, sl.ev[0], sl.ev[1]); t.walk_ms = ms;
-        (void)hipEventElapsedTime(&ms, sl.ev[1], sl.ev[2]); t.seekverify_ms = ms;
-        (void)hipEventElapsedTime(&ms, sl.ev[2], sl.ev[4]); t.chain_ms = ms;
+        (void)hipEventElapsedTime(&ms, sl.ev[kEvStart], sl.ev[kEvWalk]); t.walk_ms = ms;
+        (void)hipEventElapsedTime(&ms, sl.ev[kEvWalk], sl.ev[kEvVerify]); t.seekverify_ms = ms;
+        (void)hipEventElapsedTime(&ms, sl.ev[kEvVerify], sl.ev[kEvPlan]); t.chain_ms = ms;
         if (!detect) {
-            (void)hipEventElapsedTime(&ms, sl.ev[4], sl.ev[5]); t.paymf_ms = ms;
-            (void)hipEventElapsedTime(&ms, sl.ev[6], sl.ev[7]); t.paydec_ms = ms;
+            (void)hipEventElapsedTime(&ms, sl.ev[kEvPlan], sl.ev[kEvMf]); t.paymf_ms = ms;
+            (void)hipEventElapsedTime(&ms, sl.ev[kEvPll], sl.ev[kEvDec]); t.paydec_ms = ms;
         }
     }
-    if (sl.timing_level >= 1 && !detect) { (void)hipEventElapsedTime(&ms, sl.ev[5], sl.ev[6]); t.paypll_ms = ms; }
+    if (sl.timing_level >= 1 && !detect) { (void)hipEventElapsedTime(&ms, sl.ev[kEvMf], sl.ev[kEvPll]); t.paypll_ms = ms; }
     t.total_ms = t.walk_ms + t.seekverify_ms + t.chain_ms + t.paymf_ms + t.paypll_ms + t.paydec_ms;
     t.hops = h.hops + sl.kept_hops; t.hops_cheap = h.hops_cheap + sl.kept_cheap; t.walk_jobs = sl.NJ; t.repairs = h.repairs + sl.kept_repairs + h.n_repair_req; t.frames = h.n_frames;
     t.payload_symbols = h.sym_total; t.verify_hops = h.verify_hops + sl.kept_vhops; t.verify_failures = h.verify_failures + sl.kept_vfail;
