@@ -90,7 +90,7 @@ EXPORTS = [
     "fxrx_mod_from_index", "fxrx_mod_to_index", "fxrx_inner_from_index", "fxrx_inner_to_index",
     "fxrx_outer_from_index", "fxrx_outer_to_index",
     "fxtx_create", "fxtx_destroy", "fxtx_frame_len", "fxtx_generate",
-    "fxtx_apply_channel", "fxrx_set_timing", "fxrx_debug_block_times", "fxrx_ready", "fxrx_inflight", "fxrx_debug_fail", "fxrx_debug_gang_stats", "fxrx_debug_prescan_stats", "fxrx_debug_prescan_words", "fxrx_debug_gang_open", "fxrx_pinned_alloc", "fxrx_pinned_free", "fxrx_sync_context",
+    "fxtx_apply_channel", "fxrx_set_timing", "fxrx_debug_block_times", "fxrx_ready", "fxrx_inflight", "fxrx_debug_fail", "fxrx_debug_gang_stats", "fxrx_debug_prescan_stats", "fxrx_debug_prescan_words", "fxrx_debug_gang_open", "fxrx_debug_late_stats", "fxrx_pinned_alloc", "fxrx_pinned_free", "fxrx_sync_context",
     "fxrx_debug_header_decode", "fxrx_debug_block_decode", "fxrx_sync_set_soft_block",
     "fxrx_debug_block_siso", "fxrx_sync_set_soft_chain",
     "fxrx_sync_set_streaming", "fxrx_qdet_flush", "fxrx_qdet_pending", "fxrx_qdet_set_block", "fxrx_qdet_context",
@@ -200,6 +200,7 @@ def lib():
     L.fxrx_debug_prescan_stats.restype = C.c_int; L.fxrx_debug_prescan_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 3)]
     L.fxrx_debug_prescan_words.restype = C.c_int
     L.fxrx_debug_prescan_words.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64 * 3)]
+    L.fxrx_debug_late_stats.restype = C.c_int; L.fxrx_debug_late_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 10)]
     L.fxrx_debug_gang_open.restype = C.c_int; L.fxrx_debug_gang_open.argtypes = [C.c_void_p]
     L.fxrx_debug_header_decode.restype = C.c_int
     L.fxrx_debug_header_decode.argtypes = [C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.POINTER(C.c_int)]

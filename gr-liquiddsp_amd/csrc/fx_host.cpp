@@ -263,6 +263,7 @@ struct fxrx_ctx_s {
     std::vector<std::unique_ptr<Slot>> slots; unsigned depth = 1, head = 0, tail = 0, inflight = 0;
     Slot *last = nullptr;                // slot whose results are currently exposed through fxrx_result
     uint64_t replays = 0, repairs_host = 0, late_decodes = 0;
+    uint64_t late_reason[6] = {};        // fxrx_debug_late_stats: collected blocks finish_decode acted on, per reason (a block may count under several)
     uint64_t late_windows = 0;           // blocks whose aligned windows had to be completed at collect (more detections than slots were reserved)
     uint32_t detwin_reserve = 0;         // FXRX_DETWIN_RESERVE (tests): window slots reserved per block instead of the last block's count plus a margin
     unsigned noskip_left = 0;            // blocks still to be walked with the exact detector on every hop (after a verification failure)
@@ -506,6 +507,8 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_VB_BLK")) if (std::atoi(e) > 0) c->vb_blk_force = (uint32_t)std::min(4096, std::max(128, (std::atoi(e) + 63) / 64 * 64));
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) c->n_cus = prop.multiProcessorCount;
+    // FXRX_DEBUG_CUS (tests): plan every launch as for a chip, or a partition, of that many CUs -- never more than there are
+    if (const char *e = std::getenv("FXRX_DEBUG_CUS")) c->n_cus = std::min(c->n_cus, std::max(1, std::atoi(e)));
     if (upload_tables(c) != 0) return fail();
     const unsigned NS = cfg->n_streams;
     c->st.resize(NS);
@@ -1001,7 +1004,8 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         // keep turning up.  What a launch did not cover is decoded when the block is collected (finish_decode).
         // (the plain instance too is only launched while such frames keep turning up: with the batch path on, a block normally has none)
         sl.dec_launched = c->first_block ? chain_slots : (c->plain_hint || !sl.vb_blk ? (unsigned)std::min<uint64_t>(chain_slots, c->plain_hint + c->plain_hint / 2 + 64) : 0u);
-        sl.rs_launched = c->rs_hint ? (unsigned)std::min<uint64_t>(chain_slots, c->rs_hint + c->rs_hint / 2 + 64) : 0u;
+        // (nothing collected yet: launched like the others -- the instance strides, a margin's worth of waves covers whatever the block holds)
+        sl.rs_launched = c->rs_hint ? (unsigned)std::min<uint64_t>(chain_slots, c->rs_hint + c->rs_hint / 2 + 64) : c->first_block ? std::min<uint32_t>(chain_slots, 64u) : 0u;
         // batch Viterbi path (most frames: hard decisions, convolutional fec0): front part, forward pass over trellis blocks, back part
         if (sl.vb_blk) {
             sl.vb_pre_launched = c->first_block ? chain_slots : (unsigned)std::min<uint64_t>(chain_slots, c->batch_hint + c->batch_hint / 2 + 64);
@@ -1017,7 +1021,8 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
             // frames whose hand-overs could not be verified (a block that ran again and ended differently): the wave-per-frame decoder,
             // launched with the chain only while such frames keep turning up (the count reaches the host either way; what a launch
             // did not cover is decoded when the block is collected)
-            sl.fb_launched = trellis && (c->first_block || c->fb_hint || c->vb_debug) ? (uint32_t)std::min<uint64_t>(chain_slots, std::max<uint64_t>(kFallbackWaves, c->fb_hint + c->fb_hint / 2 + 16)) : 0u;
+            sl.fb_launched = c->first_block ? chain_slots
+                           : trellis && (c->fb_hint || c->vb_debug) ? (uint32_t)std::min<uint64_t>(chain_slots, std::max<uint64_t>(kFallbackWaves, c->fb_hint + c->fb_hint / 2 + 16)) : 0u;
         } else { sl.vb_pre_launched = sl.vb_items_launched = sl.vb_fin_launched = sl.fb_launched = 0; sl.vb_early = false; sl.tail_vb_packed = sl.tail_with_fix = 0; }
         sl.timing.trellis_launched = sl.vb_fin_launched ? 1 : 0;
         // Deferred into the open gang when there is enough ahead of this block to keep the queues busy meanwhile: a deep pipeline
@@ -1312,12 +1317,14 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     const FxBlockHdr &h = *sl.h_hdr.p;
     const bool more_plain = h.n_dec_plain > sl.dec_launched, more_rs = h.n_dec_rs > 0 && sl.rs_launched == 0;   // (the Reed-Solomon instance strides: any launch covers all)
     const bool no_trellis = sl.vb_blk && sl.vb_fin_launched == 0;              // (left out of the chain: see fxrx_ctx_s.vb_early_tail)
-    const bool more_batch = h.n_dec_batch > sl.vb_pre_launched || (!no_trellis && h.n_vb_items > sl.vb_items_launched);
+    const bool more_frames = h.n_dec_batch > sl.vb_pre_launched, more_items = !no_trellis && h.n_vb_items > sl.vb_items_launched;
+    const bool more_batch = more_frames || more_items;
     // fx_vbpre_kernel met a frame that is not clean and the trellis kernels were not launched: they run now, over all items (clean
     // frames' items are off, their waves of the back part leave at once); fx_vbpre_kernel itself is done and is not needed again
     const bool late_trellis = no_trellis && !more_batch && *(volatile const uint32_t *)&sl.h_hdr.p->vb_dirty != 0u;
     const bool more_fb = sl.vb_blk && h.n_vb_fallback > sl.fb_launched;
     if (!more_plain && !more_rs && !more_batch && !more_fb && !late_trellis) return 0;
+    const bool why[6] = { more_plain, more_rs, more_frames, more_items, more_fb, late_trellis };      // fxrx_debug_late_stats
     HIP_OK(launch_decoders(c, sl, sl.st, sl.dec_launched, more_plain ? h.n_dec_plain - sl.dec_launched : 0u, more_rs ? h.n_dec_rs : 0u));
     if (more_batch || late_trellis) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
         HIP_OK(hipMemsetAsync(&hdr_pay->n_vb_fallback, 0, sizeof(uint32_t), sl.st));
@@ -1338,6 +1345,7 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     HIP_OK(hipStreamSynchronize(sl.st));
     sl.dec_launched = std::max(sl.dec_launched, h.n_dec_plain); if (more_rs) sl.rs_launched = h.n_dec_rs;
     c->late_decodes++;
+    for (int i = 0; i < 6; i++) c->late_reason[i] += why[i] ? 1u : 0u;
     return 0;
 }
 
@@ -1431,6 +1439,18 @@ int fxrx_debug_gang_stats(const fxrx_ctx *c, uint64_t out[2])
 {
     if (!c || !out) return FXRX_ERR_ARG;
     out[0] = c->gang_launches; out[1] = c->gang_members;
+    return 0;
+}
+
+// out[0..5]: collected blocks so far that finish_decode completed because of -- plain frames beyond the launch | Reed-Solomon frames without
+// a launch | batch-path frames beyond the launch | trellis work items beyond the launch | handed-back frames beyond the fallback launch |
+// frames that were not clean in a chain without the trellis kernels; out[6..9]: n_dec_plain, n_dec_batch, n_dec_rs, n_vb_items of the last collected block
+int fxrx_debug_late_stats(const fxrx_ctx *c, uint64_t out[10])
+{
+    if (!c || !out) return FXRX_ERR_ARG;
+    for (int i = 0; i < 6; i++) out[i] = c->late_reason[i];
+    const FxBlockHdr *h = c->last ? c->last->h_hdr.p : nullptr;
+    out[6] = h ? h->n_dec_plain : 0; out[7] = h ? h->n_dec_batch : 0; out[8] = h ? h->n_dec_rs : 0; out[9] = h ? h->n_vb_items : 0;
     return 0;
 }
 

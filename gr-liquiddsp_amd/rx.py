@@ -144,6 +144,16 @@ class RxContext:
             raise RxError("fxrx_debug_gang_stats failed")
         return int(out[0]), int(out[1])
 
+    LATE_REASONS = ("more_plain", "more_rs", "more_batch_frames", "more_batch_items", "more_fb", "late_trellis")
+
+    def late_stats(self):
+        """Ten counts: blocks so far whose decoding fxrx_collect had to complete, per reason (LATE_REASONS), then n_dec_plain, n_dec_batch,
+        n_dec_rs and n_vb_items of the last collected block: see fxrx_debug_late_stats."""
+        out = (C.c_uint64 * 10)()
+        if self.L.fxrx_debug_late_stats(self.h, C.byref(out)) != 0:
+            raise RxError("fxrx_debug_late_stats failed")
+        return tuple(int(v) for v in out)
+
     def gang_open(self):
         """Blocks in flight whose tails are deferred at this moment: see fxrx_debug_gang_open."""
         n = self.L.fxrx_debug_gang_open(self.h)

@@ -312,6 +312,13 @@ int fxrx_debug_prescan_stats(const fxrx_ctx *c, uint64_t out[3]);
  * holds a hit, 0 when none does; out[0] = position the walk goes on from, out[1] = hops added to the cheap-hop counter, out[2] = hops the
  * scan covers (new half inside the segment and the data, at most K) */
 int fxrx_debug_prescan_words(const uint32_t *words, uint32_t n_words, uint32_t K, int64_t start, int64_t stop, int64_t n, int64_t out[3]);
+/* tests: which of its reasons made fxrx_collect complete a block's decoding (fxrx_timing.late_decodes counts the blocks; a block may count
+ * under several reasons).  out[0..5], cumulative since fxrx_create: plain frames beyond the decode launch | Reed-Solomon frames and no
+ * Reed-Solomon launch | batch Viterbi frames beyond the launch | trellis work items beyond the launch | handed-back frames beyond the fallback
+ * launch | frames that were not clean in a chain without the trellis kernels.  out[6..9], of the last collected block: frames on the
+ * wave-per-frame list, on the batch Viterbi list, on the Reed-Solomon list, and trellis work items (class padding included).
+ * (FXRX_DEBUG_CUS=<n>, read by fxrx_create: plan the launches as for a chip of n CUs, 1 <= n <= the real count) */
+int fxrx_debug_late_stats(const fxrx_ctx *c, uint64_t out[10]);
 /* tests: blocks in flight whose tails are deferred at this moment (the open gang's members; 0 .. 3) */
 int fxrx_debug_gang_open(const fxrx_ctx *c);
 /* tests: run the walker's header decoder on the GPU over n headers given in host memory.  soft != 0: `in` holds 432 soft values per
