@@ -47,6 +47,7 @@
 #include "fx_device.h"
 #include "fx_codec.hpp"
 #include "fx_launch.h"
+#include "fx_traffic.h"
 
 namespace {
 
@@ -114,8 +115,6 @@ static bool pinned_device_ptr(const void *p, const void **dev, uintptr_t align_m
 inline unsigned iq_sample_bytes(int fmt) { return fmt == FXRX_IQ_FC32 ? 8u : fmt == FXRX_IQ_SC16 ? 4u : fmt == FXRX_IQ_SC8 ? 2u : 0u; }
 constexpr unsigned kMaxDepth = 32;
 constexpr unsigned kStateRing = kMaxDepth + 3;      // FxStreamState records per stream: one per block in flight and then some
-constexpr unsigned kTrellisHold = 8;                // blocks that keep the trellis kernels in their chain after a collected block with frames that were not clean
-constexpr uint32_t kFallbackWaves = 32;             // in-chain launch for frames the batch Viterbi path hands back (normally none)
 constexpr uint32_t kRepairCap = 256;                // frame-table slots per stream for walks done by the chain kernel
 
 struct StreamState {
@@ -172,9 +171,7 @@ struct Slot {
     DevBuf<uint8_t> d_vb_vec;                // batch Viterbi: metric differences at the start and end of every trellis block
     DevBuf<unsigned long long> d_vb_dw;      // its decision words, step-major within the 64 work items of a wave
     DevBuf<uint32_t> d_vb_st;                // traceback states and flags per work item
-    uint32_t vb_cap = 0, vb_blk = 0, vb_pre_launched = 0, vb_items_launched = 0, fb_launched = 0;
-    uint32_t vb_fin_launched = 0;            // waves of fx_vbfinish_kernel launched with the chain (0: the trellis kernels were left out)
-    bool vb_early = false;                   // clean frames finish in fx_vbpre_kernel (fxrx_ctx_s.vb_early_tail and the codeword check on)
+    uint32_t vb_cap = 0, vb_blk = 0;
     uint64_t vb_dw_words = 0, vb_slots_alloc = 128;
     DevBuf<FxPayJob> d_pjobs; DevBuf<FxPayResult> d_pres;
     uint32_t run_cap = 0, chain_cap = 0, mf_cap = 0, frame_slots = 0;
@@ -193,7 +190,6 @@ struct Slot {
     fxrx_timing timing{};
     double host_submit_ms = 0.0;
     bool any_late = false;
-    uint32_t dec_launched = 0, rs_launched = 0;   // decode waves launched with the chain (lean / Reed-Solomon instance)
     double dbg_submit_ms = 0.0, dbg_collect_ms = 0.0, dbg_gpu_start_ms = 0.0, dbg_gpu_done_ms = 0.0;   // fxrx_debug_block_times
     bool force_noskip = false;               // walk this block with the exact detector on every hop (nothing to verify)
     int timing_level = 0;                    // which stage events this block recorded (fxrx_set_timing)
@@ -201,7 +197,7 @@ struct Slot {
     uint32_t kept_hops = 0, kept_cheap = 0, kept_vhops = 0, kept_vfail = 0, kept_repairs = 0;   // walk-phase counters of a block whose back part was run again
     // the block's tail -- everything behind the payload matched filter: PLL, decode launches, symbol copy, ev[kEvPll .. kEvDone] --, whose grids are
     // fixed when the block is submitted; the launches themselves may wait in the context's open gang (launch_tails)
-    unsigned tail_pll_waves = 0, tail_mf_grid = 0; int tail_vb_packed = 0, tail_with_fix = 0;
+    TailPlan tail;
     bool tail_launched = true;               // false: deferred -- ev[kEvDone] has not been recorded for this block, nobody may wait for it
     hipStream_t tail_st = nullptr;           // the stream the tail went to (a gang's: its last member's)
     // views of the arenas: nothing is allocated or kept (jobs_rw: the chain kernel rewrites the jobs of the segments it queues for repair)
@@ -230,10 +226,7 @@ struct fxrx_ctx_s {
     uint64_t seq = 0;                    // blocks submitted so far
     hipEvent_t prev_chain = nullptr;     // chain kernel of the newest submitted block (borrowed from its slot)
     hipEvent_t carry_reader[3] = { nullptr, nullptr, nullptr };   // payload MF of the newest block that reads carry[i]
-    uint32_t verify_per = 4;             // hops per verification run (adapted to the traffic)
-    uint64_t frames_hint = 0, rs_hint = 0;   // frames / Reed-Solomon frames of the last collected block (size the PLL / decode grids)
-    uint64_t plain_hint = 0, batch_hint = 0, vb_items_hint = 0, vb_steps_hint = 0, vb_want_hint = 0;   // likewise: frames of the wave-per-frame / batch decoders, trellis blocks, trellis steps
-    bool first_block = true;             // nothing collected yet: grids cover their lists' capacity
+    Traffic traffic;                     // what the last collected block held: sizes the next blocks' grids and arenas (fx_traffic.h)
     bool batch_viterbi = true;           // FXRX_BATCH_VITERBI=0: every frame through the wave-per-frame decoder
     bool vb_clean = true;                // FXRX_VB_CLEAN=0: no codeword check in fx_vbpre_kernel, every batch-path frame runs the trellis
     // The repair round within the chain costs two launches per block -- and launches are what the pipeline is short of (DESIGN.md
@@ -242,21 +235,17 @@ struct fxrx_ctx_s {
     int inchain_repair = 1; unsigned inchain_left = 0;
     bool plan_fused = true;              // FXRX_PLAN_FUSED=0: the plan stage is two launches even when one workgroup plans the block
     // FXRX_VB_EARLY_TAIL=0: the tail of clean frames runs in fx_vbfinish_kernel and the trellis kernels are launched with every block.
-    // Otherwise fx_vbpre_kernel finishes clean frames, and the trellis kernels (forward pass, hand-over check, traceback, back part,
-    // fallback decoder: up to five launches a block) join the chain only while frames that need them keep turning up: for the next
-    // kTrellisHold blocks after a collected block that held one.  A block that meets one without them is completed when it is collected.
-    bool vb_early_tail = true; unsigned trellis_left = 0;
+    // Otherwise fx_vbpre_kernel finishes clean frames, and the trellis kernels join the chain only while frames that need them keep turning
+    // up (Traffic::trellis_left).  A block that meets one without them is completed when it is collected.
+    bool vb_early_tail = true;
     int timing_level = -1;               // stage events per block: -1 auto (all stages one block at a time, none with blocks in flight) | 0 none | 1 the PLL only | 2 all stages
     hipEvent_t ref_event = nullptr; double ref_host_ms = 0.0;   // fxrx_debug_block_times: a common origin of GPU and host clocks
     int debug_walk_twice = 0;            // FXRX_DEBUG_WALK_TWICE: the speculative walkers are launched twice, the stage time is the second launch's (cold-start experiment)
     int debug_stop_after = 0;            // FXRX_DEBUG_STOP_AFTER (tools/dev/dev_stage_cost.py): 4 plan | 5 matched filter | 6 PLL -- the chain ends there, no results
-    uint64_t vbfix_hint = 0;             // the last collected block's batch Viterbi path ran blocks again / handed frames back: the hand-over check is launched with the next one
-    uint64_t fb_hint = 0;                // frames the last collected block's batch Viterbi path handed back (sizes the fallback launch; 0: none enqueued)
     uint32_t walk_per_cu = 2;            // walker workgroups resident per CU (FXRX_WALK_PER_CU; follows the kernel's register budget)
     hipStream_t st_chain = nullptr;      // highest priority: the state-dependent stretch of continuing blocks (true walkers, their verification, chain kernel)
     uint32_t verify_per_cu = 4;          // FXRX_VERIFY_PER_CU: workgroups of the seek verifier per CU (they stride over the runs)
     uint32_t mf_per_cu = 0;              // FXRX_MF_PER_CU: workgroups of the payload matched filter per CU (0: one per item of the last block)
-    uint64_t mf_items_hint = 0;
     uint32_t plan_grid = 0;              // FXRX_PLAN_GRID: workgroups of the plan kernels (tests; default: from the last block's frame count)
     uint32_t vb_debug = 0, vb_blk_force = 0;   // tests: FXRX_VB_DEBUG (see fx_vbfix_kernel / fx_vbtrace_kernel), FXRX_VB_BLK (trellis steps per block)
     // pipeline: a ring of depth + 1 slots, so that the block whose results are exposed is never the one being refilled
@@ -281,7 +270,6 @@ struct fxrx_ctx_s {
     // walkers scan for their first preamble themselves -- measured faster on config 2, the extra launch costs more than the walkers
     // save).  FXRX_PRESCAN_HOPS: hops scanned per speculative job instead of the traffic's figure (0: none).
     bool prescan = false; int prescan_hops = -1;
-    uint64_t samples_hint = 0;           // samples of the last collected block (with frames_hint: the mean frame spacing)
     std::vector<Slot *> gang;            // the open gang: blocks in flight whose tails are deferred, oldest first
     uint64_t gang_launches = 0, gang_members = 0;   // fxrx_debug_gang_stats: tail launches that carried more than one block / the blocks they carried
 };
@@ -614,7 +602,7 @@ static inline hipError_t launch_trellis(const fxrx_ctx_s *c, const Slot &sl, hip
 {
     hipError_t e = fx_launch_vbitems(0, n_items, st, sl.d_pjobs.p, sl.d_vb_items.p, sl.vb_cap, sl.hdr_pay(), sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, c->vb_debug, packed, with_fix);
     if (e == hipSuccess) e = fx_launch_vbfinish(0, n_fin, st, sl.d_pjobs.p, sl.dec_list(kDecBatch), sl.hdr_pay(), sl.d_bufA.p, sl.d_bufB.p, sl.d_vb_dw.p, sl.d_vb_vec.p, sl.d_vb_st.p, sl.dec_list(kDecFallback),
-                                                sl.list_cap(), sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.vb_early ? 1 : 0);
+                                                sl.list_cap(), sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.tail.vb_early ? 1 : 0);
     return e != hipSuccess ? e : launch_paydec(c, sl, st, kDecFallback, 0u, fb_waves, 1u);
 }
 // detector windows of the records [first, last), on the block's stream; late: at collect (windows that start in the carried tail are not written again)
@@ -648,7 +636,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     if (c->prescan && !detect) {
         if (c->prescan_hops >= 0) ps_K = (uint32_t)c->prescan_hops;             // (as given: the last chunk may be a short one)
         else {
-            ps_K = c->frames_hint ? (uint32_t)std::min<uint64_t>(128, std::max<uint64_t>(16, c->samples_hint / c->frames_hint / FX_HOP + 2)) : 64u;
+            ps_K = c->traffic.frames ? (uint32_t)std::min<uint64_t>(128, std::max<uint64_t>(16, c->traffic.samples / c->traffic.frames / FX_HOP + 2)) : 64u;
             ps_K = (ps_K + FX_PRESCAN_CHUNK - 1) / FX_PRESCAN_CHUNK * FX_PRESCAN_CHUNK;
         }
     }
@@ -726,7 +714,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
             j.threshold = c->cfg.threshold;
             j.no_skip = (detect || !c->skip_seek || sl.force_noskip || sn.noskip) ? 1u : 0u;
             j.state_in = (first && cont) ? sd.state_in : nullptr;
-            j.stream = s; j.verify_per = c->verify_per; j.eq = (!detect && c->cfg.equalizer) ? 1u : 0u;
+            j.stream = s; j.verify_per = c->traffic.verify_per; j.eq = (!detect && c->cfg.equalizer) ? 1u : 0u;
             (first && cont ? late : early).push_back((uint32_t)jobs.size());
             jobs.push_back(j);
             p = j.stop; first = false;
@@ -757,7 +745,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     {
         const uint64_t want_items = 64ull * 4ull * (uint64_t)c->n_cus * 6ull;
         sl.vb_blk = (detect || c->cfg.soft_decision || !c->batch_viterbi) ? 0u
-                  : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(192, ((c->vb_steps_hint / want_items + 63) / 64) * 64));
+                  : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(192, ((c->traffic.vb_steps / want_items + 63) / 64) * 64));
     }
     if (sl.vb_blk && c->vb_blk_force) sl.vb_blk = c->vb_blk_force;
     // (arena: 1.5 trellis steps per sample of span -- QPSK r1/2 has 0.47, QAM16 r2/3 1.17 -- or what the last block's traffic
@@ -765,7 +753,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
     // decoded by the wave-per-frame kernel, and the next block's arena is larger.  Sized in steps, not items, so that a
     // change of block length does not reallocate gigabytes.)
     {
-        const uint64_t steps_cap = std::min<uint64_t>(std::max<uint64_t>(span + span / 2, c->vb_steps_hint + c->vb_steps_hint / 4), 4 * span);
+        const uint64_t steps_cap = std::min<uint64_t>(std::max<uint64_t>(span + span / 2, c->traffic.vb_steps + c->traffic.vb_steps / 4), 4 * span);
         sl.vb_cap = sl.vb_blk ? (uint32_t)((steps_cap / sl.vb_blk + 2048 + 127) & ~127ull) : 128u;
         // (the decision-word arena itself: the same number of words whatever the block length -- the 2048 extra work items
         // priced at the longest block --, or a change of block length by one notch would reallocate it, 1.5 x larger)
@@ -802,7 +790,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
         // aligned windows: one 4 KB slot per detection the block is expected to hold -- the last collected block's count plus a margin, as
         // for the other lists only the device can count (one slot per possible detection would be twice the input, in pinned memory); a
         // block that holds more is completed when it is collected (finish_windows)
-        sl.win_reserved = (uint32_t)std::min<uint64_t>(chain_slots, c->detwin_reserve ? c->detwin_reserve : c->frames_hint + c->frames_hint / 2 + 64);
+        sl.win_reserved = c->detwin_reserve ? std::min(chain_slots, c->detwin_reserve) : with_margin(c->traffic.frames, chain_slots);
         if (sl.h_win.reserve((size_t)sl.win_reserved * FX_NFFT) || sl.h_wintail.reserve(2 * (size_t)NS * FX_NFFT) || sl.h_winflag.reserve(1)) return FXRX_ERR_HIP;
         *sl.h_winflag.p = 0u;
     }
@@ -902,7 +890,7 @@ static int launch_tails(fxrx_ctx_s *c, Slot *const *m, unsigned n)
     };
     {
         FxPllGang g; unsigned waves[FX_GANG_MAX]; g.n = n;
-        for (unsigned i = 0; i < n; i++) { const Slot &sl = *m[i]; g.m[i] = FxPllMember{ sl.d_pjobs.p, sl.d_pll_list.p, sl.hdr_pay(), sl.d_symraw.p, sl.d_symraw.p, sl.d_hard.p, sl.h_recs.p }; waves[i] = sl.tail_pll_waves; }
+        for (unsigned i = 0; i < n; i++) { const Slot &sl = *m[i]; g.m[i] = FxPllMember{ sl.d_pjobs.p, sl.d_pll_list.p, sl.hdr_pay(), sl.d_symraw.p, sl.d_symraw.p, sl.d_hard.p, sl.h_recs.p }; waves[i] = sl.tail.pll_waves; }
         HIP_OK(fx_launch_paypll(&g, waves, c->pll_waves, st, c->d_tables));
     }
     for (unsigned i = 0; i < n; i++) if (m[i]->timing_level >= 1) HIP_OK(hipEventRecord(m[i]->ev[kEvPll], st));
@@ -912,19 +900,19 @@ static int launch_tails(fxrx_ctx_s *c, Slot *const *m, unsigned n)
         if (c->cfg.soft_decision) {
             // per-bit soft values from the carrier-recovered symbols (data parallel, off the PLL's recurrence); the decoder
             // de-interleaves them in place, so a caller that wants to see them gets a copy first
-            HIP_OK(fx_launch_softdemod(sl.tail_mf_grid, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.hdr_pay(), sl.d_symraw.p, sl.d_hard.p, sl.d_soft.p, c->d_tables));
+            HIP_OK(fx_launch_softdemod(sl.tail.mf_grid, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.hdr_pay(), sl.d_symraw.p, sl.d_hard.p, sl.d_soft.p, c->d_tables));
             if (c->cfg.want_framesyms) HIP_OK(hipMemcpyAsync(sl.h_soft.p, sl.d_soft.p, 8 * sl.byte_cap, hipMemcpyDeviceToHost, st));
         }
-        HIP_OK(launch_decoders(c, sl, st, 0u, sl.dec_launched, sl.rs_launched));
+        HIP_OK(launch_decoders(c, sl, st, 0u, sl.tail.plain, sl.tail.rs));
     }
     {
         FxVbpreGang g; g.n = n;
-        for (unsigned i = 0; i < n; i++) g.m[i] = vbpre_member(*m[i], 0u, m[i]->vb_blk ? m[i]->vb_pre_launched : 0u);
+        for (unsigned i = 0; i < n; i++) g.m[i] = vbpre_member(*m[i], 0u, m[i]->vb_blk ? m[i]->tail.vb_pre : 0u);
         HIP_OK(fx_launch_vbpre(&g, st, c->d_tables, c->vb_clean ? 1 : 0, c->vb_early_tail && c->vb_clean ? 1 : 0));
     }
     for (unsigned i = 0; i < n; i++) {
         Slot &sl = *m[i];
-        if (sl.vb_blk) HIP_OK(launch_trellis(c, sl, st, sl.vb_items_launched, sl.tail_vb_packed, sl.tail_with_fix, sl.vb_fin_launched, sl.fb_launched));
+        if (sl.vb_blk) HIP_OK(launch_trellis(c, sl, st, sl.tail.vb_items, sl.tail.vb_packed, sl.tail.with_fix, sl.tail.vb_fin, sl.tail.fb));
         if (sl.timing_level >= 2) HIP_OK(hipEventRecord(sl.ev[kEvDec], st));
         // (a copy kernel: it knows how many symbols the block really holds)
         if (c->cfg.want_framesyms) HIP_OK(fx_launch_symcopy(2u * (unsigned)c->n_cus, st, sl.hdr_pay(), sl.d_symraw.p, sl.h_framesyms.p));
@@ -978,60 +966,31 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
     if (chain_mode == kChainFast && chain_st && chain_st != st) HIP_OK(hipStreamWaitEvent(st, sl.ev[kEvChain], 0));   // back onto the block's own stream
     c->prev_chain = sl.ev[kEvChain];
     // (the plan kernels' workgroups take contiguous ranges of the chain's frames: about 2048 each, from the last block's count)
-    HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->frames_hint / 2048 + 1), sl.streams(), NS, detect ? 1u : 0u, c->cfg.equalizer ? 1u : 0u, sl.vb_blk, sl.d_chain.p,
+    HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->traffic.frames / 2048 + 1), sl.streams(), NS, detect ? 1u : 0u, c->cfg.equalizer ? 1u : 0u, sl.vb_blk, sl.d_chain.p,
                           sl.d_chain_count.p, sl.d_stream_base.p, sl.d_pjobs.p, sl.h_recs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.mf_cap, sl.d_pll_list.p, sl.dec_list(kDecPlain), sl.list_cap(), sl.d_vb_items.p, sl.vb_cap,
                           sl.hdr_walk(), sl.hdr_pay(), sl.h_hdr.p, sl.d_plan_ws.p, c->plan_fused ? 1 : 0));
     const int tl = sl.timing_level;
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvPlan], st));
     if (c->debug_stop_after == 4) { c->carry_reader[b % 3] = nullptr; HIP_OK(hipEventRecord(sl.ev[kEvDone], st)); return 0; }
     if (!detect) {
-        // grids stride over lists whose lengths only the device knows; size them from what the last block held
-        const uint64_t fh = c->frames_hint ? std::min<uint64_t>(chain_slots, c->frames_hint + c->frames_hint / 2 + 64) : chain_slots;
-        // (one workgroup per item of 1024 symbols when the previous block's count is anything to go by -- measured better than
-        // fewer workgroups striding over the items: 8 per CU 34.3, 18: 35.1, one per item (36 per CU on config 2): 35.3 Gsamples/s)
-        const unsigned mf_grid = (unsigned)std::min<uint64_t>(sl.mf_cap, c->mf_per_cu ? (uint64_t)c->mf_per_cu * (uint64_t)c->n_cus
-                                                                                     : std::max<uint64_t>(8ull * (uint64_t)c->n_cus, c->mf_items_hint + c->mf_items_hint / 8 + 64));
-        HIP_OK(fx_launch_paymf(mf_grid, c->cfg.equalizer ? 1 : 0, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.hdr_pay(), sl.d_chain.p, sl.d_symraw.p, c->d_tables));
+        // grids stride over lists whose lengths only the device knows; size them from what the last collected block held, as it stands now
+        // (a replay plans again).  What a launch did not cover is decoded when the block is collected (finish_decode).
+        const TailPlan plan = plan_tail(c->traffic, TailCaps{ chain_slots, sl.mf_cap, sl.vb_cap, sl.vb_blk }, TailKnobs{ c->depth, c->n_cus, c->mf_per_cu, c->vb_debug, c->vb_early_tail, c->vb_clean });
+        HIP_OK(fx_launch_paymf(plan.mf_grid, c->cfg.equalizer ? 1 : 0, st, sl.d_pjobs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.hdr_pay(), sl.d_chain.p, sl.d_symraw.p, c->d_tables));
         HIP_OK(hipEventRecord(sl.ev[kEvMf], st));
         c->carry_reader[b % 3] = sl.ev[kEvMf];
         if (c->debug_stop_after == 5) { HIP_OK(hipEventRecord(sl.ev[kEvDone], st)); return 0; }
-        // ---- the block's tail: its grids now (they stride over lists whose lengths only the device knows, sized from what the last
-        // collected block held), its launches now or with the gang (launch_tails) ----
-        sl.tail_pll_waves = (unsigned)(fh / 64 + FX_PLL_CLASSES); sl.tail_mf_grid = mf_grid;
-        // decode: one wave per frame.  The lean instance has no loop (it would double its registers) and an empty workgroup
-        // still has to be given its registers before it can leave: so the grid covers what the last block held plus a margin,
-        // not the list's capacity, and the Reed-Solomon instance (256 registers a wave) is only launched while such frames
-        // keep turning up.  What a launch did not cover is decoded when the block is collected (finish_decode).
-        // (the plain instance too is only launched while such frames keep turning up: with the batch path on, a block normally has none)
-        sl.dec_launched = c->first_block ? chain_slots : (c->plain_hint || !sl.vb_blk ? (unsigned)std::min<uint64_t>(chain_slots, c->plain_hint + c->plain_hint / 2 + 64) : 0u);
-        // (nothing collected yet: launched like the others -- the instance strides, a margin's worth of waves covers whatever the block holds)
-        sl.rs_launched = c->rs_hint ? (unsigned)std::min<uint64_t>(chain_slots, c->rs_hint + c->rs_hint / 2 + 64) : c->first_block ? std::min<uint32_t>(chain_slots, 64u) : 0u;
-        // batch Viterbi path (most frames: hard decisions, convolutional fec0): front part, forward pass over trellis blocks, back part
-        if (sl.vb_blk) {
-            sl.vb_pre_launched = c->first_block ? chain_slots : (unsigned)std::min<uint64_t>(chain_slots, c->batch_hint + c->batch_hint / 2 + 64);
-            // (two work items per lane once the items fill the chip or other blocks do; one per lane for a lone small block)
-            sl.tail_vb_packed = (c->depth > 1 || c->vb_items_hint > 64ull * 4ull * (uint64_t)c->n_cus * 3ull / 2ull) ? 1 : 0;
-            sl.tail_with_fix = (c->first_block || c->vbfix_hint || c->vb_debug) ? 1 : 0;
-            // (the trellis kernels: always without the early tail; with it, while the traffic has frames for them)
-            sl.vb_early = c->vb_early_tail && c->vb_clean;
-            const bool trellis = !sl.vb_early || c->first_block || c->vb_debug || c->trellis_left > 0;
-            if (c->trellis_left) c->trellis_left--;
-            sl.vb_items_launched = !trellis ? 0u : c->first_block ? sl.vb_cap : (unsigned)std::min<uint64_t>(sl.vb_cap, c->vb_items_hint + c->vb_items_hint / 2 + 1024);
-            sl.vb_fin_launched = trellis ? sl.vb_pre_launched : 0u;
-            // frames whose hand-overs could not be verified (a block that ran again and ended differently): the wave-per-frame decoder,
-            // launched with the chain only while such frames keep turning up (the count reaches the host either way; what a launch
-            // did not cover is decoded when the block is collected)
-            sl.fb_launched = c->first_block ? chain_slots
-                           : trellis && (c->fb_hint || c->vb_debug) ? (uint32_t)std::min<uint64_t>(chain_slots, std::max<uint64_t>(kFallbackWaves, c->fb_hint + c->fb_hint / 2 + 16)) : 0u;
-        } else { sl.vb_pre_launched = sl.vb_items_launched = sl.vb_fin_launched = sl.fb_launched = 0; sl.vb_early = false; sl.tail_vb_packed = sl.tail_with_fix = 0; }
-        sl.timing.trellis_launched = sl.vb_fin_launched ? 1 : 0;
+        // ---- the block's tail: its grids now, its launches now or with the gang (launch_tails) ----
+        sl.tail = plan;
+        if (sl.vb_blk && c->traffic.trellis_left) c->traffic.trellis_left--;
+        sl.timing.trellis_launched = plan.vb_fin ? 1 : 0;
         // Deferred into the open gang when there is enough ahead of this block to keep the queues busy meanwhile: a deep pipeline
         // (depth >= 4), the traffic known (not the first block), no more events than the PLL's pair, and at least a gang's worth of
         // blocks in flight in front of it whose tails are out.  Anything else goes at once, alone, behind whatever the gang holds.
         unsigned ahead = 0;
         for (unsigned k = 0; k < c->inflight; k++) ahead += c->slots[(c->tail + k) % (c->depth + 1)]->tail_launched ? 1u : 0u;
         const unsigned G = c->tail_gang;
-        if (G >= 2 && may_defer && c->depth >= 4 && !c->first_block && !c->debug_stop_after && tl <= 1 && ahead >= G) {
+        if (G >= 2 && may_defer && c->depth >= 4 && c->traffic.seen && !c->debug_stop_after && tl <= 1 && ahead >= G) {
             sl.tail_launched = false; sl.tail_st = nullptr;
             c->gang.push_back(&sl);
             return c->gang.size() >= G ? close_gang(c) : 0;
@@ -1314,38 +1273,33 @@ static int finish_decode(fxrx_ctx_s *c, Slot &sl)
     // frames the batch path handed back: how many (the block is done: a plain copy)
     auto fetch_fb = [&]() -> int { uint32_t nfb = 0; HIP_OK(hipMemcpy(&nfb, &hdr_pay->n_vb_fallback, sizeof nfb, hipMemcpyDeviceToHost)); sl.h_hdr.p->n_vb_fallback = nfb; sl.h_hdr.p->vb_ticket = 0; return 0; };
     if (sl.vb_blk && sl.h_hdr.p->vb_ticket && fetch_fb()) return FXRX_ERR_HIP;
-    const FxBlockHdr &h = *sl.h_hdr.p;
-    const bool more_plain = h.n_dec_plain > sl.dec_launched, more_rs = h.n_dec_rs > 0 && sl.rs_launched == 0;   // (the Reed-Solomon instance strides: any launch covers all)
-    const bool no_trellis = sl.vb_blk && sl.vb_fin_launched == 0;              // (left out of the chain: see fxrx_ctx_s.vb_early_tail)
-    const bool more_frames = h.n_dec_batch > sl.vb_pre_launched, more_items = !no_trellis && h.n_vb_items > sl.vb_items_launched;
-    const bool more_batch = more_frames || more_items;
-    // fx_vbpre_kernel met a frame that is not clean and the trellis kernels were not launched: they run now, over all items (clean
+    FxBlockHdr h = *sl.h_hdr.p; h.vb_dirty = *(volatile const uint32_t *)&sl.h_hdr.p->vb_dirty;
+    TailPlan &p = sl.tail;
+    const LateWork w = late_work(p, h, sl.vb_blk);
+    if (!w.any()) return 0;
+    HIP_OK(launch_decoders(c, sl, sl.st, p.plain, w.more_plain ? h.n_dec_plain - p.plain : 0u, w.more_rs ? h.n_dec_rs : 0u));
+    // late_trellis: fx_vbpre_kernel met a frame that is not clean and the trellis kernels were not launched: they run now, over all items (clean
     // frames' items are off, their waves of the back part leave at once); fx_vbpre_kernel itself is done and is not needed again
-    const bool late_trellis = no_trellis && !more_batch && *(volatile const uint32_t *)&sl.h_hdr.p->vb_dirty != 0u;
-    const bool more_fb = sl.vb_blk && h.n_vb_fallback > sl.fb_launched;
-    if (!more_plain && !more_rs && !more_batch && !more_fb && !late_trellis) return 0;
-    const bool why[6] = { more_plain, more_rs, more_frames, more_items, more_fb, late_trellis };      // fxrx_debug_late_stats
-    HIP_OK(launch_decoders(c, sl, sl.st, sl.dec_launched, more_plain ? h.n_dec_plain - sl.dec_launched : 0u, more_rs ? h.n_dec_rs : 0u));
-    if (more_batch || late_trellis) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
+    if (w.more_batch() || w.late_trellis) {       // (all parts again, for all of the path's frames: they are idempotent -- but for the fallback list, which starts over)
         HIP_OK(hipMemsetAsync(&hdr_pay->n_vb_fallback, 0, sizeof(uint32_t), sl.st));
-        if (more_batch) {
+        if (w.more_batch()) {
             FxVbpreGang g; g.n = 1; g.m[0] = vbpre_member(sl, 0u, h.n_dec_batch);
-            HIP_OK(fx_launch_vbpre(&g, sl.st, c->d_tables, c->vb_clean ? 1 : 0, sl.vb_early ? 1 : 0));
+            HIP_OK(fx_launch_vbpre(&g, sl.st, c->d_tables, c->vb_clean ? 1 : 0, p.vb_early ? 1 : 0));
         }
         HIP_OK(launch_trellis(c, sl, sl.st, h.n_vb_items, 1, 1, h.n_dec_batch, kFallbackWaves));
-        sl.vb_pre_launched = sl.vb_fin_launched = h.n_dec_batch; sl.vb_items_launched = h.n_vb_items; sl.fb_launched = kFallbackWaves;
+        p.vb_pre = p.vb_fin = h.n_dec_batch; p.vb_items = h.n_vb_items; p.fb = kFallbackWaves;
         HIP_OK(hipStreamSynchronize(sl.st));
         if (fetch_fb()) return FXRX_ERR_HIP;
     }
     const uint32_t n_fb = *(volatile const uint32_t *)&sl.h_hdr.p->n_vb_fallback;
-    if (sl.vb_blk && n_fb > sl.fb_launched) {
-        HIP_OK(launch_paydec(c, sl, sl.st, kDecFallback, sl.fb_launched, n_fb - sl.fb_launched, c->dec_waves));
-        sl.fb_launched = n_fb;
+    if (sl.vb_blk && n_fb > p.fb) {
+        HIP_OK(launch_paydec(c, sl, sl.st, kDecFallback, p.fb, n_fb - p.fb, c->dec_waves));
+        p.fb = n_fb;
     }
     HIP_OK(hipStreamSynchronize(sl.st));
-    sl.dec_launched = std::max(sl.dec_launched, h.n_dec_plain); if (more_rs) sl.rs_launched = h.n_dec_rs;
+    p.plain = std::max(p.plain, h.n_dec_plain); if (w.more_rs) p.rs = h.n_dec_rs;
     c->late_decodes++;
-    for (int i = 0; i < 6; i++) c->late_reason[i] += why[i] ? 1u : 0u;
+    w.count(c->late_reason);
     return 0;
 }
 
@@ -1569,13 +1523,8 @@ static int collect_block(fxrx_ctx_s *c)
         if (!S.fresh_start && S.total >= end_total)
             S.carry_bound = std::min<int64_t>(S.carry_bound, std::min<int64_t>(S.carry_cap, hs[s].carry_len + (S.total - end_total)));
     }
-    { uint64_t tot = 0; for (unsigned s = 0; s < NS; s++) tot += sl.n[s]; c->samples_hint = tot; }
     sl.ps_taken += h.ps_taken; sl.ps_fallback += h.ps_fallback;
-    c->frames_hint = h.n_frames; c->plain_hint = h.n_dec_plain; c->batch_hint = h.n_dec_batch; c->vb_items_hint = h.n_vb_items;
-    if (sl.vb_early && h.n_dec_batch > vb_clean) c->trellis_left = kTrellisHold;     // frames that were not clean: the trellis kernels stay in the chain for a while
-    c->fb_hint = h.n_vb_fallback; c->vbfix_hint = h.n_vb_fallback + vb_rep; c->mf_items_hint = h.n_mfblk; c->vb_want_hint = h.vb_want; c->vb_steps_hint = (uint64_t)h.vb_want * (h.vb_blk ? h.vb_blk : 1u); c->first_block = false;
-    c->rs_hint = h.n_dec_rs ? h.n_dec_rs : c->rs_hint - std::min<uint64_t>(c->rs_hint, std::max<uint64_t>(1, c->rs_hint / 8));   // (fades out, to zero, over a few dozen blocks without such frames)
-    if (h.verify_hops) c->verify_per = (uint32_t)std::min<uint64_t>(16, std::max<uint64_t>(1, ((uint64_t)h.verify_hops + 4ull * c->n_cus - 1) / (4ull * c->n_cus)));
+    { uint64_t tot = 0; for (unsigned s = 0; s < NS; s++) tot += sl.n[s]; c->traffic.observe(h, vb_rep, vb_clean, sl.tail.vb_early, tot, c->n_cus); }
     fxrx_timing &t = sl.timing;
     float ms = 0;
     if (sl.timing_level >= 2) {
