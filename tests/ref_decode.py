@@ -500,11 +500,13 @@ _C0 = 2 * _OUT[0][_S] + _OUT[1][_S]                 # the branch p0 -> s holds r
 _C1 = 2 * _OUT[0][_S | 64] + _OUT[1][_S | 64]       # the branch p1 -> s holds register s | 64
 
 
-def viterbi(fs, vals, dec_len, vmax):
+def viterbi(fs, vals, dec_len, vmax, spread=None):
     """Maximum-likelihood decoding of F frames of equal length at once.  vals: (F, coded bits) in [0, vmax] (hard: 0/1 with
     vmax 1; soft: 0..255 with vmax 255); expecting bit e costs e ? vmax - v : v, punctured positions cost 0.  int64 path
     metrics without normalisation; start in state 0, traceback from state 0 after 8 dec_len + 6 steps.  A tie between the two
-    branches into a state goes to the predecessor whose MSB is 0.  Returns (messages (F, dec_len) uint8, final metrics (F,))."""
+    branches into a state goes to the predecessor whose MSB is 0.  Returns (messages (F, dec_len) uint8, final metrics (F,)).
+    spread (a list) gets max(pm) - min(pm) of frame 0 after every step (meaningless before step 6: states not yet reached
+    from the start state hold 2^40)."""
     vals = np.atleast_2d(np.asarray(vals, np.int64))
     F, n = vals.shape[0], 8 * dec_len + 6
     mask = _conv_mask(fs, n)
@@ -531,6 +533,8 @@ def viterbi(fs, vals, dec_len, vmax):
             d = m1 < m0
             pm = np.where(d, m1, m0)
             dec[t0 + t] = d
+            if spread is not None:
+                spread.append(int(pm[0].max() - pm[0].min()))
     bits = np.zeros((F, n), np.uint8)
     s = np.zeros(F, np.int64)
     fr = np.arange(F)
