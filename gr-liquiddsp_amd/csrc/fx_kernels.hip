@@ -13,7 +13,8 @@
 //   fx_seekverify_kernel  the exact detector on every skipped hop (thousands of independent workgroups).
 //   fx_chainfast_kernel   stitches the segments' lists into the sequential machine's list; resume state, carried tail
 //                       (fx_chain_kernel: the full-size fallback that can walk by itself).
-//   fx_plan_kernel, fx_planlists_kernel   arena offsets, jobs, result records, work lists of the payload stage.
+//   fx_plan_kernel, fx_planlists_kernel   arena offsets, jobs, result records, work lists of the payload stage
+//                       (fx_planfused_kernel: the same by one workgroup, in LDS, when one workgroup plans the block).
 //   fx_paymf_kernel     per frame, data parallel: closed-form NCO mix (32-bit phase) + fixed-branch
 //                       polyphase matched filter + decimate-by-2 over the payload span.
 //   fx_paypll_kernel    one lane per frame: the decision-directed payload PLL (the only true
@@ -2157,6 +2158,21 @@ __device__ __forceinline__ uint32_t wave_agg_add(uint32_t *counters, uint32_t ke
 struct PlanFrame {                      // what both passes of fx_plan_kernel derive from a chain frame
     const FxFrame *fp; uint32_t sidx, bps, k, l0, l1, nblk, vnb; bool valid, batch;
 };
+// the arena sizes v[] of a frame with a valid header, and what its job says about its codes
+__device__ __forceinline__ void plan_sizes(PlanFrame &f, uint32_t nsym, uint32_t plen, uint32_t ms, uint32_t check, uint32_t fec0, uint32_t fec1, uint32_t vb_blk, uint32_t (&v)[PLAN_NV])
+{
+    f.bps = modem_bps(ms);
+    f.k = plen + crc_len(check); f.l0 = fec_enc_len(fec0, f.k); f.l1 = fec_enc_len(fec1, f.l0);
+    f.nblk = (nsym + 1023u) / 1024u;
+    v[0] = (nsym + 7u) & ~7u;                                               // 8-symbol granules: 64-byte block I/O in the PLL kernel
+    v[1] = (max(f.l1, f.k) + 8u + 15u) & ~15u;
+    v[2] = ((8u * max(f.l0, f.k) + 6u + 63u) & ~63u) + 64u;                  // whole 64-step chunks, lane-major
+    v[3] = (plen + 15u) & ~15u;
+    v[4] = f.nblk; v[5] = 1u;
+    // batch Viterbi path: hard decisions, fec0 a K = 7 convolutional code, fec1 neither convolutional nor Reed-Solomon
+    f.batch = vb_blk && conv_p(fec0) && !conv_p(fec1) && fec1 != FX_FEC_RS_M8;
+    if (f.batch) { f.vnb = (8u * f.k + 6u + vb_blk - 1u) / vb_blk; v[6] = f.vnb; }
+}
 __device__ __forceinline__ PlanFrame plan_frame(uint32_t g, bool live, const FxStreamDesc *streams, uint32_t nstreams, const uint32_t *stream_base, const FxFrame *chain,
                                                 uint32_t detect, uint32_t vb_blk, uint32_t (&v)[PLAN_NV])
 {
@@ -2170,20 +2186,7 @@ __device__ __forceinline__ PlanFrame plan_frame(uint32_t g, bool live, const FxS
     const FxFrame *fp = chain + streams[lo].chain_base + (g - stream_base[lo]);
     f.fp = fp;
     f.valid = !detect && (fp->flags & FX_FLAG_HEADER_VALID);
-    if (f.valid) {
-        const uint32_t nsym = fp->pay_sym_len, plen = fp->pay_len;
-        f.bps = modem_bps(fp->ms);
-        f.k = plen + crc_len(fp->check); f.l0 = fec_enc_len(fp->fec0, f.k); f.l1 = fec_enc_len(fp->fec1, f.l0);
-        f.nblk = (nsym + 1023u) / 1024u;
-        v[0] = (nsym + 7u) & ~7u;                                           // 8-symbol granules: 64-byte block I/O in the PLL kernel
-        v[1] = (max(f.l1, f.k) + 8u + 15u) & ~15u;
-        v[2] = ((8u * max(f.l0, f.k) + 6u + 63u) & ~63u) + 64u;              // whole 64-step chunks, lane-major
-        v[3] = (plen + 15u) & ~15u;
-        v[4] = f.nblk; v[5] = 1u;
-        // batch Viterbi path: hard decisions, fec0 a K = 7 convolutional code, fec1 neither convolutional nor Reed-Solomon
-        f.batch = vb_blk && conv_p(fp->fec0) && !conv_p(fp->fec1) && fp->fec1 != FX_FEC_RS_M8;
-        if (f.batch) { f.vnb = (8u * f.k + 6u + vb_blk - 1u) / vb_blk; v[6] = f.vnb; }
-    }
+    if (f.valid) plan_sizes(f, fp->pay_sym_len, fp->pay_len, fp->ms, fp->check, fp->fec0, fp->fec1, vb_blk, v);
     return f;
 }
 // the frames a workgroup of a plan kernel handles: [g0, g1), whole chunks of PLAN_THREADS
@@ -2210,14 +2213,10 @@ __device__ __forceinline__ uint32_t plan_stream_bases(const uint32_t *chain_coun
     return run;
 }
 
-// What the list pass needs of a frame's job, kept in LDS by the one-workgroup kernel for the first PLAN_KEEP chunks (2048 frames:
-// what one workgroup is given) instead of being read back from pjobs: x = vb_nblk | valid << 16, y = ms, z = fec0, w = fec1 (32 KB of LDS, in one workgroup).
-#define PLAN_KEEP 8
-
-// the body of fx_plan_kernel (keep: nullptr, or PLAN_KEEP * PLAN_THREADS LDS slots that receive those fields of the range's first frames)
+// the body of fx_plan_kernel
 __device__ __forceinline__ void plan_jobs_body(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
                                                const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0,
-                                               uint32_t mf_cap, uint32_t vb_cap, uint32_t *pw, uint32_t (*ws)[PLAN_NV], uint32_t *base_s, uint4 *keep)
+                                               uint32_t mf_cap, uint32_t vb_cap, uint32_t *pw, uint32_t (*ws)[PLAN_NV], uint32_t *base_s)
 {
     // vb_blk: trellis steps per block of the batch Viterbi path (0: path off, e.g. soft decisions)
     const int tid = threadIdx.x;
@@ -2278,7 +2277,6 @@ __device__ __forceinline__ void plan_jobs_body(const FxStreamDesc *streams, uint
             j.byte_off = byte_off; j.dw_off = dw_off; j.out_off = out_off; j.pad_ = f.valid ? 1u : 0u;
             j.eq = eq; j.chain_idx = (uint32_t)(fp - chain); j.vb_off = 0; j.vb_nblk = (uint16_t)f.vnb; j.vb_clean = 0;
             pjobs[g] = j;
-            if (keep && c0 - g0 < PLAN_KEEP * PLAN_THREADS) keep[c0 - g0 + tid] = make_uint4((uint32_t)j.vb_nblk | (f.valid ? 0x10000u : 0u), j.ms, j.fec0, j.fec1);
             // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
             union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
             u.r.start = sd.abs_base + fp->start; u.r.stream = f.sidx; u.r.offset = fp->offset;
@@ -2316,15 +2314,14 @@ void fx_plan_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t det
 {
     __shared__ uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
     __shared__ uint32_t base_s[PLAN_NV];
-    plan_jobs_body(streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0, mf_cap, vb_cap, pw, ws, base_s, nullptr);
+    plan_jobs_body(streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0, mf_cap, vb_cap, pw, ws, base_s);
 }
 
 struct PlanListsShared { FxBlockHdr h; uint32_t cls_base[FX_PLL_CLASSES + 1], vbc_base[8], last; };
-// the body of fx_planlists_kernel (keep: nullptr, or what plan_jobs_body left there in the same workgroup).  The counts were added up with
-// device-scope atomics; they are read the same way, so that the one-workgroup kernel sees them without a kernel boundary in between.
+// the body of fx_planlists_kernel.  The counts were added up with device-scope atomics; they are read the same way.
 __device__ __forceinline__ void plan_lists_body(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_base, FxPayJob *pjobs, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
                                                 uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw,
-                                                PlanListsShared &sh, const uint4 *keep)
+                                                PlanListsShared &sh)
 {
     uint32_t (&cls_base)[FX_PLL_CLASSES + 1] = sh.cls_base; uint32_t (&vbc_base)[8] = sh.vbc_base; uint32_t &last = sh.last;
     const int tid = threadIdx.x;
@@ -2343,10 +2340,7 @@ __device__ __forceinline__ void plan_lists_body(uint32_t nstreams, uint32_t vb_b
         const uint32_t g = c0 + tid;
         const bool live = g < g1;
         uint32_t ms = 0, fec0 = 0, fec1 = 0, vnb = 0; bool val = false;
-        if (live && keep && c0 - g0 < PLAN_KEEP * PLAN_THREADS) {
-            const uint4 kp = keep[c0 - g0 + tid];
-            val = (kp.x >> 16) != 0; vnb = kp.x & 0xffffu; ms = kp.y; fec0 = kp.z; fec1 = kp.w;
-        } else if (live) { const FxPayJob &j = pjobs[g]; val = j.pad_ != 0; ms = j.ms; fec0 = j.fec0; fec1 = j.fec1; vnb = j.vb_nblk; }
+        if (live) { const FxPayJob &j = pjobs[g]; val = j.pad_ != 0; ms = j.ms; fec0 = j.fec0; fec1 = j.fec1; vnb = j.vb_nblk; }
         const unsigned c = pll_class(ms);
         const uint32_t pp = cls_base[c] + wave_agg_add(pw + PW_CLS_FILL, c, 1u, val);
         if (val && pp < list_cap) pll_list[pp] = g;
@@ -2407,25 +2401,257 @@ void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_ba
                          uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw)
 {
     __shared__ PlanListsShared sh;
-    plan_lists_body(nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, pw, sh, nullptr);
+    plan_lists_body(nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, pw, sh);
 }
 
-// Both passes in ONE workgroup (launched as a grid of one: the usual case, a block of up to ~2048 frames): the grid-wide counts the
-// list pass waits for are this workgroup's own, so a barrier stands where the kernel boundary was.  With blocks in flight on few
-// hardware queues a launch costs its duration plus a gap, and these two are latency-bound single workgroups.
-// Workgroup 0 has nothing to look back at; its flag and inclusive prefix are still written (the header is built from them).
-extern "C" __global__ __launch_bounds__(PLAN_THREADS)
-void fx_planfused_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain, const uint32_t *chain_count,
-                         uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
-                         uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw)
+// ---- the plan stage of a block that ONE workgroup plans (launched as a grid of one: the usual case, a block of up to ~2048 frames).
+// What the pair does across workgroups with global counters, look-back flags and a kernel boundary is this workgroup's own here, so it
+// lives in LDS and registers, and the kernel never touches the workspace (it finds and leaves it zero, as the pair needs it):
+//   tile     PLAN_KEEP x PLAN_THREADS = 2048 frames; a thread owns `per` CONSECUTIVE frames of it (per = frames of the tile / 256, rounded up)
+//   sizes    the seven words of every frame of the thread that decide its sizes are loaded in one go (all loads in flight, one round trip),
+//            the thread adds its frames' seven sizes up, ONE workgroup scan runs over the 256 partial sums; offsets are running sums from there
+//   counts   frames per modulation class / decode list, trellis items per code class: LDS atomics.  The class bases need the counts of all
+//            frames, so a block of more than one tile gets a counting sweep first (the only case that reads the size words twice more)
+//   jobs     frame by frame in the thread: the rest of the frame record is read (its lines are the ones the size words came from), job and
+//            host record go out, list slots come from LDS cursors (any order within a class, as with the pair's atomics), and the frame's
+//            trellis / matched-filter runs are noted in LDS: keep[] = (first trellis item, trellis blocks, first filter item, filter blocks)
+//   items    16 lanes per frame write those runs, consecutive lanes consecutive slots
+//   header   read a word per thread at the start, filled from LDS, mirrored and zeroed a word per thread
+// The arena offsets, the matched-filter item order and the frames demoted at the end of the trellis arena are the pair's: all three depend
+// only on prefix sums in frame order.
+#define PLAN_KEEP 8
+#define PLAN_LDS_STREAMS 256            // stream bases of up to this many streams are searched in LDS (more: in stream_base, as the pair does)
+enum { PO_CLS = 0, PO_DEC = FX_PLL_CLASSES, PO_VBC = FX_PLL_CLASSES + 4, PO_N = FX_PLL_CLASSES + 12 };
+struct PlanOneShared {
+    FxBlockHdr h;
+    uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
+    uint32_t cnt[PO_N], fill[PO_N];     // frames (trellis items) per class, and the cursors that hand the slots out
+    uint32_t cls_base[FX_PLL_CLASSES + 1], vbc_base[8];
+    uint32_t sbase[PLAN_LDS_STREAMS + 1], cbase[PLAN_LDS_STREAMS];   // frames before each stream / its region of the chain table
+};
+// chain slot of frame g (stream order, then position) and its stream
+__device__ __forceinline__ uint32_t plan_one_slot(uint32_t g, const FxStreamDesc *streams, uint32_t nstreams, const uint32_t *stream_base, const PlanOneShared &sh, uint32_t &sidx)
 {
-    __shared__ uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
-    __shared__ uint32_t base_s[PLAN_NV];
-    __shared__ PlanListsShared sh;
+    uint32_t lo = 0, hi = nstreams;                                          // base[lo] <= g < base[hi]
+    if (nstreams <= PLAN_LDS_STREAMS) {
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (sh.sbase[mid] <= g) lo = mid; else hi = mid; }
+        sidx = lo;
+        return sh.cbase[lo] + (g - sh.sbase[lo]);
+    }
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (stream_base[mid] <= g) lo = mid; else hi = mid; }
+    sidx = lo;
+    return streams[lo].chain_base + (g - stream_base[lo]);
+}
+
+extern "C" __global__ __launch_bounds__(PLAN_THREADS)
+void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *__restrict__ chain,
+                         const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *__restrict__ pjobs, FxOutRec *__restrict__ recs, uint32_t *mf_job, uint32_t *mf_c0,
+                         uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
+                         FxBlockHdr *hdr_host, uint32_t *pw)
+{
+    __shared__ PlanOneShared sh;
     __shared__ uint4 keep[PLAN_KEEP * PLAN_THREADS];
-    plan_jobs_body(streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0, mf_cap, vb_cap, pw, ws, base_s, keep);
+    constexpr uint32_t TILE = PLAN_KEEP * PLAN_THREADS;
+    constexpr int HW = (int)(sizeof(FxBlockHdr) / 4);
+    const uint32_t tid = threadIdx.x;
+    (void)pw;
+    // diagnostic builds: thread 0's shader clocks per step, summed over tiles, in the header's free stamp words -- [1] header read, stream
+    // bases, sizes, scan, counts, class bases | [2] jobs and records | [6] item runs, padding | [7] the fence in front of the header
+#ifdef FX_STAMPS
+    unsigned long long tk_ = __builtin_readcyclecounter(); uint32_t st1_ = 0, st2_ = 0, st6_ = 0, st7_ = 0;
+#define PLAN_TICK(acc) do { const unsigned long long t_ = __builtin_readcyclecounter(); acc += (uint32_t)(t_ - tk_); tk_ = t_; } while (0)
+#else
+#define PLAN_TICK(acc) do { } while (0)
+#endif
+    // the block's walk-phase header (complete: its writers ran before this kernel), a word per thread; counters and cursors
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(hdr); uint32_t *dst = reinterpret_cast<uint32_t *>(&sh.h);
+        for (int i = (int)tid; i < HW; i += PLAN_THREADS) dst[i] = src[i];
+        if (tid < PO_N) { sh.cnt[tid] = 0u; sh.fill[tid] = 0u; }
+        if (tid <= FX_PLL_CLASSES) sh.cls_base[tid] = 0u;
+        if (tid < 8) sh.vbc_base[tid] = 0u;
+    }
+    // frames before each stream (one stream, the usual case: {0, its count}, no scan)
+    uint32_t N;
+    if (nstreams <= PLAN_LDS_STREAMS) {
+        uint32_t v[PLAN_NV] = { tid < nstreams ? chain_count[tid] : 0u, 0, 0, 0, 0, 0, 0 }, tot[PLAN_NV];
+        if (nstreams > 1) plan_scan(v, tot, sh.ws); else { tot[0] = v[0]; v[0] = 0u; }
+        if (tid < nstreams) { sh.sbase[tid] = v[0]; stream_base[tid] = v[0]; sh.cbase[tid] = streams[tid].chain_base; }
+        if (tid == 0) { sh.sbase[nstreams] = tot[0]; stream_base[nstreams] = tot[0]; }
+        __syncthreads();
+        N = sh.sbase[nstreams];
+    } else N = plan_stream_bases(chain_count, nstreams, stream_base, sh.ws);
+
+    uint32_t run[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };                         // totals of the tiles done (after the last one: of the block)
+    for (int pass = N > TILE ? 0 : 1; pass < 2; pass++) {                    // pass 0: the counting sweep of a block of several tiles
+#pragma unroll
+        for (int q = 0; q < PLAN_NV; q++) run[q] = 0u;
+        for (uint32_t t0 = 0; t0 < N; t0 += TILE) {
+            const uint32_t nt = min(TILE, N - t0), t1 = t0 + nt, per = (nt + PLAN_THREADS - 1) / PLAN_THREADS, f0 = t0 + tid * per;
+            // 1. sizes of my frames: every load is issued before any is used (frames that are not mine read the tile's first one)
+            uint32_t st[PLAN_NV], tot[PLAN_NV];
+            uint32_t info[PLAN_KEEP];                                        // vnb | class << 16 | Reed-Solomon << 20 | code class << 21 | valid << 24 | batch << 25
+            {
+                uint32_t w[PLAN_KEEP][7];
+#pragma unroll
+                for (int i = 0; i < PLAN_KEEP; i++) {
+                    const bool live = (uint32_t)i < per && f0 + i < t1;
+                    uint32_t sidx;
+                    const FxFrame *fp = chain + plan_one_slot(live ? f0 + i : t0, streams, nstreams, stream_base, sh, sidx);
+                    w[i][0] = fp->flags; w[i][1] = fp->pay_sym_len; w[i][2] = fp->pay_len; w[i][3] = fp->ms; w[i][4] = fp->check; w[i][5] = fp->fec0; w[i][6] = fp->fec1;
+                }
+#pragma unroll
+                for (int q = 0; q < PLAN_NV; q++) st[q] = 0u;
+#pragma unroll
+                for (int i = 0; i < PLAN_KEEP; i++) {
+                    const bool live = (uint32_t)i < per && f0 + i < t1;
+                    PlanFrame f; f.bps = f.k = f.l0 = f.l1 = f.nblk = f.vnb = 0; f.batch = false;
+                    f.valid = live && !detect && (w[i][0] & FX_FLAG_HEADER_VALID);
+                    uint32_t v[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };
+                    info[i] = 0u;
+                    if (f.valid) {
+                        plan_sizes(f, w[i][1], w[i][2], w[i][3], w[i][4], w[i][5], w[i][6], vb_blk, v);
+                        info[i] = f.vnb | pll_class(w[i][3]) << 16 | ((w[i][5] == FX_FEC_RS_M8 || w[i][6] == FX_FEC_RS_M8) ? 1u << 20 : 0u) |
+                                  (f.batch ? ((uint32_t)conv_p(w[i][5]) - 1u) << 21 | 1u << 25 : 0u) | 1u << 24;
+                    }
+#pragma unroll
+                    for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
+                }
+            }
+            // 2. one scan over the 256 partial sums: st[] = what lies before my first frame
+            plan_scan(st, tot, sh.ws);
+#pragma unroll
+            for (int q = 0; q < PLAN_NV; q++) st[q] += run[q];
+            // 3. counts per list, where no counting sweep has done it (work items beyond the arena, padding of the seven code classes included:
+            // the frame goes the wave-per-frame way, and so does every frame behind it)
+            if (pass == 0 || N <= TILE) {
+                uint32_t vb = st[6];
+#pragma unroll
+                for (int i = 0; i < PLAN_KEEP; i++) {
+                    const uint32_t vnb = info[i] & 0xffffu;
+                    bool batch = (info[i] >> 25) & 1u;
+                    if (batch && (uint64_t)vb + vnb + 7u * 128u > vb_cap) batch = false;
+                    vb += vnb;
+                    if ((info[i] >> 24) & 1u) {
+                        atomicAdd(&sh.cnt[PO_CLS + ((info[i] >> 16) & 15u)], 1u);
+                        atomicAdd(&sh.cnt[PO_DEC + (batch ? 2u : (info[i] >> 20) & 1u)], 1u);
+                        if (batch) atomicAdd(&sh.cnt[PO_VBC + ((info[i] >> 21) & 7u)], vnb);
+                    }
+                }
+            }
+            if (pass == 0) {
+#pragma unroll
+                for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
+                continue;
+            }
+            if (t0 == 0) {                                                   // the counts are complete: first slot of every class
+                __syncthreads();
+                if (tid == 0) {
+                    uint32_t b = 0;
+                    for (int c = 0; c < FX_PLL_CLASSES; c++) { sh.cls_base[c] = b; b += (sh.cnt[PO_CLS + c] + 63u) & ~63u; }     // whole waves
+                    sh.cls_base[FX_PLL_CLASSES] = b;
+                    uint32_t vb = 0;
+                    for (int c = 0; c < 7; c++) { sh.vbc_base[c] = vb; vb += (sh.cnt[PO_VBC + c] + 127u) & ~127u; }              // whole forward-pass waves: 128 slots
+                    sh.vbc_base[7] = vb;
+                }
+                __syncthreads();
+            }
+            PLAN_TICK(st1_);
+            // 4. jobs, records, list slots of my frames, one after the other
+            uint32_t sym_run = st[0], byte_run = st[1], dw_run = st[2], out_run = st[3], mf_run = st[4], vb_run = st[6];
+            for (uint32_t i = 0; i < per && f0 + i < t1; i++) {
+                const uint32_t g = f0 + i;
+                uint32_t sidx;
+                const uint32_t slot = plan_one_slot(g, streams, nstreams, stream_base, sh, sidx);
+                const FxFrame *__restrict__ fp = chain + slot;
+                const uint32_t flags = fp->flags, nsym = fp->pay_sym_len, plen = fp->pay_len, ms = fp->ms, check = fp->check, fec0 = fp->fec0, fec1 = fp->fec1;
+                PlanFrame f; f.bps = f.k = f.l0 = f.l1 = f.nblk = f.vnb = 0; f.batch = false;
+                f.valid = !detect && (flags & FX_FLAG_HEADER_VALID);
+                uint32_t v[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };
+                if (f.valid) plan_sizes(f, nsym, plen, ms, check, fec0, fec1, vb_blk, v);
+                if (f.batch && (uint64_t)vb_run + f.vnb + 7u * 128u > vb_cap) { f.batch = false; f.vnb = 0; }
+                const uint32_t sym_off = sym_run, byte_off = byte_run, dw_off = dw_run, out_off = out_run, mf_off = mf_run;
+                sym_run += v[0]; byte_run += v[1]; dw_run += v[2]; out_run += v[3]; mf_run += v[4]; vb_run += v[6];
+                uint32_t at = 0;
+                if (f.valid) {
+                    const unsigned c = pll_class(ms);
+                    const uint32_t pp = sh.cls_base[c] + atomicAdd(&sh.fill[PO_CLS + c], 1u);
+                    if (pp < list_cap) pll_list[pp] = g;
+                    const uint32_t rs = f.batch ? 2u : ((fec0 == FX_FEC_RS_M8 || fec1 == FX_FEC_RS_M8) ? 1u : 0u);
+                    const uint32_t dp = atomicAdd(&sh.fill[PO_DEC + rs], 1u);
+                    if (dp < list_cap) dec_list[(size_t)rs * list_cap + dp] = g;
+                    if (f.batch) { const uint32_t vc = (uint32_t)conv_p(fec0) - 1u; at = sh.vbc_base[vc] + atomicAdd(&sh.fill[PO_VBC + vc], f.vnb); }   // its trellis blocks, among those of the same code
+                }
+                keep[g - t0] = make_uint4(at, f.vnb, mf_off, f.nblk);
+                const FxStreamDesc &sd = streams[sidx];
+                FxPayJob j;
+                j.x = sd.x; j.xa_end = sd.xa_end; j.start = fp->start; j.mix_th = fp->mix_th; j.mix_dl = fp->mix_dl; j.mf_scale = fp->mf_scale;
+                j.pfb = fp->pfb; j.mfc0 = fp->mfc0; j.pll_th = fp->pll_th; j.pll_f = fp->pll_f; j.ms = ms; j.bps = f.bps;
+                j.nsym = f.valid ? nsym : 0u; j.sym_off = sym_off;
+                j.pay_len = plen; j.check = check; j.fec0 = fec0; j.fec1 = fec1; j.k = f.k; j.l0 = f.l0; j.l1 = f.l1;
+                j.byte_off = byte_off; j.dw_off = dw_off; j.out_off = out_off; j.pad_ = f.valid ? 1u : 0u;
+                j.eq = eq; j.chain_idx = slot; j.vb_off = at; j.vb_nblk = (uint16_t)f.vnb; j.vb_clean = 0;
+                pjobs[g] = j;
+                // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
+                union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
+                u.r.start = sd.abs_base + fp->start; u.r.stream = sidx; u.r.offset = fp->offset;
+                u.r.rxy = fp->rxy; u.r.tau = fp->tau; u.r.gamma = fp->gamma; u.r.dphi = fp->dphi; u.r.phi = fp->phi; u.r.pfb = fp->pfb;
+                u.r.pilot_dphi = fp->pilot_dphi; u.r.pilot_phi = fp->pilot_phi; u.r.pilot_gain = fp->pilot_gain;
+                u.r.flags = flags & FX_FLAG_HEADER_VALID;
+                u.r.pay_len = f.valid ? plen : 0u; u.r.ms = ms; u.r.check = check; u.r.fec0 = fec0; u.r.fec1 = fec1;
+                u.r.nsym = f.valid ? nsym : 0u; u.r.bps = f.bps; u.r.sym_off = sym_off; u.r.out_off = out_off;
+                u.r.evm_sum = 0.0f; u.r.payload_valid = 0; u.r.status = 0;
+                const uint32_t *hw = reinterpret_cast<const uint32_t *>(fp->header); uint32_t *rw = reinterpret_cast<uint32_t *>(u.r.header);
+#pragma unroll
+                for (int k = 0; k < FX_HDR_DEC / 4; k++) rw[k] = hw[k];
+                u.r.byte_off = byte_off;
+                uint4 *dst = reinterpret_cast<uint4 *>(recs + g);
+#pragma unroll
+                for (int k = 0; k < (int)(sizeof(FxOutRec) / 16); k++) dst[k] = u.q[k];
+            }
+            __syncthreads();
+            PLAN_TICK(st2_);
+            // 5. the trellis and matched-filter runs of the tile's frames: 16 lanes per frame, consecutive lanes consecutive slots
+            for (uint32_t k = tid >> 4; k < nt; k += PLAN_THREADS / 16) {
+                const uint4 kp = keep[k];
+                const uint32_t g = t0 + k, sub = tid & 15u;
+                for (uint32_t b = sub; b < kp.y; b += 16u) if (kp.x + b < vb_cap) { vb_items[kp.x + b] = g; vb_items[vb_cap + kp.x + b] = b; }
+                for (uint32_t c = sub; c < kp.w; c += 16u) if (kp.z + c < mf_cap) { mf_job[kp.z + c] = g; mf_c0[kp.z + c] = c * 1024u; }
+            }
+#pragma unroll
+            for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
+            __syncthreads();                                                 // (keep[] belongs to the next tile from here)
+        }
+    }
+    // padding slots of every class
+    for (int c = 0; c < FX_PLL_CLASSES; c++)
+        for (uint32_t i = sh.cls_base[c] + sh.cnt[PO_CLS + c] + tid; i < sh.cls_base[c + 1] && i < list_cap; i += PLAN_THREADS) pll_list[i] = 0xFFFFFFFFu;
+    for (int c = 0; c < 7; c++)
+        for (uint32_t i = sh.vbc_base[c] + sh.cnt[PO_VBC + c] + tid; i < sh.vbc_base[c + 1] && i < vb_cap; i += PLAN_THREADS) vb_items[i] = 0xFFFFFFFFu;
+    // block header for the payload kernels and for the host (behind everything written above); the walk-phase header is zeroed for the
+    // slot's next block
+    PLAN_TICK(st6_);
     __threadfence(); __syncthreads();
-    plan_lists_body(nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, pw, sh, keep);
+    PLAN_TICK(st7_);
+    if (tid == 0) {
+        FxBlockHdr &h = sh.h;
+#ifdef FX_STAMPS
+        h.stamp[1] = st1_; h.stamp[2] = st2_; h.stamp[6] = st6_; h.stamp[7] = st7_;
+#endif
+        h.n_frames = N; h.n_pjobs = run[5]; h.n_mfblk = min(run[4], mf_cap);
+        h.n_dec_plain = sh.cnt[PO_DEC + 0]; h.n_dec_rs = sh.cnt[PO_DEC + 1]; h.n_dec_batch = sh.cnt[PO_DEC + 2];
+        h.n_vb_items = min(sh.vbc_base[7], vb_cap); h.vb_blk = vb_blk; h.vb_want = run[6] + 7u * 128u; h.n_vb_fallback = 0;
+        for (int c = 0; c < FX_PLL_CLASSES; c++) { h.pll_cnt[c] = sh.cnt[PO_CLS + c]; h.pll_base[c] = sh.cls_base[c]; }
+        h.pll_base[FX_PLL_CLASSES] = sh.cls_base[FX_PLL_CLASSES];
+        h.sym_total = run[0]; h.byte_total = run[1]; h.dw_total = run[2]; h.out_total = run[3];
+        h.done = 1;
+    }
+    __syncthreads();
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(&sh.h);
+        uint32_t *d0 = reinterpret_cast<uint32_t *>(hdr_pay), *d1 = reinterpret_cast<uint32_t *>(hdr_host), *z = reinterpret_cast<uint32_t *>(hdr);
+        for (int i = (int)tid; i < HW; i += PLAN_THREADS) { const uint32_t w = src[i]; d0[i] = w; d1[i] = w; z[i] = 0u; }
+    }
 }
 
 extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
