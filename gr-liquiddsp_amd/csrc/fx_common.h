@@ -343,3 +343,18 @@ struct FxVbpreMember {
     uint32_t first_wave, n_waves;        // the waves this member would have launched alone: blockIdx.x = 0 .. n_waves - 1 stands for job first_wave + blockIdx.x
 };
 struct FxVbpreGang { uint32_t n; FxVbpreMember m[FX_GANG_MAX]; };
+
+// ---- a block's plan stage (fx_launch_plan): what fx_planfused_kernel, or fx_plan_kernel and fx_planlists_kernel, work on.  Passed by value. ----
+struct FxPlanArgs {
+    const FxStreamDesc *streams; uint32_t nstreams;
+    uint32_t detect, eq;                 // 1: detector mode (no payload stage) / equaliser on
+    uint32_t vb_blk;                     // trellis steps per block of the batch Viterbi path (0: path off, e.g. soft decisions)
+    const FxFrame *chain; const uint32_t *chain_count;
+    uint32_t *stream_base;               // out: frames before each stream, [nstreams]: the block's
+    FxPayJob *pjobs; FxOutRec *recs;     // out: one per chain frame (recs: pinned host memory)
+    uint32_t *mf_job, *mf_c0, mf_cap;    // out: matched-filter items (frame, first symbol)
+    uint32_t *pll_list, *dec_list, list_cap;   // out: the PLL lists (one per modulation class) and the three decode lists, list_cap slots each
+    uint32_t *vb_items, vb_cap;          // out: batch-Viterbi work items (frame at [i], trellis block at [vb_cap + i])
+    FxBlockHdr *hdr, *hdr_pay, *hdr_host;   // the walk-phase header (zeroed again) / what the payload kernels read / the host's copy
+    uint32_t *ws;                        // fx_plan_ws_words() words, zero between blocks
+};

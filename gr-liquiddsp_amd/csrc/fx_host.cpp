@@ -966,9 +966,17 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
     if (chain_mode == kChainFast && chain_st && chain_st != st) HIP_OK(hipStreamWaitEvent(st, sl.ev[kEvChain], 0));   // back onto the block's own stream
     c->prev_chain = sl.ev[kEvChain];
     // (the plan kernels' workgroups take contiguous ranges of the chain's frames: about 2048 each, from the last block's count)
-    HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->traffic.frames / 2048 + 1), sl.streams(), NS, detect ? 1u : 0u, c->cfg.equalizer ? 1u : 0u, sl.vb_blk, sl.d_chain.p,
-                          sl.d_chain_count.p, sl.d_stream_base.p, sl.d_pjobs.p, sl.h_recs.p, sl.d_mf_job.p, sl.d_mf_c0.p, sl.mf_cap, sl.d_pll_list.p, sl.dec_list(kDecPlain), sl.list_cap(), sl.d_vb_items.p, sl.vb_cap,
-                          sl.hdr_walk(), sl.hdr_pay(), sl.h_hdr.p, sl.d_plan_ws.p, c->plan_fused ? 1 : 0));
+    {
+        FxPlanArgs a;
+        a.streams = sl.streams(); a.nstreams = NS; a.detect = detect ? 1u : 0u; a.eq = c->cfg.equalizer ? 1u : 0u; a.vb_blk = sl.vb_blk;
+        a.chain = sl.d_chain.p; a.chain_count = sl.d_chain_count.p; a.stream_base = sl.d_stream_base.p;
+        a.pjobs = sl.d_pjobs.p; a.recs = sl.h_recs.p;
+        a.mf_job = sl.d_mf_job.p; a.mf_c0 = sl.d_mf_c0.p; a.mf_cap = sl.mf_cap;
+        a.pll_list = sl.d_pll_list.p; a.dec_list = sl.dec_list(kDecPlain); a.list_cap = sl.list_cap();
+        a.vb_items = sl.d_vb_items.p; a.vb_cap = sl.vb_cap;
+        a.hdr = sl.hdr_walk(); a.hdr_pay = sl.hdr_pay(); a.hdr_host = sl.h_hdr.p; a.ws = sl.d_plan_ws.p;
+        HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->traffic.frames / 2048 + 1), c->plan_fused ? 1 : 0, a));
+    }
     const int tl = sl.timing_level;
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvPlan], st));
     if (c->debug_stop_after == 4) { c->carry_reader[b % 3] = nullptr; HIP_OK(hipEventRecord(sl.ev[kEvDone], st)); return 0; }

@@ -2078,6 +2078,8 @@ extern "C" hipError_t fx_launch_hdrdec(int soft, unsigned n, hipStream_t st, con
 // writes one FxOutRec per frame straight into pinned host memory and mirrors the block header there.
 #define PLAN_THREADS 256
 #define PLAN_NV 7
+// what a plan adds up in frame order: the offsets in the symbol, byte, decision-word and output arenas, matched-filter items, jobs, trellis items
+enum { PV_SYM = 0, PV_BYTE, PV_DW, PV_OUT, PV_MF, PV_JOB, PV_VB };
 
 __device__ __forceinline__ unsigned pll_class(unsigned ms)
 {
@@ -2111,10 +2113,7 @@ __device__ __forceinline__ void plan_scan(uint32_t (&v)[PLAN_NV], uint32_t (&tot
     }
 }
 
-// hdr: the block's walk-phase counters (zeroed again at the end, for the slot's next block); hdr_pay: what the payload kernels
-// read; hdr_host: the host's copy.
-//
-// Two kernels, each a handful of workgroups over contiguous ranges of the frames (one workgroup took 2 ms for the 38 k frames
+// (Arguments: FxPlanArgs, fx_common.h.)  Two kernels, each a handful of workgroups over contiguous ranges of the frames (one workgroup took 2 ms for the 38 k frames
 // and 317 k trellis work items of config 4):
 //   fx_plan_kernel       sizes -> arena offsets (prefix sums), jobs, records, matched-filter items, counts per list.  The
 //                        prefix across workgroups is a decoupled look-back: a workgroup publishes the totals of its range,
@@ -2155,38 +2154,149 @@ __device__ __forceinline__ uint32_t wave_agg_add(uint32_t *counters, uint32_t ke
     return result;
 }
 
-struct PlanFrame {                      // what both passes of fx_plan_kernel derive from a chain frame
-    const FxFrame *fp; uint32_t sidx, bps, k, l0, l1, nblk, vnb; bool valid, batch;
+// ---- what the pair and the one-workgroup kernel share: every layout rule once.  Their outputs are compared field for field. ----
+struct PlanWords { uint32_t flags, nsym, plen, ms, check, fec0, fec1; };   // the seven words of a chain frame that decide its sizes and its lists
+__device__ __forceinline__ PlanWords plan_words(const FxFrame *fp) { return { fp->flags, fp->pay_sym_len, fp->pay_len, fp->ms, fp->check, fp->fec0, fp->fec1 }; }
+struct PlanFrame {                      // what a plan kernel derives from them (plan_sizes), and where the frame is (its caller)
+    const FxFrame *fp = nullptr; uint32_t sidx = 0, bps = 0, k = 0, l0 = 0, l1 = 0, nblk = 0, vnb = 0; bool valid = false, batch = false;
 };
-// the arena sizes v[] of a frame with a valid header, and what its job says about its codes
-__device__ __forceinline__ void plan_sizes(PlanFrame &f, uint32_t nsym, uint32_t plen, uint32_t ms, uint32_t check, uint32_t fec0, uint32_t fec1, uint32_t vb_blk, uint32_t (&v)[PLAN_NV])
+// a frame's sizes v[] (PV_*; all zero without a valid header, in detector mode, or if not live) and what its job says about its codes
+__device__ __forceinline__ PlanFrame plan_sizes(const PlanWords &w, bool live, uint32_t detect, uint32_t vb_blk, uint32_t (&v)[PLAN_NV])
 {
-    f.bps = modem_bps(ms);
-    f.k = plen + crc_len(check); f.l0 = fec_enc_len(fec0, f.k); f.l1 = fec_enc_len(fec1, f.l0);
-    f.nblk = (nsym + 1023u) / 1024u;
-    v[0] = (nsym + 7u) & ~7u;                                               // 8-symbol granules: 64-byte block I/O in the PLL kernel
-    v[1] = (max(f.l1, f.k) + 8u + 15u) & ~15u;
-    v[2] = ((8u * max(f.l0, f.k) + 6u + 63u) & ~63u) + 64u;                  // whole 64-step chunks, lane-major
-    v[3] = (plen + 15u) & ~15u;
-    v[4] = f.nblk; v[5] = 1u;
-    // batch Viterbi path: hard decisions, fec0 a K = 7 convolutional code, fec1 neither convolutional nor Reed-Solomon
-    f.batch = vb_blk && conv_p(fec0) && !conv_p(fec1) && fec1 != FX_FEC_RS_M8;
-    if (f.batch) { f.vnb = (8u * f.k + 6u + vb_blk - 1u) / vb_blk; v[6] = f.vnb; }
-}
-__device__ __forceinline__ PlanFrame plan_frame(uint32_t g, bool live, const FxStreamDesc *streams, uint32_t nstreams, const uint32_t *stream_base, const FxFrame *chain,
-                                                uint32_t detect, uint32_t vb_blk, uint32_t (&v)[PLAN_NV])
-{
-    PlanFrame f; f.fp = chain; f.sidx = 0; f.bps = f.k = f.l0 = f.l1 = f.nblk = f.vnb = 0; f.valid = f.batch = false;
+    PlanFrame f;
 #pragma unroll
-    for (int q = 0; q < PLAN_NV; q++) v[q] = 0;
-    if (!live) return f;
-    uint32_t lo = 0, hi = nstreams;                                          // stream_base[lo] <= g < stream_base[hi]
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (stream_base[mid] <= g) lo = mid; else hi = mid; }
-    f.sidx = lo;
-    const FxFrame *fp = chain + streams[lo].chain_base + (g - stream_base[lo]);
-    f.fp = fp;
-    f.valid = !detect && (fp->flags & FX_FLAG_HEADER_VALID);
-    if (f.valid) plan_sizes(f, fp->pay_sym_len, fp->pay_len, fp->ms, fp->check, fp->fec0, fp->fec1, vb_blk, v);
+    for (int q = 0; q < PLAN_NV; q++) v[q] = 0u;
+    f.valid = live && !detect && (w.flags & FX_FLAG_HEADER_VALID);
+    if (!f.valid) return f;
+    f.bps = modem_bps(w.ms);
+    f.k = w.plen + crc_len(w.check); f.l0 = fec_enc_len(w.fec0, f.k); f.l1 = fec_enc_len(w.fec1, f.l0);
+    f.nblk = (w.nsym + 1023u) / 1024u;
+    v[PV_SYM] = (w.nsym + 7u) & ~7u;                                         // 8-symbol granules: 64-byte block I/O in the PLL kernel
+    v[PV_BYTE] = (max(f.l1, f.k) + 8u + 15u) & ~15u;
+    v[PV_DW] = ((8u * max(f.l0, f.k) + 6u + 63u) & ~63u) + 64u;              // whole 64-step chunks, lane-major
+    v[PV_OUT] = (w.plen + 15u) & ~15u;
+    v[PV_MF] = f.nblk; v[PV_JOB] = 1u;
+    // batch Viterbi path: hard decisions, fec0 a K = 7 convolutional code, fec1 neither convolutional nor Reed-Solomon
+    f.batch = vb_blk && conv_p(w.fec0) && !conv_p(w.fec1) && w.fec1 != FX_FEC_RS_M8;
+    if (f.batch) { f.vnb = (8u * f.k + 6u + vb_blk - 1u) / vb_blk; v[PV_VB] = f.vnb; }
+    return f;
+}
+// A batch frame whose trellis items (vnb of them, behind the vb_before of the frames in front of it) would pass the end of the arena, the
+// padding of the seven code classes included, goes the wave-per-frame way -- and so does every frame behind it.
+__device__ __forceinline__ bool plan_demote(uint32_t vb_before, uint32_t vnb, uint32_t vb_cap) { return (uint64_t)vb_before + vnb + 7u * 128u > vb_cap; }
+
+// the lists of a frame with a valid header: its PLL class, its decode list, and the code class its trellis items go with if it is a batch frame
+struct PlanKey {
+    uint32_t cls, rs, vc;
+    __device__ uint32_t dec(bool batch) const { return batch ? 2u : rs; }   // 0 plain, 1 with a Reed-Solomon stage, 2 batch Viterbi
+    __device__ uint32_t pack() const { return cls | rs << 4 | vc << 5; }    // (8 bits)
+    __device__ static PlanKey unpack(uint32_t p) { return { p & 15u, (p >> 4) & 1u, (p >> 5) & 7u }; }
+};
+__device__ __forceinline__ PlanKey plan_key(uint32_t ms, uint32_t fec0, uint32_t fec1)
+{
+    const uint32_t p = (uint32_t)conv_p(fec0);
+    return { pll_class(ms), (fec0 == FX_FEC_RS_M8 || fec1 == FX_FEC_RS_M8) ? 1u : 0u, p ? p - 1u : 0u };
+}
+
+// the stream of frame g: base[s] <= g < base[s + 1]
+__device__ __forceinline__ uint32_t plan_stream_of(const uint32_t *base, uint32_t nstreams, uint32_t g)
+{
+    uint32_t lo = 0, hi = nstreams;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (base[mid] <= g) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// One frame's job and host record: from its chain record, its stream, the size words (which the caller holds in registers: they are not
+// read again) and what plan_sizes made of them, the frame's offsets off[] (PV_*), its chain slot and the first of its trellis items.
+__device__ __forceinline__ void plan_emit(FxPayJob *__restrict__ job, FxOutRec *__restrict__ rec, const FxFrame *__restrict__ fp, const FxStreamDesc *__restrict__ sd,
+                                          const PlanWords &w, const PlanFrame &f, const uint32_t (&off)[PLAN_NV], uint32_t eq, uint32_t slot, uint32_t vb_off)
+{
+    FxPayJob j;
+    j.x = sd->x; j.xa_end = sd->xa_end; j.start = fp->start; j.mix_th = fp->mix_th; j.mix_dl = fp->mix_dl; j.mf_scale = fp->mf_scale;
+    j.pfb = fp->pfb; j.mfc0 = fp->mfc0; j.pll_th = fp->pll_th; j.pll_f = fp->pll_f; j.ms = w.ms; j.bps = f.bps;
+    j.nsym = f.valid ? w.nsym : 0u; j.sym_off = off[PV_SYM];
+    j.pay_len = w.plen; j.check = w.check; j.fec0 = w.fec0; j.fec1 = w.fec1; j.k = f.k; j.l0 = f.l0; j.l1 = f.l1;
+    j.byte_off = off[PV_BYTE]; j.dw_off = off[PV_DW]; j.out_off = off[PV_OUT]; j.pad_ = f.valid ? 1u : 0u;
+    j.eq = eq; j.chain_idx = slot; j.vb_off = vb_off; j.vb_nblk = (uint16_t)f.vnb; j.vb_clean = 0;
+    *job = j;
+    // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
+    union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
+    u.r.start = sd->abs_base + fp->start; u.r.stream = f.sidx; u.r.offset = fp->offset;
+    u.r.rxy = fp->rxy; u.r.tau = fp->tau; u.r.gamma = fp->gamma; u.r.dphi = fp->dphi; u.r.phi = fp->phi; u.r.pfb = fp->pfb;
+    u.r.pilot_dphi = fp->pilot_dphi; u.r.pilot_phi = fp->pilot_phi; u.r.pilot_gain = fp->pilot_gain;
+    u.r.flags = w.flags & FX_FLAG_HEADER_VALID;
+    u.r.pay_len = f.valid ? w.plen : 0u; u.r.ms = w.ms; u.r.check = w.check; u.r.fec0 = w.fec0; u.r.fec1 = w.fec1;
+    u.r.nsym = f.valid ? w.nsym : 0u; u.r.bps = f.bps; u.r.sym_off = off[PV_SYM]; u.r.out_off = off[PV_OUT];
+    u.r.evm_sum = 0.0f; u.r.payload_valid = 0; u.r.status = 0;
+    const uint32_t *hw = reinterpret_cast<const uint32_t *>(fp->header); uint32_t *rw = reinterpret_cast<uint32_t *>(u.r.header);
+#pragma unroll
+    for (int i = 0; i < FX_HDR_DEC / 4; i++) rw[i] = hw[i];
+    u.r.byte_off = off[PV_BYTE];
+    uint4 *dst = reinterpret_cast<uint4 *>(rec);
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(FxOutRec) / 16); i++) dst[i] = u.q[i];
+}
+
+// Where a path keeps its counts -- frames per modulation class and per decode list, trellis items per code class: the one-workgroup kernel in
+// LDS, the pair in the workspace (AGENT), where they were added up with device-scope atomics and are read the same way.
+template <bool AGENT> struct PlanCounts {
+    const uint32_t *cls_, *dec_, *vbc_;
+    __device__ __forceinline__ static uint32_t ld(const uint32_t *p)
+    {
+        if constexpr (AGENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else return *p;
+    }
+    __device__ __forceinline__ uint32_t cls(int c) const { return ld(cls_ + c); }
+    __device__ __forceinline__ uint32_t dec(int c) const { return ld(dec_ + c); }
+    __device__ __forceinline__ uint32_t vbc(int c) const { return ld(vbc_ + c); }
+};
+// first slot of every class, once the counts are complete (one thread)
+template <class Counts> __device__ __forceinline__ void plan_class_bases(const Counts &cnt, uint32_t (&cls_base)[FX_PLL_CLASSES + 1], uint32_t (&vbc_base)[8])
+{
+    uint32_t b = 0;
+    for (int c = 0; c < FX_PLL_CLASSES; c++) { cls_base[c] = b; b += (cnt.cls(c) + 63u) & ~63u; }     // whole waves
+    cls_base[FX_PLL_CLASSES] = b;
+    uint32_t vb = 0;
+    for (int c = 0; c < 7; c++) { vbc_base[c] = vb; vb += (cnt.vbc(c) + 127u) & ~127u; }              // whole forward-pass waves: 128 slots
+    vbc_base[7] = vb;
+}
+// padding slots of every class (one workgroup)
+template <class Counts> __device__ __forceinline__ void plan_pad_lists(const Counts &cnt, const uint32_t (&cls_base)[FX_PLL_CLASSES + 1], const uint32_t (&vbc_base)[8], const FxPlanArgs &a)
+{
+    for (int c = 0; c < FX_PLL_CLASSES; c++)
+        for (uint32_t i = cls_base[c] + cnt.cls(c) + threadIdx.x; i < cls_base[c + 1] && i < a.list_cap; i += PLAN_THREADS) a.pll_list[i] = 0xFFFFFFFFu;
+    for (int c = 0; c < 7; c++)
+        for (uint32_t i = vbc_base[c] + cnt.vbc(c) + threadIdx.x; i < vbc_base[c + 1] && i < a.vb_cap; i += PLAN_THREADS) a.vb_items[i] = 0xFFFFFFFFu;
+}
+// The block header, from the block's totals tot[] (PV_*), counts and class bases, on top of the walk-phase header h holds (one thread).  It
+// is put together in LDS -- a local struct indexed per class would live in scratch memory.
+template <class Tot, class Counts> __device__ __forceinline__ void plan_fill_hdr(FxBlockHdr &h, uint32_t N, Tot tot, const Counts &cnt, const uint32_t (&cls_base)[FX_PLL_CLASSES + 1],
+                                                                                 const uint32_t (&vbc_base)[8], const FxPlanArgs &a)
+{
+    h.n_frames = N; h.n_pjobs = tot[PV_JOB]; h.n_mfblk = min(tot[PV_MF], a.mf_cap);
+    h.n_dec_plain = cnt.dec(0); h.n_dec_rs = cnt.dec(1); h.n_dec_batch = cnt.dec(2);
+    h.n_vb_items = min(vbc_base[7], a.vb_cap); h.vb_blk = a.vb_blk; h.vb_want = tot[PV_VB] + 7u * 128u; h.n_vb_fallback = 0;
+    for (int c = 0; c < FX_PLL_CLASSES; c++) { h.pll_cnt[c] = cnt.cls(c); h.pll_base[c] = cls_base[c]; }
+    h.pll_base[FX_PLL_CLASSES] = cls_base[FX_PLL_CLASSES];
+    h.sym_total = tot[PV_SYM]; h.byte_total = tot[PV_BYTE]; h.dw_total = tot[PV_DW]; h.out_total = tot[PV_OUT];
+    h.done = 1;
+}
+// ... goes out to the payload kernels' copy and to the host's a word per thread, and the walk-phase header is zeroed for the slot's next block
+__device__ __forceinline__ void plan_mirror_hdr(const FxBlockHdr &h, const FxPlanArgs &a)
+{
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&h);
+    uint32_t *d0 = reinterpret_cast<uint32_t *>(a.hdr_pay), *d1 = reinterpret_cast<uint32_t *>(a.hdr_host), *z = reinterpret_cast<uint32_t *>(a.hdr);
+    for (int i = threadIdx.x; i < (int)(sizeof(FxBlockHdr) / 4); i += PLAN_THREADS) { const uint32_t w = src[i]; d0[i] = w; d1[i] = w; z[i] = 0u; }
+}
+
+// ---- the pair ----
+// frame g (stream order, then position), its size words and sizes; not live: beyond the workgroup's range, nothing is read
+__device__ __forceinline__ PlanFrame plan_frame(uint32_t g, bool live, const FxPlanArgs &a, PlanWords &w, uint32_t (&v)[PLAN_NV])
+{
+    const uint32_t sidx = live ? plan_stream_of(a.stream_base, a.nstreams, g) : 0u;
+    const FxFrame *fp = live ? a.chain + a.streams[sidx].chain_base + (g - a.stream_base[sidx]) : nullptr;
+    w = live ? plan_words(fp) : PlanWords{};
+    PlanFrame f = plan_sizes(w, live, a.detect, a.vb_blk, v);
+    f.fp = fp; f.sidx = sidx;
     return f;
 }
 // the frames a workgroup of a plan kernel handles: [g0, g1), whole chunks of PLAN_THREADS
@@ -2213,21 +2323,21 @@ __device__ __forceinline__ uint32_t plan_stream_bases(const uint32_t *chain_coun
     return run;
 }
 
-// the body of fx_plan_kernel
-__device__ __forceinline__ void plan_jobs_body(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
-                                               const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0,
-                                               uint32_t mf_cap, uint32_t vb_cap, uint32_t *pw, uint32_t (*ws)[PLAN_NV], uint32_t *base_s)
+extern "C" __global__ __launch_bounds__(PLAN_THREADS)
+void fx_plan_kernel(const FxPlanArgs a)
 {
-    // vb_blk: trellis steps per block of the batch Viterbi path (0: path off, e.g. soft decisions)
+    __shared__ uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
+    __shared__ uint32_t base_s[PLAN_NV];
+    uint32_t *const pw = a.ws;
     const int tid = threadIdx.x;
-    const uint32_t N = plan_stream_bases(chain_count, nstreams, stream_base, ws);
+    const uint32_t N = plan_stream_bases(a.chain_count, a.nstreams, a.stream_base, ws);
     uint32_t g0, g1; plan_range(N, g0, g1);
     const uint32_t wg = blockIdx.x;
     // 1. totals of the range
     uint32_t run[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };
     for (uint32_t c0 = g0; c0 < g1; c0 += PLAN_THREADS) {
-        uint32_t v[PLAN_NV], tot[PLAN_NV];
-        (void)plan_frame(c0 + tid, c0 + tid < g1, streams, nstreams, stream_base, chain, detect, vb_blk, v);
+        uint32_t v[PLAN_NV], tot[PLAN_NV]; PlanWords w;
+        (void)plan_frame(c0 + tid, c0 + tid < g1, a, w, v);
         plan_scan(v, tot, ws);
 #pragma unroll
         for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
@@ -2254,154 +2364,76 @@ __device__ __forceinline__ void plan_jobs_body(const FxStreamDesc *streams, uint
     }
     __syncthreads();
     // 3. jobs, records, matched-filter items, counts
-    uint32_t sym_run = base_s[0], byte_run = base_s[1], dw_run = base_s[2], out_run = base_s[3], mf_run = base_s[4], vb_run = base_s[6];
+    uint32_t before[PLAN_NV];
+#pragma unroll
+    for (int q = 0; q < PLAN_NV; q++) before[q] = base_s[q];
     for (uint32_t c0 = g0; c0 < g1; c0 += PLAN_THREADS) {
         const uint32_t g = c0 + tid;
         const bool live = g < g1;
-        uint32_t v[PLAN_NV], tot[PLAN_NV];
-        PlanFrame f = plan_frame(g, live, streams, nstreams, stream_base, chain, detect, vb_blk, v);
-        const FxFrame *fp = f.fp;
+        uint32_t v[PLAN_NV], tot[PLAN_NV]; PlanWords w;
+        PlanFrame f = plan_frame(g, live, a, w, v);
         plan_scan(v, tot, ws);
-        // (work items beyond the arena, padding of the seven code classes included: the frame goes the wave-per-frame way, and
-        // so does every frame behind it)
-        if (f.batch && (uint64_t)vb_run + v[6] + f.vnb + 7u * 128u > vb_cap) { f.batch = false; f.vnb = 0; }
-        const uint32_t sym_off = sym_run + v[0], byte_off = byte_run + v[1], dw_off = dw_run + v[2], out_off = out_run + v[3], mf_off = mf_run + v[4];
-        sym_run += tot[0]; byte_run += tot[1]; dw_run += tot[2]; out_run += tot[3]; mf_run += tot[4]; vb_run += tot[6];
+#pragma unroll
+        for (int q = 0; q < PLAN_NV; q++) { v[q] += before[q]; before[q] += tot[q]; }   // v[]: the frame's offsets from here
+        if (f.batch && plan_demote(v[PV_VB], f.vnb, a.vb_cap)) { f.batch = false; f.vnb = 0; }
         if (live) {
-            const FxStreamDesc &sd = streams[f.sidx];
-            FxPayJob j;
-            j.x = sd.x; j.xa_end = sd.xa_end; j.start = fp->start; j.mix_th = fp->mix_th; j.mix_dl = fp->mix_dl; j.mf_scale = fp->mf_scale;
-            j.pfb = fp->pfb; j.mfc0 = fp->mfc0; j.pll_th = fp->pll_th; j.pll_f = fp->pll_f; j.ms = fp->ms; j.bps = f.bps;
-            j.nsym = f.valid ? fp->pay_sym_len : 0u; j.sym_off = sym_off;
-            j.pay_len = fp->pay_len; j.check = fp->check; j.fec0 = fp->fec0; j.fec1 = fp->fec1; j.k = f.k; j.l0 = f.l0; j.l1 = f.l1;
-            j.byte_off = byte_off; j.dw_off = dw_off; j.out_off = out_off; j.pad_ = f.valid ? 1u : 0u;
-            j.eq = eq; j.chain_idx = (uint32_t)(fp - chain); j.vb_off = 0; j.vb_nblk = (uint16_t)f.vnb; j.vb_clean = 0;
-            pjobs[g] = j;
-            // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
-            union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
-            u.r.start = sd.abs_base + fp->start; u.r.stream = f.sidx; u.r.offset = fp->offset;
-            u.r.rxy = fp->rxy; u.r.tau = fp->tau; u.r.gamma = fp->gamma; u.r.dphi = fp->dphi; u.r.phi = fp->phi; u.r.pfb = fp->pfb;
-            u.r.pilot_dphi = fp->pilot_dphi; u.r.pilot_phi = fp->pilot_phi; u.r.pilot_gain = fp->pilot_gain;
-            u.r.flags = fp->flags & FX_FLAG_HEADER_VALID;
-            u.r.pay_len = f.valid ? fp->pay_len : 0u; u.r.ms = fp->ms; u.r.check = fp->check; u.r.fec0 = fp->fec0; u.r.fec1 = fp->fec1;
-            u.r.nsym = f.valid ? fp->pay_sym_len : 0u; u.r.bps = f.bps; u.r.sym_off = sym_off; u.r.out_off = out_off;
-            u.r.evm_sum = 0.0f; u.r.payload_valid = 0; u.r.status = 0;
-            const uint32_t *hw = reinterpret_cast<const uint32_t *>(fp->header); uint32_t *rw = reinterpret_cast<uint32_t *>(u.r.header);
-#pragma unroll
-            for (int i = 0; i < FX_HDR_DEC / 4; i++) rw[i] = hw[i];
-            u.r.byte_off = byte_off;
-            uint4 *dst = reinterpret_cast<uint4 *>(recs + g);
-#pragma unroll
-            for (int i = 0; i < (int)(sizeof(FxOutRec) / 16); i++) dst[i] = u.q[i];
-            if (f.valid) {
-                for (uint32_t c = 0; c < f.nblk; c++) if (mf_off + c < mf_cap) { mf_job[mf_off + c] = g; mf_c0[mf_off + c] = c * 1024u; }
-            }
+            // (vb_off: the frame's trellis items get their slots in fx_planlists_kernel, which stores it)
+            plan_emit(a.pjobs + g, a.recs + g, f.fp, a.streams + f.sidx, w, f, v, a.eq, (uint32_t)(f.fp - a.chain), 0u);
+            for (uint32_t c = 0; c < f.nblk; c++) if (v[PV_MF] + c < a.mf_cap) { a.mf_job[v[PV_MF] + c] = g; a.mf_c0[v[PV_MF] + c] = c * 1024u; }
         }
         {   // counts per list (wave-aggregated: one atomic per wave and list)
-            const bool val = live && f.valid;
-            const uint32_t ms = val ? fp->ms : 0u, fec0 = val ? fp->fec0 : 0u, fec1 = val ? fp->fec1 : 0u;
-            (void)wave_agg_add(pw + PW_CLS_CNT, pll_class(ms), 1u, val);
-            (void)wave_agg_add(pw + PW_DEC_CNT, f.batch ? 2u : ((fec0 == FX_FEC_RS_M8 || fec1 == FX_FEC_RS_M8) ? 1u : 0u), 1u, val);
-            (void)wave_agg_add(pw + PW_VBC_CNT, val && f.batch ? (uint32_t)conv_p(fec0) - 1u : 0u, f.vnb, val && f.batch);
+            const PlanKey key = plan_key(w.ms, w.fec0, w.fec1);
+            (void)wave_agg_add(pw + PW_CLS_CNT, key.cls, 1u, f.valid);
+            (void)wave_agg_add(pw + PW_DEC_CNT, key.dec(f.batch), 1u, f.valid);
+            (void)wave_agg_add(pw + PW_VBC_CNT, key.vc, f.vnb, f.batch);
         }
         __syncthreads();
     }
 }
 
 extern "C" __global__ __launch_bounds__(PLAN_THREADS)
-void fx_plan_kernel(const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain, const uint32_t *chain_count,
-                    uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap, uint32_t vb_cap, uint32_t *pw)
+void fx_planlists_kernel(const FxPlanArgs a)
 {
-    __shared__ uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
-    __shared__ uint32_t base_s[PLAN_NV];
-    plan_jobs_body(streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0, mf_cap, vb_cap, pw, ws, base_s);
-}
-
-struct PlanListsShared { FxBlockHdr h; uint32_t cls_base[FX_PLL_CLASSES + 1], vbc_base[8], last; };
-// the body of fx_planlists_kernel.  The counts were added up with device-scope atomics; they are read the same way.
-__device__ __forceinline__ void plan_lists_body(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_base, FxPayJob *pjobs, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
-                                                uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw,
-                                                PlanListsShared &sh)
-{
-    uint32_t (&cls_base)[FX_PLL_CLASSES + 1] = sh.cls_base; uint32_t (&vbc_base)[8] = sh.vbc_base; uint32_t &last = sh.last;
+    __shared__ struct { FxBlockHdr h; uint32_t cls_base[FX_PLL_CLASSES + 1], vbc_base[8], last; } sh;
+    uint32_t *const pw = a.ws;
+    const PlanCounts<true> cnt{ pw + PW_CLS_CNT, pw + PW_DEC_CNT, pw + PW_VBC_CNT };
     const int tid = threadIdx.x;
-    const uint32_t N = __hip_atomic_load(&stream_base[nstreams], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) {
-        uint32_t b = 0;
-        for (int c = 0; c < FX_PLL_CLASSES; c++) { cls_base[c] = b; b += (__hip_atomic_load(&pw[PW_CLS_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 63u) & ~63u; }   // whole waves
-        cls_base[FX_PLL_CLASSES] = b;
-        uint32_t vb = 0;
-        for (int c = 0; c < 7; c++) { vbc_base[c] = vb; vb += (__hip_atomic_load(&pw[PW_VBC_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 127u) & ~127u; }            // whole forward-pass waves: 128 slots
-        vbc_base[7] = vb;
-    }
+    const uint32_t N = __hip_atomic_load(&a.stream_base[a.nstreams], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) plan_class_bases(cnt, sh.cls_base, sh.vbc_base);
     __syncthreads();
     uint32_t g0, g1; plan_range(N, g0, g1);
     for (uint32_t c0 = g0; c0 < g1; c0 += PLAN_THREADS) {                     // (whole chunks: the slot cursors are advanced wave by wave)
         const uint32_t g = c0 + tid;
         const bool live = g < g1;
         uint32_t ms = 0, fec0 = 0, fec1 = 0, vnb = 0; bool val = false;
-        if (live) { const FxPayJob &j = pjobs[g]; val = j.pad_ != 0; ms = j.ms; fec0 = j.fec0; fec1 = j.fec1; vnb = j.vb_nblk; }
-        const unsigned c = pll_class(ms);
-        const uint32_t pp = cls_base[c] + wave_agg_add(pw + PW_CLS_FILL, c, 1u, val);
-        if (val && pp < list_cap) pll_list[pp] = g;
-        const uint32_t rs = vnb ? 2u : ((fec0 == FX_FEC_RS_M8 || fec1 == FX_FEC_RS_M8) ? 1u : 0u);
-        const uint32_t dp = wave_agg_add(pw + PW_DEC_FILL, rs, 1u, val);
-        if (val && dp < list_cap) dec_list[(size_t)rs * list_cap + dp] = g;
-        const bool bt = val && vnb;                                             // its trellis blocks, among those of the same code
-        const uint32_t vc = bt ? (uint32_t)conv_p(fec0) - 1u : 0u;
-        const uint32_t at = vbc_base[vc] + wave_agg_add(pw + PW_VBC_FILL, vc, vnb, bt);
+        if (live) { const FxPayJob &j = a.pjobs[g]; val = j.pad_ != 0; ms = j.ms; fec0 = j.fec0; fec1 = j.fec1; vnb = j.vb_nblk; }
+        const PlanKey key = plan_key(ms, fec0, fec1);
+        const bool bt = val && vnb;                                             // a batch frame: the only ones with trellis blocks
+        const uint32_t pp = sh.cls_base[key.cls] + wave_agg_add(pw + PW_CLS_FILL, key.cls, 1u, val);
+        if (val && pp < a.list_cap) a.pll_list[pp] = g;
+        const uint32_t rs = key.dec(bt), dp = wave_agg_add(pw + PW_DEC_FILL, rs, 1u, val);
+        if (val && dp < a.list_cap) a.dec_list[(size_t)rs * a.list_cap + dp] = g;
+        const uint32_t at = sh.vbc_base[key.vc] + wave_agg_add(pw + PW_VBC_FILL, key.vc, vnb, bt);   // its trellis blocks, among those of the same code
         if (bt) {
-            for (uint32_t b = 0; b < vnb; b++) if (at + b < vb_cap) { vb_items[at + b] = g; vb_items[vb_cap + at + b] = b; }
-            pjobs[g].vb_off = at;
+            for (uint32_t b = 0; b < vnb; b++) if (at + b < a.vb_cap) { a.vb_items[at + b] = g; a.vb_items[a.vb_cap + at + b] = b; }
+            a.pjobs[g].vb_off = at;
         }
     }
-    if (blockIdx.x == 0) {                                                      // padding slots of every class
-        for (int c = 0; c < FX_PLL_CLASSES; c++)
-            for (uint32_t i = cls_base[c] + __hip_atomic_load(&pw[PW_CLS_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + tid; i < cls_base[c + 1] && i < list_cap; i += PLAN_THREADS) pll_list[i] = 0xFFFFFFFFu;
-        for (int c = 0; c < 7; c++)
-            for (uint32_t i = vbc_base[c] + __hip_atomic_load(&pw[PW_VBC_CNT + c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + tid; i < vbc_base[c + 1] && i < vb_cap; i += PLAN_THREADS) vb_items[i] = 0xFFFFFFFFu;
-    }
+    if (blockIdx.x == 0) plan_pad_lists(cnt, sh.cls_base, sh.vbc_base, a);
     // the workgroup that finishes last: block header for the payload kernels and for the host; counters, workspace and the
     // walk-phase header are zeroed for the slot's next block
     __threadfence(); __syncthreads();
-    if (tid == 0) last = atomicAdd(&pw[PW_TICKET], 1u) == gridDim.x - 1 ? 1u : 0u;
+    if (tid == 0) sh.last = atomicAdd(&pw[PW_TICKET], 1u) == gridDim.x - 1 ? 1u : 0u;
     __syncthreads();
-    if (!last) return;
+    if (!sh.last) return;
     __threadfence();
-    // (the header is put together in LDS -- a local struct indexed per class would live in scratch memory -- and goes out to both
-    // copies a word per thread)
     if (tid == 0) {
-        const volatile uint32_t *tot = pw + PW_INC + 8 * (gridDim.x - 1), *cnt = pw;
-        FxBlockHdr &h = sh.h;
-        h = *hdr;
-        h.n_frames = N; h.n_pjobs = tot[5]; h.n_mfblk = min(tot[4], mf_cap);
-        h.n_dec_plain = cnt[PW_DEC_CNT + 0]; h.n_dec_rs = cnt[PW_DEC_CNT + 1]; h.n_dec_batch = cnt[PW_DEC_CNT + 2];
-        h.n_vb_items = min(vbc_base[7], vb_cap); h.vb_blk = vb_blk; h.vb_want = tot[6] + 7u * 128u; h.n_vb_fallback = 0;
-        for (int c = 0; c < FX_PLL_CLASSES; c++) { h.pll_cnt[c] = cnt[PW_CLS_CNT + c]; h.pll_base[c] = cls_base[c]; }
-        h.pll_base[FX_PLL_CLASSES] = cls_base[FX_PLL_CLASSES];
-        h.sym_total = tot[0]; h.byte_total = tot[1]; h.dw_total = tot[2]; h.out_total = tot[3];
-        h.done = 1;
+        sh.h = *a.hdr;
+        plan_fill_hdr(sh.h, N, (const volatile uint32_t *)(pw + PW_INC + 8 * (gridDim.x - 1)), cnt, sh.cls_base, sh.vbc_base, a);
     }
     __syncthreads();
-    {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(&sh.h);
-        uint32_t *d0 = reinterpret_cast<uint32_t *>(hdr_pay), *d1 = reinterpret_cast<uint32_t *>(hdr_host);
-        for (int i = tid; i < (int)(sizeof(FxBlockHdr) / 4); i += PLAN_THREADS) { const uint32_t w = src[i]; d0[i] = w; d1[i] = w; }
-    }
-    __syncthreads();
-    {
-        uint32_t *z = reinterpret_cast<uint32_t *>(hdr);
-        for (int i = tid; i < (int)(sizeof(FxBlockHdr) / 4); i += PLAN_THREADS) z[i] = 0u;
-        for (int i = tid; i < PW_WORDS; i += PLAN_THREADS) pw[i] = 0u;
-    }
-}
-
-extern "C" __global__ __launch_bounds__(PLAN_THREADS)
-void fx_planlists_kernel(uint32_t nstreams, uint32_t vb_blk, uint32_t *stream_base, FxPayJob *pjobs, uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list,
-                         uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay, FxBlockHdr *hdr_host, uint32_t *pw)
-{
-    __shared__ PlanListsShared sh;
-    plan_lists_body(nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, pw, sh);
+    plan_mirror_hdr(sh.h, a);
+    for (int i = tid; i < PW_WORDS; i += PLAN_THREADS) pw[i] = 0u;
 }
 
 // ---- the plan stage of a block that ONE workgroup plans (launched as a grid of one: the usual case, a block of up to ~2048 frames).
@@ -2430,31 +2462,21 @@ struct PlanOneShared {
     uint32_t sbase[PLAN_LDS_STREAMS + 1], cbase[PLAN_LDS_STREAMS];   // frames before each stream / its region of the chain table
 };
 // chain slot of frame g (stream order, then position) and its stream
-__device__ __forceinline__ uint32_t plan_one_slot(uint32_t g, const FxStreamDesc *streams, uint32_t nstreams, const uint32_t *stream_base, const PlanOneShared &sh, uint32_t &sidx)
+__device__ __forceinline__ uint32_t plan_one_slot(uint32_t g, const FxPlanArgs &a, const PlanOneShared &sh, uint32_t &sidx)
 {
-    uint32_t lo = 0, hi = nstreams;                                          // base[lo] <= g < base[hi]
-    if (nstreams <= PLAN_LDS_STREAMS) {
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (sh.sbase[mid] <= g) lo = mid; else hi = mid; }
-        sidx = lo;
-        return sh.cbase[lo] + (g - sh.sbase[lo]);
-    }
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (stream_base[mid] <= g) lo = mid; else hi = mid; }
-    sidx = lo;
-    return streams[lo].chain_base + (g - stream_base[lo]);
+    if (a.nstreams <= PLAN_LDS_STREAMS) { sidx = plan_stream_of(sh.sbase, a.nstreams, g); return sh.cbase[sidx] + (g - sh.sbase[sidx]); }
+    sidx = plan_stream_of(a.stream_base, a.nstreams, g);
+    return a.streams[sidx].chain_base + (g - a.stream_base[sidx]);
 }
 
 extern "C" __global__ __launch_bounds__(PLAN_THREADS)
-void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *__restrict__ chain,
-                         const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *__restrict__ pjobs, FxOutRec *__restrict__ recs, uint32_t *mf_job, uint32_t *mf_c0,
-                         uint32_t mf_cap, uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
-                         FxBlockHdr *hdr_host, uint32_t *pw)
+void fx_planfused_kernel(const FxPlanArgs a)
 {
     __shared__ PlanOneShared sh;
     __shared__ uint4 keep[PLAN_KEEP * PLAN_THREADS];
     constexpr uint32_t TILE = PLAN_KEEP * PLAN_THREADS;
-    constexpr int HW = (int)(sizeof(FxBlockHdr) / 4);
-    const uint32_t tid = threadIdx.x;
-    (void)pw;
+    const PlanCounts<false> cnt{ sh.cnt + PO_CLS, sh.cnt + PO_DEC, sh.cnt + PO_VBC };
+    const uint32_t tid = threadIdx.x, nstreams = a.nstreams;
     // diagnostic builds: thread 0's shader clocks per step, summed over tiles, in the header's free stamp words -- [1] header read, stream
     // bases, sizes, scan, counts, class bases | [2] jobs and records | [6] item runs, padding | [7] the fence in front of the header
 #ifdef FX_STAMPS
@@ -2465,8 +2487,8 @@ void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstr
 #endif
     // the block's walk-phase header (complete: its writers ran before this kernel), a word per thread; counters and cursors
     {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(hdr); uint32_t *dst = reinterpret_cast<uint32_t *>(&sh.h);
-        for (int i = (int)tid; i < HW; i += PLAN_THREADS) dst[i] = src[i];
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.hdr); uint32_t *dst = reinterpret_cast<uint32_t *>(&sh.h);
+        for (int i = (int)tid; i < (int)(sizeof(FxBlockHdr) / 4); i += PLAN_THREADS) dst[i] = src[i];
         if (tid < PO_N) { sh.cnt[tid] = 0u; sh.fill[tid] = 0u; }
         if (tid <= FX_PLL_CLASSES) sh.cls_base[tid] = 0u;
         if (tid < 8) sh.vbc_base[tid] = 0u;
@@ -2474,13 +2496,13 @@ void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstr
     // frames before each stream (one stream, the usual case: {0, its count}, no scan)
     uint32_t N;
     if (nstreams <= PLAN_LDS_STREAMS) {
-        uint32_t v[PLAN_NV] = { tid < nstreams ? chain_count[tid] : 0u, 0, 0, 0, 0, 0, 0 }, tot[PLAN_NV];
+        uint32_t v[PLAN_NV] = { tid < nstreams ? a.chain_count[tid] : 0u, 0, 0, 0, 0, 0, 0 }, tot[PLAN_NV];
         if (nstreams > 1) plan_scan(v, tot, sh.ws); else { tot[0] = v[0]; v[0] = 0u; }
-        if (tid < nstreams) { sh.sbase[tid] = v[0]; stream_base[tid] = v[0]; sh.cbase[tid] = streams[tid].chain_base; }
-        if (tid == 0) { sh.sbase[nstreams] = tot[0]; stream_base[nstreams] = tot[0]; }
+        if (tid < nstreams) { sh.sbase[tid] = v[0]; a.stream_base[tid] = v[0]; sh.cbase[tid] = a.streams[tid].chain_base; }
+        if (tid == 0) { sh.sbase[nstreams] = tot[0]; a.stream_base[nstreams] = tot[0]; }
         __syncthreads();
         N = sh.sbase[nstreams];
-    } else N = plan_stream_bases(chain_count, nstreams, stream_base, sh.ws);
+    } else N = plan_stream_bases(a.chain_count, nstreams, a.stream_base, sh.ws);
 
     uint32_t run[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };                         // totals of the tiles done (after the last one: of the block)
     for (int pass = N > TILE ? 0 : 1; pass < 2; pass++) {                    // pass 0: the counting sweep of a block of several tiles
@@ -2490,30 +2512,22 @@ void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstr
             const uint32_t nt = min(TILE, N - t0), t1 = t0 + nt, per = (nt + PLAN_THREADS - 1) / PLAN_THREADS, f0 = t0 + tid * per;
             // 1. sizes of my frames: every load is issued before any is used (frames that are not mine read the tile's first one)
             uint32_t st[PLAN_NV], tot[PLAN_NV];
-            uint32_t info[PLAN_KEEP];                                        // vnb | class << 16 | Reed-Solomon << 20 | code class << 21 | valid << 24 | batch << 25
+            uint32_t info[PLAN_KEEP];                                        // vnb | list key (PlanKey::pack) << 16 | valid << 24 | batch << 25
             {
-                uint32_t w[PLAN_KEEP][7];
+                PlanWords w[PLAN_KEEP];
 #pragma unroll
                 for (int i = 0; i < PLAN_KEEP; i++) {
                     const bool live = (uint32_t)i < per && f0 + i < t1;
                     uint32_t sidx;
-                    const FxFrame *fp = chain + plan_one_slot(live ? f0 + i : t0, streams, nstreams, stream_base, sh, sidx);
-                    w[i][0] = fp->flags; w[i][1] = fp->pay_sym_len; w[i][2] = fp->pay_len; w[i][3] = fp->ms; w[i][4] = fp->check; w[i][5] = fp->fec0; w[i][6] = fp->fec1;
+                    w[i] = plan_words(a.chain + plan_one_slot(live ? f0 + i : t0, a, sh, sidx));
                 }
 #pragma unroll
                 for (int q = 0; q < PLAN_NV; q++) st[q] = 0u;
 #pragma unroll
                 for (int i = 0; i < PLAN_KEEP; i++) {
-                    const bool live = (uint32_t)i < per && f0 + i < t1;
-                    PlanFrame f; f.bps = f.k = f.l0 = f.l1 = f.nblk = f.vnb = 0; f.batch = false;
-                    f.valid = live && !detect && (w[i][0] & FX_FLAG_HEADER_VALID);
-                    uint32_t v[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };
-                    info[i] = 0u;
-                    if (f.valid) {
-                        plan_sizes(f, w[i][1], w[i][2], w[i][3], w[i][4], w[i][5], w[i][6], vb_blk, v);
-                        info[i] = f.vnb | pll_class(w[i][3]) << 16 | ((w[i][5] == FX_FEC_RS_M8 || w[i][6] == FX_FEC_RS_M8) ? 1u << 20 : 0u) |
-                                  (f.batch ? ((uint32_t)conv_p(w[i][5]) - 1u) << 21 | 1u << 25 : 0u) | 1u << 24;
-                    }
+                    uint32_t v[PLAN_NV];
+                    const PlanFrame f = plan_sizes(w[i], (uint32_t)i < per && f0 + i < t1, a.detect, a.vb_blk, v);
+                    info[i] = f.valid ? f.vnb | plan_key(w[i].ms, w[i].fec0, w[i].fec1).pack() << 16 | 1u << 24 | (f.batch ? 1u << 25 : 0u) : 0u;
 #pragma unroll
                     for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
                 }
@@ -2522,20 +2536,19 @@ void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstr
             plan_scan(st, tot, sh.ws);
 #pragma unroll
             for (int q = 0; q < PLAN_NV; q++) st[q] += run[q];
-            // 3. counts per list, where no counting sweep has done it (work items beyond the arena, padding of the seven code classes included:
-            // the frame goes the wave-per-frame way, and so does every frame behind it)
+            // 3. counts per list, where no counting sweep has done it
             if (pass == 0 || N <= TILE) {
-                uint32_t vb = st[6];
+                uint32_t vb = st[PV_VB];
 #pragma unroll
                 for (int i = 0; i < PLAN_KEEP; i++) {
                     const uint32_t vnb = info[i] & 0xffffu;
-                    bool batch = (info[i] >> 25) & 1u;
-                    if (batch && (uint64_t)vb + vnb + 7u * 128u > vb_cap) batch = false;
+                    const bool batch = ((info[i] >> 25) & 1u) && !plan_demote(vb, vnb, a.vb_cap);
                     vb += vnb;
                     if ((info[i] >> 24) & 1u) {
-                        atomicAdd(&sh.cnt[PO_CLS + ((info[i] >> 16) & 15u)], 1u);
-                        atomicAdd(&sh.cnt[PO_DEC + (batch ? 2u : (info[i] >> 20) & 1u)], 1u);
-                        if (batch) atomicAdd(&sh.cnt[PO_VBC + ((info[i] >> 21) & 7u)], vnb);
+                        const PlanKey key = PlanKey::unpack(info[i] >> 16);
+                        atomicAdd(&sh.cnt[PO_CLS + key.cls], 1u);
+                        atomicAdd(&sh.cnt[PO_DEC + key.dec(batch)], 1u);
+                        if (batch) atomicAdd(&sh.cnt[PO_VBC + key.vc], vnb);
                     }
                 }
             }
@@ -2544,70 +2557,35 @@ void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstr
                 for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
                 continue;
             }
-            if (t0 == 0) {                                                   // the counts are complete: first slot of every class
+            if (t0 == 0) {                                                   // the counts are complete
                 __syncthreads();
-                if (tid == 0) {
-                    uint32_t b = 0;
-                    for (int c = 0; c < FX_PLL_CLASSES; c++) { sh.cls_base[c] = b; b += (sh.cnt[PO_CLS + c] + 63u) & ~63u; }     // whole waves
-                    sh.cls_base[FX_PLL_CLASSES] = b;
-                    uint32_t vb = 0;
-                    for (int c = 0; c < 7; c++) { sh.vbc_base[c] = vb; vb += (sh.cnt[PO_VBC + c] + 127u) & ~127u; }              // whole forward-pass waves: 128 slots
-                    sh.vbc_base[7] = vb;
-                }
+                if (tid == 0) plan_class_bases(cnt, sh.cls_base, sh.vbc_base);
                 __syncthreads();
             }
             PLAN_TICK(st1_);
-            // 4. jobs, records, list slots of my frames, one after the other
-            uint32_t sym_run = st[0], byte_run = st[1], dw_run = st[2], out_run = st[3], mf_run = st[4], vb_run = st[6];
+            // 4. jobs, records, list slots of my frames, one after the other; st[]: the frame's offsets
             for (uint32_t i = 0; i < per && f0 + i < t1; i++) {
                 const uint32_t g = f0 + i;
-                uint32_t sidx;
-                const uint32_t slot = plan_one_slot(g, streams, nstreams, stream_base, sh, sidx);
-                const FxFrame *__restrict__ fp = chain + slot;
-                const uint32_t flags = fp->flags, nsym = fp->pay_sym_len, plen = fp->pay_len, ms = fp->ms, check = fp->check, fec0 = fp->fec0, fec1 = fp->fec1;
-                PlanFrame f; f.bps = f.k = f.l0 = f.l1 = f.nblk = f.vnb = 0; f.batch = false;
-                f.valid = !detect && (flags & FX_FLAG_HEADER_VALID);
-                uint32_t v[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };
-                if (f.valid) plan_sizes(f, nsym, plen, ms, check, fec0, fec1, vb_blk, v);
-                if (f.batch && (uint64_t)vb_run + f.vnb + 7u * 128u > vb_cap) { f.batch = false; f.vnb = 0; }
-                const uint32_t sym_off = sym_run, byte_off = byte_run, dw_off = dw_run, out_off = out_run, mf_off = mf_run;
-                sym_run += v[0]; byte_run += v[1]; dw_run += v[2]; out_run += v[3]; mf_run += v[4]; vb_run += v[6];
+                uint32_t sidx, v[PLAN_NV];
+                const uint32_t slot = plan_one_slot(g, a, sh, sidx);
+                const FxFrame *fp = a.chain + slot;
+                const PlanWords w = plan_words(fp);
+                PlanFrame f = plan_sizes(w, true, a.detect, a.vb_blk, v);
+                f.fp = fp; f.sidx = sidx;
+                if (f.batch && plan_demote(st[PV_VB], f.vnb, a.vb_cap)) { f.batch = false; f.vnb = 0; }
                 uint32_t at = 0;
                 if (f.valid) {
-                    const unsigned c = pll_class(ms);
-                    const uint32_t pp = sh.cls_base[c] + atomicAdd(&sh.fill[PO_CLS + c], 1u);
-                    if (pp < list_cap) pll_list[pp] = g;
-                    const uint32_t rs = f.batch ? 2u : ((fec0 == FX_FEC_RS_M8 || fec1 == FX_FEC_RS_M8) ? 1u : 0u);
-                    const uint32_t dp = atomicAdd(&sh.fill[PO_DEC + rs], 1u);
-                    if (dp < list_cap) dec_list[(size_t)rs * list_cap + dp] = g;
-                    if (f.batch) { const uint32_t vc = (uint32_t)conv_p(fec0) - 1u; at = sh.vbc_base[vc] + atomicAdd(&sh.fill[PO_VBC + vc], f.vnb); }   // its trellis blocks, among those of the same code
+                    const PlanKey key = plan_key(w.ms, w.fec0, w.fec1);
+                    const uint32_t pp = sh.cls_base[key.cls] + atomicAdd(&sh.fill[PO_CLS + key.cls], 1u);
+                    if (pp < a.list_cap) a.pll_list[pp] = g;
+                    const uint32_t rs = key.dec(f.batch), dp = atomicAdd(&sh.fill[PO_DEC + rs], 1u);
+                    if (dp < a.list_cap) a.dec_list[(size_t)rs * a.list_cap + dp] = g;
+                    if (f.batch) at = sh.vbc_base[key.vc] + atomicAdd(&sh.fill[PO_VBC + key.vc], f.vnb);   // its trellis blocks, among those of the same code
                 }
-                keep[g - t0] = make_uint4(at, f.vnb, mf_off, f.nblk);
-                const FxStreamDesc &sd = streams[sidx];
-                FxPayJob j;
-                j.x = sd.x; j.xa_end = sd.xa_end; j.start = fp->start; j.mix_th = fp->mix_th; j.mix_dl = fp->mix_dl; j.mf_scale = fp->mf_scale;
-                j.pfb = fp->pfb; j.mfc0 = fp->mfc0; j.pll_th = fp->pll_th; j.pll_f = fp->pll_f; j.ms = ms; j.bps = f.bps;
-                j.nsym = f.valid ? nsym : 0u; j.sym_off = sym_off;
-                j.pay_len = plen; j.check = check; j.fec0 = fec0; j.fec1 = fec1; j.k = f.k; j.l0 = f.l0; j.l1 = f.l1;
-                j.byte_off = byte_off; j.dw_off = dw_off; j.out_off = out_off; j.pad_ = f.valid ? 1u : 0u;
-                j.eq = eq; j.chain_idx = slot; j.vb_off = at; j.vb_nblk = (uint16_t)f.vnb; j.vb_clean = 0;
-                pjobs[g] = j;
-                // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
-                union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
-                u.r.start = sd.abs_base + fp->start; u.r.stream = sidx; u.r.offset = fp->offset;
-                u.r.rxy = fp->rxy; u.r.tau = fp->tau; u.r.gamma = fp->gamma; u.r.dphi = fp->dphi; u.r.phi = fp->phi; u.r.pfb = fp->pfb;
-                u.r.pilot_dphi = fp->pilot_dphi; u.r.pilot_phi = fp->pilot_phi; u.r.pilot_gain = fp->pilot_gain;
-                u.r.flags = flags & FX_FLAG_HEADER_VALID;
-                u.r.pay_len = f.valid ? plen : 0u; u.r.ms = ms; u.r.check = check; u.r.fec0 = fec0; u.r.fec1 = fec1;
-                u.r.nsym = f.valid ? nsym : 0u; u.r.bps = f.bps; u.r.sym_off = sym_off; u.r.out_off = out_off;
-                u.r.evm_sum = 0.0f; u.r.payload_valid = 0; u.r.status = 0;
-                const uint32_t *hw = reinterpret_cast<const uint32_t *>(fp->header); uint32_t *rw = reinterpret_cast<uint32_t *>(u.r.header);
+                keep[g - t0] = make_uint4(at, f.vnb, st[PV_MF], f.nblk);
+                plan_emit(a.pjobs + g, a.recs + g, fp, a.streams + sidx, w, f, st, a.eq, slot, at);
 #pragma unroll
-                for (int k = 0; k < FX_HDR_DEC / 4; k++) rw[k] = hw[k];
-                u.r.byte_off = byte_off;
-                uint4 *dst = reinterpret_cast<uint4 *>(recs + g);
-#pragma unroll
-                for (int k = 0; k < (int)(sizeof(FxOutRec) / 16); k++) dst[k] = u.q[k];
+                for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
             }
             __syncthreads();
             PLAN_TICK(st2_);
@@ -2615,60 +2593,37 @@ void fx_planfused_kernel(const FxStreamDesc *__restrict__ streams, uint32_t nstr
             for (uint32_t k = tid >> 4; k < nt; k += PLAN_THREADS / 16) {
                 const uint4 kp = keep[k];
                 const uint32_t g = t0 + k, sub = tid & 15u;
-                for (uint32_t b = sub; b < kp.y; b += 16u) if (kp.x + b < vb_cap) { vb_items[kp.x + b] = g; vb_items[vb_cap + kp.x + b] = b; }
-                for (uint32_t c = sub; c < kp.w; c += 16u) if (kp.z + c < mf_cap) { mf_job[kp.z + c] = g; mf_c0[kp.z + c] = c * 1024u; }
+                for (uint32_t b = sub; b < kp.y; b += 16u) if (kp.x + b < a.vb_cap) { a.vb_items[kp.x + b] = g; a.vb_items[a.vb_cap + kp.x + b] = b; }
+                for (uint32_t c = sub; c < kp.w; c += 16u) if (kp.z + c < a.mf_cap) { a.mf_job[kp.z + c] = g; a.mf_c0[kp.z + c] = c * 1024u; }
             }
 #pragma unroll
             for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
             __syncthreads();                                                 // (keep[] belongs to the next tile from here)
         }
     }
-    // padding slots of every class
-    for (int c = 0; c < FX_PLL_CLASSES; c++)
-        for (uint32_t i = sh.cls_base[c] + sh.cnt[PO_CLS + c] + tid; i < sh.cls_base[c + 1] && i < list_cap; i += PLAN_THREADS) pll_list[i] = 0xFFFFFFFFu;
-    for (int c = 0; c < 7; c++)
-        for (uint32_t i = sh.vbc_base[c] + sh.cnt[PO_VBC + c] + tid; i < sh.vbc_base[c + 1] && i < vb_cap; i += PLAN_THREADS) vb_items[i] = 0xFFFFFFFFu;
-    // block header for the payload kernels and for the host (behind everything written above); the walk-phase header is zeroed for the
-    // slot's next block
+    plan_pad_lists(cnt, sh.cls_base, sh.vbc_base, a);
+    // block header for the payload kernels and for the host (behind everything written above)
     PLAN_TICK(st6_);
     __threadfence(); __syncthreads();
     PLAN_TICK(st7_);
     if (tid == 0) {
-        FxBlockHdr &h = sh.h;
 #ifdef FX_STAMPS
-        h.stamp[1] = st1_; h.stamp[2] = st2_; h.stamp[6] = st6_; h.stamp[7] = st7_;
+        sh.h.stamp[1] = st1_; sh.h.stamp[2] = st2_; sh.h.stamp[6] = st6_; sh.h.stamp[7] = st7_;
 #endif
-        h.n_frames = N; h.n_pjobs = run[5]; h.n_mfblk = min(run[4], mf_cap);
-        h.n_dec_plain = sh.cnt[PO_DEC + 0]; h.n_dec_rs = sh.cnt[PO_DEC + 1]; h.n_dec_batch = sh.cnt[PO_DEC + 2];
-        h.n_vb_items = min(sh.vbc_base[7], vb_cap); h.vb_blk = vb_blk; h.vb_want = run[6] + 7u * 128u; h.n_vb_fallback = 0;
-        for (int c = 0; c < FX_PLL_CLASSES; c++) { h.pll_cnt[c] = sh.cnt[PO_CLS + c]; h.pll_base[c] = sh.cls_base[c]; }
-        h.pll_base[FX_PLL_CLASSES] = sh.cls_base[FX_PLL_CLASSES];
-        h.sym_total = run[0]; h.byte_total = run[1]; h.dw_total = run[2]; h.out_total = run[3];
-        h.done = 1;
+        plan_fill_hdr(sh.h, N, run, cnt, sh.cls_base, sh.vbc_base, a);
     }
     __syncthreads();
-    {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(&sh.h);
-        uint32_t *d0 = reinterpret_cast<uint32_t *>(hdr_pay), *d1 = reinterpret_cast<uint32_t *>(hdr_host), *z = reinterpret_cast<uint32_t *>(hdr);
-        for (int i = (int)tid; i < HW; i += PLAN_THREADS) { const uint32_t w = src[i]; d0[i] = w; d1[i] = w; z[i] = 0u; }
-    }
+    plan_mirror_hdr(sh.h, a);
 }
 
-extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
-                                     const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap,
-                                     uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
-                                     FxBlockHdr *hdr_host, uint32_t *plan_ws, int fused)
+extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, int fused, const FxPlanArgs &a)
 {
     const unsigned g = grid < 1u ? 1u : (grid > PLAN_MAXG ? PLAN_MAXG : grid);
-    if (fused && g == 1u) {
-        hipLaunchKernelGGL(fx_planfused_kernel, dim3(1), dim3(PLAN_THREADS), 0, st, streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0,
-                           mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap, hdr, hdr_pay, hdr_host, plan_ws);
-        return hipGetLastError();
+    if (fused && g == 1u) hipLaunchKernelGGL(fx_planfused_kernel, dim3(1), dim3(PLAN_THREADS), 0, st, a);
+    else {
+        hipLaunchKernelGGL(fx_plan_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, a);
+        hipLaunchKernelGGL(fx_planlists_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, a);
     }
-    hipLaunchKernelGGL(fx_plan_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, streams, nstreams, detect, eq, vb_blk, chain, chain_count, stream_base, pjobs, recs, mf_job, mf_c0,
-                       mf_cap, vb_cap, plan_ws);
-    hipLaunchKernelGGL(fx_planlists_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, nstreams, vb_blk, stream_base, pjobs, mf_cap, pll_list, dec_list, list_cap, vb_items, vb_cap,
-                       hdr, hdr_pay, hdr_host, plan_ws);
     return hipGetLastError();
 }
 extern "C" unsigned fx_plan_ws_words(void) { return PW_WORDS; }

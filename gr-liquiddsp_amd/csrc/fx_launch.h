@@ -24,10 +24,8 @@ extern "C" hipError_t fx_launch_blksiso(unsigned fs, unsigned n, unsigned count,
 extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, const FxWalkResult *results,
                                           const FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxBlockHdr *hdr, uint32_t force_repair,
                                           FxWalkJob *jobs_rw, uint32_t *req_list, uint32_t *stat, uint32_t pass);
-extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, const FxStreamDesc *streams, uint32_t nstreams, uint32_t detect, uint32_t eq, uint32_t vb_blk, const FxFrame *chain,
-                                     const uint32_t *chain_count, uint32_t *stream_base, FxPayJob *pjobs, FxOutRec *recs, uint32_t *mf_job, uint32_t *mf_c0, uint32_t mf_cap,
-                                     uint32_t *pll_list, uint32_t *dec_list, uint32_t list_cap, uint32_t *vb_items, uint32_t vb_cap, FxBlockHdr *hdr, FxBlockHdr *hdr_pay,
-                                     FxBlockHdr *hdr_host, uint32_t *plan_ws, int fused);
+// (grid workgroups, clamped; fused: a grid of one takes the one-workgroup kernel)
+extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, int fused, const FxPlanArgs &a);
 extern "C" unsigned fx_plan_ws_words(void);
 // (gang launches, fx_common.h: one launch for up to FX_GANG_MAX blocks; members without waves are left out)
 extern "C" hipError_t fx_launch_vbpre(const FxVbpreGang *gang, hipStream_t st, const FxTables *T, int clean_on, int early_tail);

@@ -23,7 +23,7 @@ import ref_decode as R
 TAIL = 600              # noise behind a piece's last frame: less than the shortest frame (a header alone is 630 samples)
 JUMP_FRAMES, JUMP_ITEMS, JUMP_FACTOR = 200, 2048, 4
 
-# ---- which decoder a frame goes to: the rule of plan_frame / plan_jobs_body (fx_kernels.hip), restated as a table of
+# ---- which decoder a frame goes to: the rule of plan_sizes / plan_key (fx_kernels.hip), restated as a table of
 # (soft decisions, family of fec0, family of fec1) with the families conv (K = 7 convolutional), rs (Reed-Solomon) and other (none, block codes)
 CLASS = {
     (0, "conv", "other"): "batch", (0, "conv", "conv"): "plain", (0, "conv", "rs"): "rs",
