@@ -129,6 +129,17 @@ __device__ __forceinline__ float2 xv(const XSrc &s, int64_t p, int64_t floor_)
 {
     return (p >= floor_ && p < s.n && (p >= 0 || s.xa_end)) ? xld(s, p) : make_float2(0.0f, 0.0f);
 }
+// x[p0, p0 + N) into LDS by NT threads, all of a thread's loads in flight at once (a rolled load / store loop pays the memory
+// latency once per pass)
+template <int NT, int N> __device__ __forceinline__ void load_span(float2 *dst, const XSrc &xs, int64_t p0, int64_t floor_, int tid)
+{
+    constexpr int NLD = (N + NT - 1) / NT;
+    float2 ld[NLD];
+#pragma unroll
+    for (int k = 0; k < NLD; k++) { const int i = tid + NT * k; ld[k] = i < N ? xv(xs, p0 + i, floor_) : make_float2(0.0f, 0.0f); }
+#pragma unroll
+    for (int k = 0; k < NLD; k++) { const int i = tid + NT * k; if (i < N) dst[i] = ld[k]; }
+}
 
 // One hop of the exact detector (qdetector SEEK): L.win holds the 512-sample window (overlap half + new half,
 // published by a barrier), x2_0 / x2_1 the energies of its halves.  Forward FFT, 49-bin CFO sweep, first maximum in
@@ -352,6 +363,166 @@ template <class LDS> __device__ __forceinline__ void decode_header_soft(LDS &L, 
     header_back(L, T, tid);
 }
 
+// ===================================================================== steps the two walkers share (detect_run, walk_run)
+// ALIGN on the 512-sample window `win` (LDS, published; each walker loads it its own way): timing offset and gain from the
+// correlation at lags 0, +1, -1 of CFO bin boff, carrier frequency from the spectral peak of x conj(s), phase from the de-rotated
+// products.  X, P, m2: LDS scratch; scr: wave 0's exchange buffer; L lends S, f[0..3], u[0] and block_csum256's slots.  Whole workgroup.
+template <class LDS>
+__device__ __forceinline__ void align_estimate(const float2 *win, float2 *X, float2 *P, float *m2, float2 *scr, LDS &L, int boff, float s2sum, const FxTables *T, const float2 *sc,
+                                               const float2 (&twA)[7], const float2 (&twB)[7], int tid, float &tau, float &gamma, float &dphi, uint32_t &mix_dl, float &phi)
+{
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (wave == 0) {
+        float2 a[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) a[q] = win[lane + 64 * q];
+        fft512_wave(a, scr, lane, twA, twB);
+        const int kb = (lane >> 3) + 8 * (lane & 7);
+#pragma unroll
+        for (int t = 0; t < 8; t++) X[kb + 64 * t] = a[t];
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int i = lane + 64 * q;
+            float2 y = cmulc(X[i], L.S[(i - boff) & (FX_NFFT - 1)]);
+            a[q] = make_float2(y.y, y.x);
+        }
+        fft512_wave(a, scr, lane, twA, twB);
+        // lags 0, +1, -1 sit in lanes 0 (t=0), 8 (t=0), 63 (t=7)
+        if (lane == 0)  L.f[0] = fmaf(a[0].y, a[0].y, a[0].x * a[0].x);
+        if (lane == 8)  L.f[1] = fmaf(a[0].y, a[0].y, a[0].x * a[0].x);
+        if (lane == 63) L.f[2] = fmaf(a[7].y, a[7].y, a[7].x * a[7].x);
+    }
+    __syncthreads();
+    {
+        float y0 = sqrtf(sqrtf(L.f[0])), ypos = sqrtf(sqrtf(L.f[1])), yneg = sqrtf(sqrtf(L.f[2]));
+        float qa = 0.5f * (ypos + yneg) - y0, qb = 0.5f * (ypos - yneg);
+        tau = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
+        if (!(fabsf(tau) < 1.0f)) tau = 0.0f;
+        float gh = fmaf(fmaf(qa, tau, qb), tau, y0);
+        gamma = gh * gh / ((float)FX_NFFT * s2sum);
+    }
+    // carrier frequency: spectral peak of x conj(s)
+    {
+        float2 p = make_float2(0.0f, 0.0f);
+        if (tid < FX_S_LEN) p = cmulc(win[tid], T->s[tid]);
+        if (tid < HALF) P[tid] = p;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float2 a[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) a[q] = (q < 4) ? P[lane + 64 * q] : make_float2(0.0f, 0.0f);
+        fft512_wave(a, scr, lane, twA, twB);
+        const uint32_t kb = (lane >> 3) + 8 * (lane & 7);
+        float bv = -1.0f; uint32_t bk = 0;
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            float m = cm2(a[t]);
+            m2[kb + 64 * t] = m;
+            if (m > bv) { bv = m; bk = kb + 64 * t; }
+        }
+        wave_argmax(bv, bk);
+        if (lane == 0) { L.f[3] = bv; L.u[0] = bk; }
+    }
+    __syncthreads();
+    {
+        const uint32_t i0 = L.u[0];
+        float v0 = sqrtf(L.f[3]);
+        float vneg = sqrtf(m2[(i0 + FX_NFFT - 1) & (FX_NFFT - 1)]);
+        float vpos = sqrtf(m2[(i0 + 1) & (FX_NFFT - 1)]);
+        float qa = 0.5f * (vpos + vneg) - v0, qb = 0.5f * (vpos - vneg);
+        float idx = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
+        float index = (float)i0 + idx;
+        dphi = (i0 > FX_NFFT / 2 ? index - (float)FX_NFFT : index) * (6.28318531f / (float)FX_NFFT);
+    }
+    mix_dl = rad2u32(dphi);
+    {
+        float2 term = make_float2(0.0f, 0.0f);
+        if (tid < FX_S_LEN) term = derot(P[tid], mix_dl * (uint32_t)tid, sc);
+        float2 metric = block_csum256(term, L, lane, wave);
+        phi = atan2c(metric.y, metric.x);
+    }
+}
+
+// The hand-off of a repair-round (EXT) walker detected (a0, boff).  Is that an exact, floor-clear frame of the list of the segment
+// it falls in (then the lists join there)?  If not, and this walker's frame table has room for that segment (`spacing`: the least
+// distance between two detections of the mode), it carries on to that segment's end: true, and `stop` moves there.  Whole workgroup.
+template <int NT>
+__device__ __forceinline__ bool handoff_extend(const FxWalkJob &job, uint32_t job_index, const FxWalkJob *all_jobs, const FxWalkResult *all_results, uint32_t n_jobs_total,
+                                               const FxFrame *frames, int64_t a0, int boff, int64_t floor_, uint32_t nfr, int spacing, int tid, int64_t &stop)
+{
+    uint32_t k = job_index + 1;                            // the segment the detection falls in (as fx_chain_kernel picks it)
+    while (k + 1 < n_jobs_total && all_jobs[k + 1].stream == job.stream && a0 >= all_jobs[k].stop + FX_HOP) k++;
+    if (!(k < n_jobs_total && all_jobs[k].stream == job.stream)) return false;
+    const FxFrame *FN = frames + all_jobs[k].frame_base;
+    const uint32_t nfn = all_results[k].n_frames;
+    int hit = 0;
+    if (floor_ <= a0)
+        for (uint32_t i = tid; i < nfn; i += NT) {
+            const uint32_t fl = FN[i].flags;
+            if ((fl & FX_FLAG_EXACT) && (fl & FX_FLAG_FLOOR_CLEAR) && FN[i].start == a0 && FN[i].offset == boff) hit = 1;
+        }
+    hit = __syncthreads_or(hit);
+    const int64_t room = (int64_t)job.max_frames - (int64_t)nfr - 8;
+    if (hit || !(room * spacing > all_jobs[k].stop - a0)) return false;
+    stop = all_jobs[k].stop; return true;
+}
+
+struct WalkHandoff { uint32_t has = 0, clear = 0; int64_t start = 0, pos = 0; int32_t off = 0; float rxy = 0.0f; };   // the first detection behind the segment's end
+
+// the frame a fresh detection starts from: ALIGN's estimates and the seek it closes, the rest zero (`next` is the caller's)
+__device__ __forceinline__ FxFrameHead detection_head(int64_t a0, int boff, float peak, float tau, float gamma, float dphi, uint32_t mix_dl, float phi,
+                                                      int64_t span_pos, int64_t span_floor, uint32_t span_flags, int64_t det_pos, int64_t floor_)
+{
+    FxFrameHead fr;
+    fr.start = a0; fr.offset = boff; fr.rxy = peak; fr.tau = tau; fr.gamma = gamma; fr.dphi = dphi; fr.phi = phi;
+    fr.seek_pos = span_pos; fr.seek_floor = span_floor; fr.det_pos = det_pos;
+    fr.pfb = 0; fr.mfc0 = 0; fr.mix_th = rad2u32(phi); fr.mix_dl = mix_dl; fr.mf_scale = 0.0f;
+    fr.pilot_dphi = fr.pilot_phi = fr.pilot_gain = 0.0f; fr.pll_th = 0; fr.pll_f = 0.0f;
+    fr.flags = (floor_ <= a0 ? FX_FLAG_FLOOR_CLEAR : 0u) | span_flags;
+    fr.pay_len = fr.ms = fr.check = fr.fec0 = fr.fec1 = fr.pay_sym_len = 0;
+#pragma unroll
+    for (int j = 0; j < FX_HDR_DEC; j++) fr.header[j] = 0;
+    return fr;
+}
+
+// the result of a walk whose stream state is invalid (one thread)
+__device__ __forceinline__ void write_invalid_result(FxWalkResult *result)
+{
+    FxWalkResult r = {};
+    r.exit_code = FX_EXIT_INVALID; r.fresh = 1; r.tail_flags = FX_FLAG_SPAN_EXACT;
+    *result = r;
+}
+
+// the result of a finished walk and its share of the header's counters (one thread); span_*, tail_flags: the seek in progress
+__device__ __forceinline__ void write_walk_result(FxWalkResult *result, FxBlockHdr *hdr, uint32_t nfr, uint32_t exit_code, int64_t pos, int64_t floor_, bool fresh, const WalkHandoff &ho,
+                                                  uint32_t hops, uint32_t hops_cheap, int64_t span_pos, int64_t span_floor, uint32_t tail_flags, const uint32_t (&stamp)[4])
+{
+    FxWalkResult r;
+    r.n_frames = nfr; r.exit_code = exit_code; r.pos = pos; r.floor = floor_; r.fresh = fresh ? 1u : 0u;
+    r.has_handoff = ho.has; r.handoff_start = ho.start; r.handoff_offset = ho.off; r.hops = hops;
+    r.handoff_rxy = ho.rxy; r.hops_cheap = hops_cheap;
+    r.tail_pos = span_pos; r.tail_floor = span_floor; r.handoff_pos = ho.pos; r.handoff_clear = ho.clear;
+    r.tail_flags = tail_flags;
+    for (int i = 0; i < 4; i++) r.stamp[i] = stamp[i];
+    *result = r;
+    atomicAdd(&hdr->hops, hops); atomicAdd(&hdr->walk_jobs_run, 1u);
+}
+
+// n frames from src to dst within a segment's table (the ranges may overlap: staged, a frame per thread and pass).  Whole workgroup.
+template <int NT>
+__device__ __forceinline__ void move_frames(FxFrame *dst, const FxFrame *src, uint32_t n, int tid)
+{
+    for (uint32_t i0 = 0; i0 < n; i0 += NT) {
+        const uint32_t i = i0 + tid; FxFrame t;
+        if (i < n) t = src[i];
+        __syncthreads();
+        if (i < n) dst[i] = t;
+        __syncthreads();
+    }
+}
+
 // ===================================================================== detector-only walker (frame_detector_cc): a wave per hop
 // In detector mode every hop costs the full sweep (1 forward + 49 inverse FFT-512 + the winner's lag), and a hop is a pure
 // function of (pos, floor).  Between two detections the hop grid is known in advance, so a workgroup takes as many hops as it has
@@ -454,18 +625,12 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
     int64_t pos = job.start, floor_ = job.floor, stop = job.stop;
     int ext_left = 6;
     bool fresh = job.fresh != 0, in_handoff = false, locked = job.prelock == 0;
-    uint32_t nfr = 0, hops = 0, exit_code = FX_EXIT_STOP, has_handoff = 0;
-    int64_t ho_start = 0, ho_pos = 0; int32_t ho_off = 0; float ho_rxy = 0.0f; uint32_t ho_clear = 0;
+    uint32_t nfr = 0, hops = 0, exit_code = FX_EXIT_STOP;
+    WalkHandoff ho;
     if (job.state_in) {
         const FxStreamState st = *job.state_in;
         if (st.invalid) {
-            if (tid == 0) {
-                FxWalkResult r; r.n_frames = 0; r.exit_code = FX_EXIT_INVALID; r.pos = 0; r.floor = 0; r.fresh = 1; r.has_handoff = 0;
-                r.handoff_start = 0; r.handoff_offset = 0; r.hops = 0; r.handoff_rxy = 0.0f; r.hops_cheap = 0; r.tail_pos = 0; r.tail_floor = 0;
-                r.handoff_pos = 0; r.handoff_clear = 0; r.tail_flags = FX_FLAG_SPAN_EXACT;
-                for (int i = 0; i < 4; i++) r.stamp[i] = 0;
-                *result = r;
-            }
+            if (tid == 0) write_invalid_result(result);
             return;
         }
         pos = st.pos; floor_ = st.floor; fresh = st.fresh != 0;
@@ -496,7 +661,6 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
         // (thread index opaque per round: lane-dependent indices are computed where they are used instead of being kept, see walk_run)
         int tid = tid_in; asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const bool lo = tid < HALF;
         pos = uniform64(pos); floor_ = uniform64(floor_);
         nfr = __builtin_amdgcn_readfirstlane(nfr); hops = __builtin_amdgcn_readfirstlane(hops);
         if (pos >= stop && !in_handoff) {
@@ -532,26 +696,9 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
             const int64_t a0 = hp - FX_HOP + (int64_t)bidx;
             if (in_handoff) {
                 bool extend = false;
-                if constexpr (EXT) {
-                    if (ext_left > 0 && all_jobs) {
-                        uint32_t k = job_index + 1;                            // the segment the detection falls in (as fx_chain_kernel picks it)
-                        while (k + 1 < n_jobs_total && all_jobs[k + 1].stream == job.stream && a0 >= all_jobs[k].stop + FX_HOP) k++;
-                        if (k < n_jobs_total && all_jobs[k].stream == job.stream) {
-                            const FxFrame *FN = frames + all_jobs[k].frame_base;
-                            const uint32_t nfn = all_results[k].n_frames;
-                            int hit = 0;
-                            if (floor_ <= a0)
-                                for (uint32_t i = tid; i < nfn; i += NT) {
-                                    const uint32_t fl = FN[i].flags;
-                                    if ((fl & FX_FLAG_EXACT) && (fl & FX_FLAG_FLOOR_CLEAR) && FN[i].start == a0 && FN[i].offset == boff) hit = 1;
-                                }
-                            hit = __syncthreads_or(hit);
-                            const int64_t room = (int64_t)job.max_frames - (int64_t)nfr - 8;
-                            if (!hit && room * FX_HOP > all_jobs[k].stop - a0) { extend = true; stop = all_jobs[k].stop; ext_left--; in_handoff = false; }
-                        }
-                    }
-                }
-                if (!extend) { has_handoff = 1; ho_start = a0; ho_off = boff; ho_rxy = peak; ho_pos = hp; ho_clear = floor_ <= a0 ? 1u : 0u; exit_code = FX_EXIT_STOP; pos = hp; fresh = fresh && h == 0; leave = true; break; }
+                if constexpr (EXT)         // (detections of this mode are a hop apart at the least)
+                    if (ext_left > 0 && all_jobs && handoff_extend<NT>(job, job_index, all_jobs, all_results, n_jobs_total, frames, a0, boff, floor_, nfr, FX_HOP, tid, stop)) { extend = true; ext_left--; in_handoff = false; }
+                if (!extend) { ho.has = 1; ho.start = a0; ho.off = boff; ho.rxy = peak; ho.pos = hp; ho.clear = floor_ <= a0 ? 1u : 0u; exit_code = FX_EXIT_STOP; pos = hp; fresh = fresh && h == 0; leave = true; break; }
             }
             if constexpr (EXT) {
                 if (resync && !in_handoff && floor_ <= a0) {
@@ -569,30 +716,15 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
                         const uint32_t q = hit, n_tail = n_old - q;
                         if (nfr + n_tail <= fcap) {
                             FxFrame *FW = frames + job.frame_base;
-                            // old[q, n_old) behind the new frames, then everything to the front (the two ranges may overlap: staged moves, a frame per thread and pass)
-                            for (uint32_t i0 = 0; i0 < n_tail; i0 += NT) {
-                                const uint32_t i = i0 + tid; FxFrame t;
-                                if (i < n_tail) t = FW[q + i];
-                                __syncthreads();
-                                if (i < n_tail) FW[fbase + nfr + i] = t;
-                                __syncthreads();
-                            }
+                            // old[q, n_old) behind the new frames, then everything to the front
+                            move_frames<NT>(FW + fbase + nfr, FW + q, n_tail, tid);
                             __threadfence(); __syncthreads();
                             const uint32_t n_all = nfr + n_tail;
-                            for (uint32_t i0 = 0; i0 < n_all; i0 += NT) {
-                                const uint32_t i = i0 + tid; FxFrame t;
-                                if (i < n_all) t = FW[fbase + i];
-                                __syncthreads();
-                                if (i < n_all) {
-                                    if (i == nfr) {                     // the frame both walks found: its seek is this walk's (exact), its coarse peak the true chain's
-                                        t.rxy = peak; t.seek_pos = span_pos; t.seek_floor = span_floor; t.det_pos = hp;
-                                        t.flags = (t.flags & ~(uint32_t)(FX_FLAG_SPAN_BAD | FX_FLAG_SEEK_FRESH)) | span_flags;
-                                    }
-                                    FW[i] = t;
-                                }
-                                __syncthreads();
-                            }
+                            move_frames<NT>(FW, FW + fbase, n_all, tid);
                             if (tid == 0) {
+                                FxFrame &t = FW[nfr];           // the frame both walks found: its seek is this walk's (exact), its coarse peak the true chain's
+                                t.rxy = peak; t.seek_pos = span_pos; t.seek_floor = span_floor; t.det_pos = hp;
+                                t.flags = (t.flags & ~(uint32_t)(FX_FLAG_SPAN_BAD | FX_FLAG_SEEK_FRESH)) | span_flags;
                                 FxWalkResult r = old_res;
                                 r.n_frames = n_all; r.hops = hops;
                                 *result = r;
@@ -613,88 +745,10 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
             __syncthreads();
             for (int i = tid; i < FX_NFFT; i += NT) win[i] = xv(xs, a0 + i, floor_);
             __syncthreads();
-            if (wave == 0) {
-                float2 a[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) a[q] = win[lane + 64 * q];
-                fft512_wave(a, L.scr[0], lane, twA, twB);
-                const int kb = (lane >> 3) + 8 * (lane & 7);
-#pragma unroll
-                for (int t = 0; t < 8; t++) X[kb + 64 * t] = a[t];
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int i = lane + 64 * q;
-                    float2 y = cmulc(X[i], L.S[(i - boff) & (FX_NFFT - 1)]);
-                    a[q] = make_float2(y.y, y.x);
-                }
-                fft512_wave(a, L.scr[0], lane, twA, twB);
-                if (lane == 0)  L.f[0] = fmaf(a[0].y, a[0].y, a[0].x * a[0].x);      // lags 0, +1, -1
-                if (lane == 8)  L.f[1] = fmaf(a[0].y, a[0].y, a[0].x * a[0].x);
-                if (lane == 63) L.f[2] = fmaf(a[7].y, a[7].y, a[7].x * a[7].x);
-            }
-            __syncthreads();
-            float tau, gamma;
-            {
-                float y0 = sqrtf(sqrtf(L.f[0])), ypos = sqrtf(sqrtf(L.f[1])), yneg = sqrtf(sqrtf(L.f[2]));
-                float qa = 0.5f * (ypos + yneg) - y0, qb = 0.5f * (ypos - yneg);
-                tau = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
-                if (!(fabsf(tau) < 1.0f)) tau = 0.0f;
-                float gh = fmaf(fmaf(qa, tau, qb), tau, y0);
-                gamma = gh * gh / ((float)FX_NFFT * s2sum);
-            }
-            {
-                float2 p = make_float2(0.0f, 0.0f);
-                if (tid < FX_S_LEN) p = cmulc(win[tid], T->s[tid]);
-                if (lo) P[tid] = p;
-            }
-            __syncthreads();
-            if (wave == 0) {
-                float2 a[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) a[q] = (q < 4) ? P[lane + 64 * q] : make_float2(0.0f, 0.0f);
-                fft512_wave(a, L.scr[0], lane, twA, twB);
-                const uint32_t kb = (lane >> 3) + 8 * (lane & 7);
-                float bv = -1.0f; uint32_t bk = 0;
-#pragma unroll
-                for (int t = 0; t < 8; t++) {
-                    float m = cm2(a[t]);
-                    m2[kb + 64 * t] = m;
-                    if (m > bv) { bv = m; bk = kb + 64 * t; }
-                }
-                wave_argmax(bv, bk);
-                if (lane == 0) { L.f[3] = bv; L.u[0] = bk; }
-            }
-            __syncthreads();
-            float dphi;
-            {
-                const uint32_t i0 = L.u[0];
-                float v0 = sqrtf(L.f[3]);
-                float vneg = sqrtf(m2[(i0 + FX_NFFT - 1) & (FX_NFFT - 1)]);
-                float vpos = sqrtf(m2[(i0 + 1) & (FX_NFFT - 1)]);
-                float qa = 0.5f * (vpos + vneg) - v0, qb = 0.5f * (vpos - vneg);
-                float idx = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
-                float index = (float)i0 + idx;
-                dphi = (i0 > FX_NFFT / 2 ? index - (float)FX_NFFT : index) * (6.28318531f / (float)FX_NFFT);
-            }
-            const uint32_t mix_dl = rad2u32(dphi);
-            float phi;
-            {
-                float2 term = make_float2(0.0f, 0.0f);
-                if (tid < FX_S_LEN) term = derot(P[tid], mix_dl * (uint32_t)tid, sc);
-                float2 metric = block_csum256(term, L, lane, wave);
-                phi = atan2c(metric.y, metric.x);
-            }
-            FxFrameHead fr;
-            fr.start = a0; fr.offset = boff; fr.rxy = peak; fr.tau = tau; fr.gamma = gamma; fr.dphi = dphi; fr.phi = phi;
-            fr.seek_pos = span_pos; fr.seek_floor = span_floor; fr.det_pos = hp;
-            fr.pfb = 0; fr.mfc0 = 0; fr.mix_th = rad2u32(phi); fr.mix_dl = mix_dl; fr.mf_scale = 0.0f;
-            fr.pilot_dphi = fr.pilot_phi = fr.pilot_gain = 0.0f; fr.pll_th = 0; fr.pll_f = 0.0f;
-            fr.flags = (floor_ <= a0 ? FX_FLAG_FLOOR_CLEAR : 0u) | span_flags | FX_FLAG_EXACT;
-            fr.pay_len = fr.ms = fr.check = fr.fec0 = fr.fec1 = fr.pay_sym_len = 0;
-#pragma unroll
-            for (int j = 0; j < FX_HDR_DEC; j++) fr.header[j] = 0;
-            locked = true;
+            float tau, gamma, dphi, phi; uint32_t mix_dl;
+            align_estimate(win, X, P, m2, L.scr[0], L, boff, s2sum, T, sc, twA, twB, tid, tau, gamma, dphi, mix_dl, phi);
+            FxFrameHead fr = detection_head(a0, boff, peak, tau, gamma, dphi, mix_dl, phi, span_pos, span_floor, span_flags, hp, floor_);
+            locked = true; fr.flags |= FX_FLAG_EXACT;
             fr.next = a0 + FX_NFFT;                                       // back to SEEK with the second half of the aligned window as overlap
             if (tid == 0) static_cast<FxFrameHead &>(frames[job.frame_base + fbase + nfr]) = fr;
             nfr++;
@@ -706,35 +760,18 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
         if (!moved) { pos += (int64_t)FX_HOP * nh; fresh = false; }
     }
 
-    if (fbase) {                                                        // a re-walk that never met its old list: its frames to the front
-        __syncthreads();
-        FxFrame *FW = frames + job.frame_base;
-        for (uint32_t i0 = 0; i0 < nfr; i0 += NT) {
-            const uint32_t i = i0 + tid; FxFrame t;
-            if (i < nfr) t = FW[fbase + i];
-            __syncthreads();
-            if (i < nfr) FW[i] = t;
-            __syncthreads();
-        }
-    }
+    // a re-walk that never met its old list: its frames to the front
+    if (fbase) { __syncthreads(); move_frames<NT>(frames + job.frame_base, frames + job.frame_base + fbase, nfr, tid); }
     if (tid == 0) {
-        FxWalkResult r;
-        r.n_frames = nfr; r.exit_code = exit_code; r.pos = pos; r.floor = floor_; r.fresh = fresh ? 1u : 0u;
-        r.has_handoff = has_handoff; r.handoff_start = ho_start; r.handoff_offset = ho_off; r.hops = hops;
-        r.handoff_rxy = ho_rxy; r.hops_cheap = 0;
-        r.tail_pos = span_pos; r.tail_floor = span_floor; r.handoff_pos = ho_pos; r.handoff_clear = ho_clear;
-        r.tail_flags = span_flags;
-        for (int i = 0; i < 4; i++) r.stamp[i] = 0;
+        uint32_t stamp[4] = { 0, 0, 0, 0 };
 #ifdef FX_STAMPS
-        r.stamp[0] = wall0_; r.stamp[1] = (uint32_t)wall_clock64(); r.stamp[2] = __smid();
+        stamp[0] = wall0_; stamp[1] = (uint32_t)wall_clock64(); stamp[2] = __smid();
 #endif
-        *result = r;
-        atomicAdd(&hdr->hops, hops); atomicAdd(&hdr->walk_jobs_run, 1u);
+        write_walk_result(result, hdr, nfr, exit_code, pos, floor_, fresh, ho, hops, 0u, span_pos, span_floor, span_flags, stamp);
     }
 }
 
-// MODE is a template parameter so that the detector-only instance (frame_detector_cc) carries none of the
-// header-recovery code or its registers.
+// ===================================================================== flex_rx walker
 #ifndef FX_DETECT_OCC
 #define FX_DETECT_OCC 4      // waves per SIMD the detector-only instance (and the seek verifier) is compiled for: 128 VGPRs, 4 x 39 KB of LDS per CU
 #endif
@@ -750,6 +787,32 @@ __device__ __forceinline__ void detect_run(const FxWalkJob &job, uint32_t job_in
 #ifndef FX_FLEX_OCC
 #define FX_FLEX_OCC 2        // same for the flex_rx instance
 #endif
+#define FX_FLEX_SPACING 600  // least distance in samples between two detections of a locked flex_rx walker, rounded down (a frame's preamble and header: 618)
+// The coarse correlator behind the differential products d (a: element lane + 64 q), by one wave: transform, product with T->TD,
+// transform back; xp (512 float2, may be scr) takes the transposes.  bv, bk: the largest |.|^2 at a lag below 512 - 156 and that
+// lag, on every lane.  coarse_pass: the scan's test of that peak against e, the energy of d about its mean.
+__device__ __forceinline__ void coarse_peak(float2 (&a)[8], float2 *xp, float2 *scr, const FxTables *T, int lane, const float2 (&twA)[7], const float2 (&twB)[7], float &bv, uint32_t &bk)
+{
+    fft512_wave(a, scr, lane, twA, twB);
+    const int kb = (lane >> 3) + 8 * (lane & 7);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < 8; t++) { float2 y = cmulc(a[t], T->TD[kb + 64 * t]); xp[kb + 64 * t] = make_float2(y.y, y.x); }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < 8; q++) a[q] = xp[lane + 64 * q];
+    if (xp == scr) __builtin_amdgcn_wave_barrier();                            // (the transform is about to write where this wave still reads)
+    fft512_wave(a, scr, lane, twA, twB);
+    bv = -1.0f; bk = 0;
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const uint32_t k = (uint32_t)kb + 64 * t;
+        const float m = cm2(a[t]);
+        if (k < FX_NFFT - FX_S_LEN && m > bv) { bv = m; bk = k; }
+    }
+    wave_argmax(bv, bk);
+}
+__device__ __forceinline__ bool coarse_pass(float bv, float e, const FxTables *T) { return e > 0.0f && bv > 0.06f * e * T->td2sum * (float)FX_NFFT * (float)FX_NFFT; }
 // One hop of the coarse scan, by one wave: the CFO-blind differential correlator d[i] = w[i+1] conj(w[i]) of the 512-sample
 // window w (LDS, published) against the zero-mean differential template T->TD, two transforms through the wave's exchange buffer
 // scr.  The energy of d is taken about its mean (oversampled signals give d a large DC term that is not information).  Returns
@@ -766,26 +829,9 @@ __device__ __forceinline__ bool coarse_hop(const float2 *w, float2 *scr, const F
     }
     e = wave_sum(e); sm.x = wave_sum(sm.x); sm.y = wave_sum(sm.y);
     e -= cm2(sm) * (1.0f / (float)FX_NFFT);
-    fft512_wave(a, scr, lane, twA, twB);
-    const int kb = (lane >> 3) + 8 * (lane & 7);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int t = 0; t < 8; t++) { float2 y = cmulc(a[t], T->TD[kb + 64 * t]); scr[kb + 64 * t] = make_float2(y.y, y.x); }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int q = 0; q < 8; q++) a[q] = scr[lane + 64 * q];
-    __builtin_amdgcn_wave_barrier();
-    fft512_wave(a, scr, lane, twA, twB);
-    float bv = -1.0f; uint32_t bk = 0;
-#pragma unroll
-    for (int t = 0; t < 8; t++) {
-        const uint32_t k = (uint32_t)kb + 64 * t;
-        const float m = cm2(a[t]);
-        if (k < FX_NFFT - FX_S_LEN && m > bv) { bv = m; bk = k; }
-    }
-    wave_argmax(bv, bk);
-    lag = bk;
-    return e > 0.0f && bv > 0.06f * e * T->td2sum * (float)FX_NFFT * (float)FX_NFFT;
+    float bv;
+    coarse_peak(a, scr, scr, T, lane, twA, twB, bv, lag);
+    return coarse_pass(bv, e, T);
 }
 
 // One walk: the synchroniser's state machine from (start, floor, fresh) of `job` until the job's stop / hand-off / end of
@@ -795,7 +841,7 @@ __device__ __forceinline__ bool coarse_hop(const float2 *w, float2 *scr, const F
 // would only be the next round's repair -- the walker looks it up itself and, if it is not there, carries on through that
 // segment as well (a few times at most, and while its frame table has room).
 // SH (fxrx_config.soft_header): the header is decoded from soft values (header_front_soft) instead of hard QPSK decisions.
-template <int MODE, int WW, bool EQ, bool EXT = false, bool SH = false>
+template <int WW, bool EQ, bool EXT = false, bool SH = false>
 __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_index, FxWalkResult *result, FxFrame *frames, FxVerifyRun *runs,
                                          uint32_t run_cap, FxBlockHdr *hdr, const FxTables *T_in, WalkLdsT<WW> &L,
                                          const float2 (&twA)[7], const float2 (&twB)[7],
@@ -811,20 +857,14 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
     int64_t pos = job.start, floor_ = job.floor, stop = job.stop;
     int ext_left = 6;
     bool fresh = job.fresh != 0, in_handoff = false, locked = job.prelock == 0;
-    uint32_t nfr = 0, hops = 0, hops_cheap = 0, exact_left = 0, exit_code = FX_EXIT_STOP, has_handoff = 0;
-    int64_t ho_start = 0, ho_pos = 0; int32_t ho_off = 0; float ho_rxy = 0.0f; uint32_t ho_clear = 0;
+    uint32_t nfr = 0, hops = 0, hops_cheap = 0, exact_left = 0, exit_code = FX_EXIT_STOP;
+    WalkHandoff ho;
     float x2_0 = 0.0f;
     if (job.state_in) {
         // true walker of a continuing stream: the previous block's chain kernel left the resume state on the device
         const FxStreamState st = *job.state_in;
         if (st.invalid) {
-            if (tid == 0) {
-                FxWalkResult r; r.n_frames = 0; r.exit_code = FX_EXIT_INVALID; r.pos = 0; r.floor = 0; r.fresh = 1; r.has_handoff = 0;
-                r.handoff_start = 0; r.handoff_offset = 0; r.hops = 0; r.handoff_rxy = 0.0f; r.hops_cheap = 0; r.tail_pos = 0; r.tail_floor = 0;
-                r.handoff_pos = 0; r.handoff_clear = 0; r.tail_flags = FX_FLAG_SPAN_EXACT;
-                for (int i = 0; i < 4; i++) r.stamp[i] = 0;
-                *result = r;
-            }
+            if (tid == 0) write_invalid_result(result);
             return;
         }
         pos = st.pos; floor_ = st.floor; fresh = st.fresh != 0;
@@ -832,7 +872,7 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
     // A locked flex_rx walker may skip hops its coarse scan finds empty (job.no_skip == 0): it stays on the true hop
     // grid and runs the exact detector only around coarse-scan candidates; every hop between span_pos and the next
     // detection is re-checked by fx_seekverify_kernel (the walker emits the runs itself when the span closes).
-    const bool may_skip = MODE == FX_MODE_FLEXRX && job.no_skip == 0;
+    const bool may_skip = job.no_skip == 0;
     int64_t span_pos = pos, span_floor = floor_;
     // the span is the chain's business only if the walker was locked when the seek began
     uint32_t span_flags = (fresh ? FX_FLAG_SEEK_FRESH : 0u) | ((!may_skip || !locked) ? FX_FLAG_SPAN_EXACT : 0u);
@@ -852,8 +892,9 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         }
         return false;
     };
+    uint32_t wst_[4] = { 0, 0, 0, 0 };                          // phase clocks of an FX_STAMPS build
 #ifdef FX_STAMPS
-    unsigned long long wt_ = __builtin_readcyclecounter(); uint32_t wst_[4] = { 0, 0, 0, 0 };
+    unsigned long long wt_ = __builtin_readcyclecounter();
 #define WSTAMP(i) do { unsigned long long t2_ = __builtin_readcyclecounter(); wst_[i] += (uint32_t)(t2_ - wt_); wt_ = t2_; } while (0)
 #else
 #define WSTAMP(i) do { } while (0)
@@ -865,7 +906,7 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
     // the first chunk word with a hit is what the unlocked candidate branch below would have found -- the exact detector takes
     // over on the hop whose new half starts at the candidate, behind a reset one hop earlier --; no hit, and the walker's own
     // scan carries on behind the scanned hops.  Nothing found before the lock is ever spliced, so either way the result is exact.
-    if (MODE == FX_MODE_FLEXRX && !EXT && job.prelock && job.prescan && !job.state_in) {
+    if (!EXT && job.prelock && job.prescan && !job.state_in) {
         int64_t p; uint32_t scanned;
         const bool took = fx_prescan_entry(job.prescan, job.prescan_words, job.prescan_hops, job.start, &p, &scanned);
         if (took) { pos = p; floor_ = p - FX_HOP; fresh = false; exact_left = 2; }
@@ -905,17 +946,10 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         // ------------------------------------------------------------ pre-lock coarse scan, four hops at a time
         // (same differential correlator as the single-hop form below, one window per wave, no block barriers
         // inside; used while at least four hops remain before the segment end / end of data)
-        if ((!locked || may_skip) && MODE == FX_MODE_FLEXRX && exact_left == 0 && pos + WALK_WAVES * FX_HOP <= n &&
+        if ((!locked || may_skip) && exact_left == 0 && pos + WALK_WAVES * FX_HOP <= n &&
             (in_handoff || pos + (WALK_WAVES - 1) * FX_HOP < stop)) {
             __syncthreads();
-            {   // (all of a thread's loads in flight at once: a rolled load / store loop pays the memory latency once per pass)
-                constexpr int NLD = ((WALK_WAVES + 1) * FX_HOP + WALK_THREADS - 1) / WALK_THREADS;
-                float2 ld[NLD];
-#pragma unroll
-                for (int k = 0; k < NLD; k++) { const int i = tid + WALK_THREADS * k; ld[k] = i < (WALK_WAVES + 1) * FX_HOP ? xv(xs, pos - FX_HOP + i, floor_) : make_float2(0.0f, 0.0f); }
-#pragma unroll
-                for (int k = 0; k < NLD; k++) { const int i = tid + WALK_THREADS * k; if (i < (WALK_WAVES + 1) * FX_HOP) L.cw[i] = ld[k]; }
-            }
+            load_span<WALK_THREADS, (WALK_WAVES + 1) * FX_HOP>(L.cw, xs, pos - FX_HOP, floor_, tid);
             __syncthreads();
             hops_cheap += WALK_WAVES;
             {
@@ -972,7 +1006,7 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         // instead of the 50 of the real detector: d[i] = w[i+1] conj(w[i]) against the zero-mean td[k] = s[k+1] conj(s[k]).
         // A hit at lag l re-arms the exact detector (fresh) one hop before the candidate.
         bool coarse_hit = false;
-        if ((!locked || may_skip) && MODE == FX_MODE_FLEXRX && exact_left == 0) {
+        if ((!locked || may_skip) && exact_left == 0) {
             __syncthreads();
             hops_cheap++;
             float2 d0 = lo ? cmulc(L.win[tid + 1], L.win[tid]) : make_float2(0.0f, 0.0f);
@@ -986,28 +1020,13 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
                 float2 a[8];
 #pragma unroll
                 for (int q = 0; q < 8; q++) a[q] = L.X[lane + 64 * q];
-                fft512_wave(a, L.scr[0], lane, twA, twB);
-                const int kb = (lane >> 3) + 8 * (lane & 7);
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int t = 0; t < 8; t++) { float2 y = cmulc(a[t], T->TD[kb + 64 * t]); L.X[kb + 64 * t] = make_float2(y.y, y.x); }
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int q = 0; q < 8; q++) a[q] = L.X[lane + 64 * q];
-                fft512_wave(a, L.scr[0], lane, twA, twB);
-                float bv = -1.0f; uint32_t bk = 0;
-#pragma unroll
-                for (int t = 0; t < 8; t++) {
-                    const uint32_t k = (uint32_t)kb + 64 * t;
-                    const float m = cm2(a[t]);
-                    if (k < FX_NFFT - FX_S_LEN && m > bv) { bv = m; bk = k; }
-                }
-                wave_argmax(bv, bk);
+                float bv; uint32_t bk;
+                coarse_peak(a, L.X, L.scr[0], T, lane, twA, twB, bv, bk);
                 if (lane == 0) { L.f[4] = bv; L.u[8] = bk; }
             }
             __syncthreads();
             const float cpk = L.f[4]; const uint32_t cl = L.u[8];
-            if (cpk > 0.06f * ed * T->td2sum * (float)FX_NFFT * (float)FX_NFFT && ed > 0.0f) {
+            if (coarse_pass(cpk, ed, T)) {
                 if (locked) { coarse_hit = true; exact_left = cl >= FX_NFFT - FX_S_LEN - 12u ? 2 : 1; hops_cheap--; }   // run the exact detector on this very hop
                 else {
                     // candidate preamble at p: the exact detector takes over on the hop whose new half starts at p (see above)
@@ -1048,152 +1067,21 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         const int64_t a0 = pos - FX_HOP + (int64_t)bidx;
         if (in_handoff) {
             bool extend = false;
-            if constexpr (EXT) {
-                if (ext_left > 0 && all_jobs) {
-                    uint32_t k = job_index + 1;                            // the segment the detection falls in (as fx_chain_kernel picks it)
-                    while (k + 1 < n_jobs_total && all_jobs[k + 1].stream == job.stream && a0 >= all_jobs[k].stop + FX_HOP) k++;
-                    if (k < n_jobs_total && all_jobs[k].stream == job.stream) {
-                        const FxFrame *FN = frames + all_jobs[k].frame_base;
-                        const uint32_t nfn = all_results[k].n_frames;
-                        int hit = 0;
-                        if (floor_ <= a0)
-                            for (uint32_t i = tid; i < nfn; i += WALK_THREADS) {
-                                const uint32_t fl = FN[i].flags;
-                                if ((fl & FX_FLAG_EXACT) && (fl & FX_FLAG_FLOOR_CLEAR) && FN[i].start == a0 && FN[i].offset == boff) hit = 1;
-                            }
-                        hit = __syncthreads_or(hit);
-                        const int64_t room = (int64_t)job.max_frames - (int64_t)nfr - 8;
-                        if (!hit && room * 600 > all_jobs[k].stop - a0) { extend = true; stop = all_jobs[k].stop; ext_left--; in_handoff = false; }
-                    }
-                }
-            }
-            if (!extend) { has_handoff = 1; ho_start = a0; ho_off = boff; ho_rxy = peak; ho_pos = pos; ho_clear = floor_ <= a0 ? 1u : 0u; exit_code = FX_EXIT_STOP; break; }
+            if constexpr (EXT)
+                if (ext_left > 0 && all_jobs && handoff_extend<WALK_THREADS>(job, job_index, all_jobs, all_results, n_jobs_total, frames, a0, boff, floor_, nfr, FX_FLEX_SPACING, tid, stop)) { extend = true; ext_left--; in_handoff = false; }
+            if (!extend) { ho.has = 1; ho.start = a0; ho.off = boff; ho.rxy = peak; ho.pos = pos; ho.clear = floor_ <= a0 ? 1u : 0u; exit_code = FX_EXIT_STOP; break; }
         }
         if (nfr >= job.max_frames) { exit_code = FX_EXIT_TABLE_FULL; break; }
         if (a0 + FX_NFFT > n) { exit_code = FX_EXIT_NEED_DATA; break; }
 
         // ------------------------------------------------------------ ALIGN on x[a0, a0+512)
         __syncthreads();
-        {
-            constexpr int NLD = (FX_NFFT + WALK_THREADS - 1) / WALK_THREADS;
-            float2 ld[NLD];
-#pragma unroll
-            for (int k = 0; k < NLD; k++) { const int i = tid + WALK_THREADS * k; ld[k] = i < FX_NFFT ? xv(xs, a0 + i, floor_) : make_float2(0.0f, 0.0f); }
-#pragma unroll
-            for (int k = 0; k < NLD; k++) { const int i = tid + WALK_THREADS * k; if (i < FX_NFFT) L.win[i] = ld[k]; }
-        }
+        load_span<WALK_THREADS, FX_NFFT>(L.win, xs, a0, floor_, tid);
         __syncthreads();
-        if (wave == 0) {
-            float2 a[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) a[q] = L.win[lane + 64 * q];
-            fft512_wave(a, L.scr[0], lane, twA, twB);
-            const int kb = (lane >> 3) + 8 * (lane & 7);
-#pragma unroll
-            for (int t = 0; t < 8; t++) L.X[kb + 64 * t] = a[t];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const int i = lane + 64 * q;
-                float2 y = cmulc(L.X[i], L.S[(i - boff) & (FX_NFFT - 1)]);
-                a[q] = make_float2(y.y, y.x);
-            }
-            fft512_wave(a, L.scr[0], lane, twA, twB);
-            // lags 0, +1, -1 sit in lanes 0 (t=0), 8 (t=0), 63 (t=7)
-            if (lane == 0)  L.f[0] = fmaf(a[0].y, a[0].y, a[0].x * a[0].x);
-            if (lane == 8)  L.f[1] = fmaf(a[0].y, a[0].y, a[0].x * a[0].x);
-            if (lane == 63) L.f[2] = fmaf(a[7].y, a[7].y, a[7].x * a[7].x);
-        }
-        __syncthreads();
-        float tau, gamma;
-        {
-            float y0 = sqrtf(sqrtf(L.f[0])), ypos = sqrtf(sqrtf(L.f[1])), yneg = sqrtf(sqrtf(L.f[2]));
-            float qa = 0.5f * (ypos + yneg) - y0, qb = 0.5f * (ypos - yneg);
-            tau = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
-            if (!(fabsf(tau) < 1.0f)) tau = 0.0f;
-            float gh = fmaf(fmaf(qa, tau, qb), tau, y0);
-            gamma = gh * gh / ((float)FX_NFFT * s2sum);
-        }
-        // carrier frequency: spectral peak of x conj(s)
-        {
-            float2 p = make_float2(0.0f, 0.0f);
-            if (tid < FX_S_LEN) p = cmulc(L.win[tid], T->s[tid]);
-            if (lo) L.P[tid] = p;
-        }
-        __syncthreads();
-        if (wave == 0) {
-            float2 a[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) a[q] = (q < 4) ? L.P[lane + 64 * q] : make_float2(0.0f, 0.0f);
-            fft512_wave(a, L.scr[0], lane, twA, twB);
-            const uint32_t kb = (lane >> 3) + 8 * (lane & 7);
-            float bv = -1.0f; uint32_t bk = 0;
-#pragma unroll
-            for (int t = 0; t < 8; t++) {
-                float m = cm2(a[t]);
-                L.m2[kb + 64 * t] = m;
-                if (m > bv) { bv = m; bk = kb + 64 * t; }
-            }
-            wave_argmax(bv, bk);
-            if (lane == 0) { L.f[3] = bv; L.u[0] = bk; }
-        }
-        __syncthreads();
-        float dphi;
-        {
-            const uint32_t i0 = L.u[0];
-            float v0 = sqrtf(L.f[3]);
-            float vneg = sqrtf(L.m2[(i0 + FX_NFFT - 1) & (FX_NFFT - 1)]);
-            float vpos = sqrtf(L.m2[(i0 + 1) & (FX_NFFT - 1)]);
-            float qa = 0.5f * (vpos + vneg) - v0, qb = 0.5f * (vpos - vneg);
-            float idx = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
-            float index = (float)i0 + idx;
-            dphi = (i0 > FX_NFFT / 2 ? index - (float)FX_NFFT : index) * (6.28318531f / (float)FX_NFFT);
-        }
-        const uint32_t mix_dl = rad2u32(dphi);
-        float phi;
-        {
-            float2 term = make_float2(0.0f, 0.0f);
-            if (tid < FX_S_LEN) term = derot(L.P[tid], mix_dl * (uint32_t)tid, sc);
-            float2 metric = block_csum256(term, L, lane, wave);
-            phi = atan2c(metric.y, metric.x);
-        }
-
+        float tau, gamma, dphi, phi; uint32_t mix_dl;
+        align_estimate(L.win, L.X, L.P, L.m2, L.scr[0], L, boff, s2sum, T, sc, twA, twB, tid, tau, gamma, dphi, mix_dl, phi);
         WSTAMP(2);
-        FxFrameHead fr;
-        fr.start = a0; fr.offset = boff; fr.rxy = peak; fr.tau = tau; fr.gamma = gamma; fr.dphi = dphi; fr.phi = phi;
-        fr.seek_pos = span_pos; fr.seek_floor = span_floor; fr.det_pos = pos;
-        fr.pfb = 0; fr.mfc0 = 0; fr.mix_th = rad2u32(phi); fr.mix_dl = mix_dl; fr.mf_scale = 0.0f;
-        fr.pilot_dphi = fr.pilot_phi = fr.pilot_gain = 0.0f; fr.pll_th = 0; fr.pll_f = 0.0f; fr.flags = (floor_ <= a0 ? FX_FLAG_FLOOR_CLEAR : 0u) | span_flags;
-        fr.pay_len = fr.ms = fr.check = fr.fec0 = fr.fec1 = fr.pay_sym_len = 0;
-#pragma unroll
-        for (int j = 0; j < FX_HDR_DEC; j++) fr.header[j] = 0;
-
-        if (MODE == FX_MODE_DETECT) {
-            // Speculative walker not yet locked: a weak peak may be a false alarm the sequential chain
-            // never sees (its hop grid differs).  Ignore it and keep the grid; lock on a strong one.
-            if (!locked && !(peak > 0.7f)) {
-                __syncthreads();
-                if (lo) { L.win[tid] = nw; L.win[FX_HOP + tid] = make_float2(0.0f, 0.0f); }
-                x2_0 = x2_1; pos += FX_HOP; fresh = false;
-                __syncthreads();
-                continue;
-            }
-            locked = true; fr.flags |= FX_FLAG_EXACT;
-            // back to SEEK with the second half of the aligned window as overlap
-            fr.next = a0 + FX_NFFT;
-            if (tid == 0) static_cast<FxFrameHead &>(frames[job.frame_base + nfr]) = fr;
-            nfr++;
-            span_pos = a0 + FX_NFFT; span_floor = floor_; span_flags = FX_FLAG_SPAN_EXACT;
-            __syncthreads();
-            float2 w = lo ? L.win[FX_HOP + tid] : make_float2(0.0f, 0.0f);
-            __syncthreads();
-            if (lo) L.win[tid] = w;
-            x2_0 = block_sum256(cm2(w), L, lane, wave);
-            pos = a0 + FX_NFFT; fresh = false;
-            __syncthreads();
-            continue;
-        }
-
+        FxFrameHead fr = detection_head(a0, boff, peak, tau, gamma, dphi, mix_dl, phi, span_pos, span_floor, span_flags, pos, floor_);
         // ------------------------------------------------------------ flex_rx: preamble + header span
         if (tau > 0.0f) { fr.pfb = (unsigned)f2i_sat(tau * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 0; }
         else { fr.pfb = (unsigned)f2i_sat((1.0f + tau) * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 1; }
@@ -1385,21 +1273,10 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
     }
 
     if (tid == 0) {
-        FxWalkResult r;
-        r.n_frames = nfr; r.exit_code = exit_code; r.pos = pos; r.floor = floor_; r.fresh = fresh ? 1u : 0u;
-        r.has_handoff = has_handoff; r.handoff_start = ho_start; r.handoff_offset = ho_off; r.hops = hops;
-        r.handoff_rxy = ho_rxy; r.hops_cheap = hops_cheap;
-        r.tail_pos = span_pos; r.tail_floor = span_floor; r.handoff_pos = ho_pos; r.handoff_clear = ho_clear;
-        // the seek in progress: a frame cut short by the end of data is walked again by the next block, from this very state
-        r.tail_flags = span_flags;
-        if (emit_runs(has_handoff ? ho_pos : pos, 0x80000000u | job_index)) r.tail_flags |= FX_FLAG_SPAN_BAD;
-#ifdef FX_STAMPS
-        for (int i = 0; i < 4; i++) r.stamp[i] = wst_[i];
-#else
-        for (int i = 0; i < 4; i++) r.stamp[i] = 0;
-#endif
-        *result = r;
-        atomicAdd(&hdr->hops, hops); atomicAdd(&hdr->hops_cheap, hops_cheap); atomicAdd(&hdr->walk_jobs_run, 1u);
+        uint32_t tail_flags = span_flags;
+        if (emit_runs(ho.has ? ho.pos : pos, 0x80000000u | job_index)) tail_flags |= FX_FLAG_SPAN_BAD;
+        write_walk_result(result, hdr, nfr, exit_code, pos, floor_, fresh, ho, hops, hops_cheap, span_pos, span_floor, tail_flags, wst_);
+        atomicAdd(&hdr->hops_cheap, hops_cheap);
     }
 }
 
@@ -1412,7 +1289,7 @@ __device__ __forceinline__ void walk_any(const FxWalkJob &job, uint32_t job_inde
                                          const FxWalkJob *all_jobs = nullptr, const FxWalkResult *all_results = nullptr, uint32_t n_jobs_total = 0)
 {
     if constexpr (MODE == FX_MODE_DETECT) detect_run<WW, EXT>(job, job_index, result, frames, hdr, T, L, twA, twB, all_jobs, all_results, n_jobs_total);
-    else walk_run<MODE, WW, EQ, EXT, SH>(job, job_index, result, frames, runs, run_cap, hdr, T, L, twA, twB, all_jobs, all_results, n_jobs_total);
+    else walk_run<WW, EQ, EXT, SH>(job, job_index, result, frames, runs, run_cap, hdr, T, L, twA, twB, all_jobs, all_results, n_jobs_total);
 }
 
 // SH: the soft-header walker (fxrx_config.soft_header; flex_rx only).  Like EQ and EXT it is a template argument: an instance's code
@@ -1505,14 +1382,7 @@ void fx_prescan_kernel(const FxWalkJob *jobs, const uint32_t *spec_list, uint32_
         if (h0 >= nvalid) break;
         const int64_t pos = job.start + (int64_t)FX_HOP * h0;
         __syncthreads();
-        {   // (all of a thread's loads in flight at once, as in the walker's round; xv() reads zeros beyond the data)
-            constexpr int NLD = ((PRESCAN_WAVES + 1) * FX_HOP + THREADS - 1) / THREADS;
-            float2 ld[NLD];
-#pragma unroll
-            for (int k = 0; k < NLD; k++) { const int i = tid + THREADS * k; ld[k] = i < (PRESCAN_WAVES + 1) * FX_HOP ? xv(xs, pos - FX_HOP + i, floor_) : make_float2(0.0f, 0.0f); }
-#pragma unroll
-            for (int k = 0; k < NLD; k++) { const int i = tid + THREADS * k; if (i < (PRESCAN_WAVES + 1) * FX_HOP) L.cw[i] = ld[k]; }
-        }
+        load_span<THREADS, (PRESCAN_WAVES + 1) * FX_HOP>(L.cw, xs, pos - FX_HOP, floor_, tid);      // (xv() reads zeros beyond the data)
         __syncthreads();
         {
             uint32_t bk;
@@ -3242,8 +3112,15 @@ __device__ __forceinline__ unsigned sb_ml(const uint32_t (&sw)[(N + 3) / 4], con
     return best & ((1u << K) - 1u);
 }
 
-// Golay(24,12), Chase-4, one codeword (24 soft values) -> its 12 data bits
-__device__ __forceinline__ unsigned sb_golay(const uint32_t (&sw)[6], const FxTables *T)
+// The Chase-4 decoders, one text for the hard output (block_fec_decode_soft) and the soft output (block_fec_decode_siso): hard
+// word, four least reliable positions, sixteen flip patterns, the hard decoder's success test, cost of the re-encoded output, ties
+// to the smallest pattern ((cost << 4) | p).  best: the winner's key or ~0 (none); dm: its message bits as a position mask (bit i
+// = message bit i, MSB-first order of the output), or the hard word's.  KEEP: cc[p], cm[p] of every candidate too (SISO_INF: none).
+#define SISO_INF 0x7fffffffu
+
+// Golay(24,12), one codeword (24 soft values): message bit i is codeword position i
+template <bool KEEP>
+__device__ __forceinline__ void sb_golay_chase(const uint32_t (&sw)[6], const FxTables *T, uint32_t &best, uint32_t &dm, uint32_t *cc = nullptr, uint32_t *cm = nullptr)
 {
     uint32_t pm[1], t[4], tr[4], tc[4];
     sb_hard<6>(sw, pm);
@@ -3256,28 +3133,47 @@ __device__ __forceinline__ unsigned sb_golay(const uint32_t (&sw)[6], const FxTa
         tr[j] = 1u << q;
         tc[j] = q >= 12u ? T->golenc[1u << (q - 12u)] & 0xfffu : tr[j];     // the syndrome of that one bit
     }
-    uint32_t best = ~0u, bd = r >> 12;
+    best = ~0u; dm = pm[0] & 0xfffu;
 #pragma unroll
     for (int p = 0; p < 16; p++) {
         uint32_t s = syn, rp = r;
 #pragma unroll
         for (int j = 0; j < 4; j++) if (p & (1 << j)) { s ^= tc[j]; rp ^= tr[j]; }
         const uint32_t e = T->golerr[s];
+        if constexpr (KEEP) { cc[p] = SISO_INF; cm[p] = 0; }
         if (e != 0xFFFFFFFFu) {
             // e has syndrome s, so rp ^ e is the codeword of its data: the re-encoding of the hard decoder's output
-            const uint32_t c = rp ^ e, cm[1] = { __builtin_bitreverse32(c) >> 8 };
-            const uint32_t key = (sb_cost<6>(sw, cm) << 4) | (uint32_t)p;
-            if (key < best) { best = key; bd = c >> 12; }
+            const uint32_t cw[1] = { __builtin_bitreverse32(rp ^ e) >> 8 };
+            const uint32_t cost = sb_cost<6>(sw, cw), key = (cost << 4) | (uint32_t)p;
+            if constexpr (KEEP) { cc[p] = cost; cm[p] = cw[0] & 0xfffu; }
+            if (key < best) { best = key; dm = cw[0] & 0xfffu; }
         }
     }
-    return bd & 0xfffu;
+}
+// -> its 12 data bits, MSB first (a bit reversal away from the position mask)
+__device__ __forceinline__ unsigned sb_golay(const uint32_t (&sw)[6], const FxTables *T)
+{
+    uint32_t best, dm;
+    sb_golay_chase<false>(sw, T, best, dm);
+    return __builtin_bitreverse32(dm) >> 20;
 }
 
-// SECDED with ND data bytes per block, Chase-4, one block: its soft values at S (parity byte's 8, then the data bits), nb data
-// bytes transmitted; `inv`: syndrome -> data column index + 1 (0: none).  Writes the nb data bytes to dec.
-template <int ND>
-__device__ __forceinline__ void sb_secded_block(const uint8_t *S, uint32_t nb, const uint8_t *col, const uint8_t *inv, uint8_t *dec)
+// SECDED with ND data bytes per block, one block: its soft values at S (parity byte's 8, then the data bits), nb data bytes
+// transmitted; `inv`: syndrome -> data column index + 1 (0: none).  Message bit i is codeword position 8 + i.
+template <int ND> struct siso_mask { typedef uint32_t type; };
+template <> struct siso_mask<8> { typedef unsigned long long type; };
+template <int M, class MT>
+__device__ __forceinline__ MT siso_data_mask(const uint32_t (&c)[M])
 {
+    if constexpr (M == 1) return (MT)(c[0] >> 8);
+    else if constexpr (M == 2) return (MT)((c[0] >> 8) | (c[1] << 24));
+    else return (MT)(c[0] >> 8) | ((MT)c[1] << 24) | ((MT)c[2] << 56);
+}
+template <int ND, bool KEEP>
+__device__ __forceinline__ void sb_secded_chase(const uint8_t *S, uint32_t nb, const uint8_t *col, const uint8_t *inv, uint32_t &best, typename siso_mask<ND>::type &dm,
+                                                uint32_t *cc = nullptr, typename siso_mask<ND>::type *cm = nullptr)
+{
+    typedef typename siso_mask<ND>::type MT;
     constexpr int W = 2 + 2 * ND, M = (W + 7) / 8;
     const uint32_t nvalid = 8u + 8u * nb;
     uint32_t sw[W], y[M], t[4], tm[4][M], tc[4];
@@ -3294,7 +3190,8 @@ __device__ __forceinline__ void sb_secded_block(const uint8_t *S, uint32_t nb, c
         sb_flip<M>(tm[j], t[j]);
         tc[j] = t[j] < 8u ? 0x80u >> t[j] : (uint32_t)col[t[j] - 8u];
     }
-    uint32_t best = ~0u, bc[M];
+    uint32_t bc[M];
+    best = ~0u;
 #pragma unroll
     for (int i = 0; i < M; i++) bc[i] = y[i];
 #pragma unroll
@@ -3311,11 +3208,12 @@ __device__ __forceinline__ void sb_secded_block(const uint8_t *S, uint32_t nb, c
         // success: syndrome 0, of weight 1 (a parity bit), or a data column.  The candidate is the re-encoded output: a data bit
         // flipped if its column is transmitted, else the parity byte re-computed (received parity ^ syndrome)
         const uint32_t iv = inv[s];
-        const bool ok = s == 0u || __popc(s) == 1u || iv != 0u;
-        if (ok) {
+        if constexpr (KEEP) { cc[p] = SISO_INF; cm[p] = 0; }
+        if (s == 0u || __popc(s) == 1u || iv != 0u) {
             if (iv != 0u && iv - 1u < 8u * nb) sb_flip<M>(c, 8u + iv - 1u);
             else c[0] ^= __builtin_bitreverse32(s) >> 24;
-            const uint32_t key = (sb_cost<W>(sw, c) << 4) | (uint32_t)p;
+            const uint32_t cost = sb_cost<W>(sw, c), key = (cost << 4) | (uint32_t)p;
+            if constexpr (KEEP) { cc[p] = cost; cm[p] = siso_data_mask<M, MT>(c); }
             if (key < best) {
                 best = key;
 #pragma unroll
@@ -3323,9 +3221,17 @@ __device__ __forceinline__ void sb_secded_block(const uint8_t *S, uint32_t nb, c
             }
         }
     }
+    dm = siso_data_mask<M, MT>(bc);
+}
+// writes the nb data bytes to dec
+template <int ND>
+__device__ __forceinline__ void sb_secded_block(const uint8_t *S, uint32_t nb, const uint8_t *col, const uint8_t *inv, uint8_t *dec)
+{
+    uint32_t best; typename siso_mask<ND>::type dm;
+    sb_secded_chase<ND, false>(S, nb, col, inv, best, dm);
 #pragma unroll
     for (int j = 0; j < ND; j++)
-        if ((uint32_t)j < nb) dec[j] = (uint8_t)(__builtin_bitreverse32((bc[(8 + 8 * j) >> 5] >> ((8 + 8 * j) & 31)) & 255u) >> 24);
+        if ((uint32_t)j < nb) dec[j] = (uint8_t)(__builtin_bitreverse32((uint32_t)(dm >> (8 * j)) & 255u) >> 24);
 }
 
 template <int ND>
@@ -3395,14 +3301,13 @@ __device__ __forceinline__ void block_fec_decode_soft(unsigned fs, uint32_t n, c
 // block_fec_decode_soft's decoders, emitting one soft value per message bit (0 = surely 0 ... 255 = surely 1, in the order of the
 // output bytes, MSB first) instead of hard bytes, so that a convolutional fec0 behind a block fec1 decodes with the soft-input
 // Viterbi.  The rule is this project's (include/fxrx.h), integers only:
-//   d = block_fec_decode_soft's message (same ties), C = the cost above, L_i >= 0 the margin of message bit i,
+//   d = block_fec_decode_soft's message (the same routines: sb_ml's rule, sb_golay_chase, sb_secded_chase), C = the cost above, L_i >= 0 the margin of message bit i,
 //   o_i = d_i ? min(255, max(128, (255 + L_i + 1) >> 1)) : max(0, min(127, (255 - L_i) >> 1))        -- o_i > 127 <=> d_i = 1
 //   Hamming codes: L_i = min{C(c) : m_i != d_i} - C(d) over all codewords (max-log-MAP) = |min over m_i = 1 - min over m_i = 0|;
 //   Golay, SECDED: the same minimum over the Chase candidates (the successful re-encodings); no such candidate: L_i = 255; no
 //     candidate at all (the output is the hard decoder's on the hard word): o_i = d_i ? 192 : 64 (SISO_NO_CANDIDATE).
 // Positions a short last block does not transmit and padding bits past 8 n are not emitted.
 #define SISO_NO_CANDIDATE 64u                   // distance from 128 of an output bit that no Chase candidate backs; not tuned
-#define SISO_INF 0x7fffffffu
 
 // decision d and margin L (any size; saturates from 254 / 255 on) -> the soft output
 __device__ __forceinline__ uint32_t siso_out(uint32_t d, uint32_t L)
@@ -3477,92 +3382,6 @@ __device__ __forceinline__ void siso_chase_out(const uint32_t (&cc)[16], const M
     }
 }
 
-// Golay(24,12), Chase-4 (sb_golay), keeping every candidate: message bit i is codeword position i
-__device__ __forceinline__ void sb_golay_siso(const uint32_t (&sw)[6], const FxTables *T, uint32_t (&cc)[16], uint32_t (&cm)[16], uint32_t &best, uint32_t &dm)
-{
-    uint32_t pm[1], t[4], tr[4], tc[4];
-    sb_hard<6>(sw, pm);
-    sb_least4<6>(sw, 24u, t);
-    const uint32_t r = __builtin_bitreverse32(pm[0]) >> 8;                     // received word, MSB first (position b = bit 23 - b)
-    const uint32_t syn = (T->golenc[r >> 12] ^ r) & 0xfffu;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const uint32_t q = 23u - t[j];
-        tr[j] = 1u << q;
-        tc[j] = q >= 12u ? T->golenc[1u << (q - 12u)] & 0xfffu : tr[j];
-    }
-    best = ~0u; dm = pm[0] & 0xfffu;
-#pragma unroll
-    for (int p = 0; p < 16; p++) {
-        uint32_t s = syn, rp = r;
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (p & (1 << j)) { s ^= tc[j]; rp ^= tr[j]; }
-        const uint32_t e = T->golerr[s];
-        cc[p] = SISO_INF; cm[p] = 0;
-        if (e != 0xFFFFFFFFu) {
-            const uint32_t cw[1] = { __builtin_bitreverse32(rp ^ e) >> 8 };
-            cc[p] = sb_cost<6>(sw, cw); cm[p] = cw[0] & 0xfffu;
-            const uint32_t key = (cc[p] << 4) | (uint32_t)p;
-            if (key < best) { best = key; dm = cm[p]; }
-        }
-    }
-}
-
-// SECDED, Chase-4 (sb_secded_block), keeping every candidate: message bit i is codeword position 8 + i
-template <int ND> struct siso_mask { typedef uint32_t type; };
-template <> struct siso_mask<8> { typedef unsigned long long type; };
-template <int M, class MT>
-__device__ __forceinline__ MT siso_data_mask(const uint32_t (&c)[M])
-{
-    if constexpr (M == 1) return (MT)(c[0] >> 8);
-    else if constexpr (M == 2) return (MT)((c[0] >> 8) | (c[1] << 24));
-    else return (MT)(c[0] >> 8) | ((MT)c[1] << 24) | ((MT)c[2] << 56);
-}
-template <int ND>
-__device__ __forceinline__ void sb_secded_siso(const uint8_t *S, uint32_t nb, const uint8_t *col, const uint8_t *inv, uint32_t (&cc)[16],
-                                               typename siso_mask<ND>::type (&cm)[16], uint32_t &best, typename siso_mask<ND>::type &dm)
-{
-    typedef typename siso_mask<ND>::type MT;
-    constexpr int W = 2 + 2 * ND, M = (W + 7) / 8;
-    const uint32_t nvalid = 8u + 8u * nb;
-    uint32_t sw[W], y[M], t[4], tm[4][M], tc[4];
-    sb_load<W>(S, nvalid / 4u, sw);
-    sb_hard<W>(sw, y);
-    sb_least4<W>(sw, nvalid, t);
-    uint32_t syn = __builtin_bitreverse32(y[0]) >> 24;
-#pragma unroll
-    for (int j = 0; j < 8 * ND; j++) if ((y[(8 + j) >> 5] >> ((8 + j) & 31)) & 1u) syn ^= col[j];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-#pragma unroll
-        for (int i = 0; i < M; i++) tm[j][i] = 0;
-        sb_flip<M>(tm[j], t[j]);
-        tc[j] = t[j] < 8u ? 0x80u >> t[j] : (uint32_t)col[t[j] - 8u];
-    }
-    best = ~0u; dm = siso_data_mask<M, MT>(y);
-#pragma unroll
-    for (int p = 0; p < 16; p++) {
-        uint32_t s = syn, c[M];
-#pragma unroll
-        for (int i = 0; i < M; i++) c[i] = y[i];
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (p & (1 << j)) {
-            s ^= tc[j];
-#pragma unroll
-            for (int i = 0; i < M; i++) c[i] ^= tm[j][i];
-        }
-        const uint32_t iv = inv[s];
-        cc[p] = SISO_INF; cm[p] = 0;
-        if (s == 0u || __popc(s) == 1u || iv != 0u) {
-            if (iv != 0u && iv - 1u < 8u * nb) sb_flip<M>(c, 8u + iv - 1u);
-            else c[0] ^= __builtin_bitreverse32(s) >> 24;
-            cc[p] = sb_cost<W>(sw, c); cm[p] = siso_data_mask<M, MT>(c);
-            const uint32_t key = (cc[p] << 4) | (uint32_t)p;
-            if (key < best) { best = key; dm = cm[p]; }
-        }
-    }
-}
-
 // In place (Sout == Sin, the decode kernel) the outputs of one group land where other lanes' inputs lie, so the work goes in
 // rounds of 64 groups: every lane reads all of its group's inputs and decodes into registers, a wave barrier, then the writes.
 // A group's outputs (one per message bit) are never more than its inputs (one per coded bit) and start no later, so round r's
@@ -3576,7 +3395,7 @@ __device__ __forceinline__ void sb_secded_siso_rounds(const uint8_t *col, const 
         const uint32_t blk = b0 + lane;
         const uint32_t nb = blk < nblk ? min((uint32_t)ND, n - ND * blk) : 0u;
         uint32_t cc[16], best = ~0u; MT cm[16], dm = 0;
-        if (blk < nblk) sb_secded_siso<ND>(Sin + 8 * (ND + 1) * (size_t)blk, nb, col, inv, cc, cm, best, dm);
+        if (blk < nblk) sb_secded_chase<ND, true>(Sin + 8 * (ND + 1) * (size_t)blk, nb, col, inv, best, dm, cc, cm);
         __threadfence_block(); __builtin_amdgcn_wave_barrier();
         if (blk < nblk) siso_chase_out<MT>(cc, cm, best, dm, 2u * nb, reinterpret_cast<uint32_t *>(Sout + 8 * ND * (size_t)blk));
         __threadfence_block(); __builtin_amdgcn_wave_barrier();
@@ -3624,7 +3443,7 @@ __device__ __forceinline__ void block_fec_decode_siso(unsigned fs, uint32_t n, c
         for (uint32_t j0 = 0; j0 < ncw; j0 += DEC_THREADS) {
             const uint32_t j = j0 + lane;
             uint32_t cc[16], cm[16], best = ~0u, dm = 0;
-            if (j < ncw) { uint32_t a[6]; sb_load<6>(Sin + 24 * (size_t)j, 6u, a); sb_golay_siso(a, T, cc, cm, best, dm); }
+            if (j < ncw) { uint32_t a[6]; sb_load<6>(Sin + 24 * (size_t)j, 6u, a); sb_golay_chase<true>(a, T, best, dm, cc, cm); }
             __threadfence_block(); __builtin_amdgcn_wave_barrier();
             if (j < ncw) siso_chase_out<uint32_t>(cc, cm, best, dm, min(3u, 2u * n - 3u * j), out + 3 * (size_t)j);
             __threadfence_block(); __builtin_amdgcn_wave_barrier();

@@ -272,7 +272,8 @@ def test_sc16_input_at_cuts(fx, oracle, world):
 
 def test_detector_mode_at_cuts(fx, oracle, world):
     """MODE_DETECTOR with want_framesyms, cuts from a - 256 to a + 512: positions and estimates identical to the one-pass run, and
-    the oracle's detector's"""
+    the oracle's detector's.  The cut runs must take segments again (the detector walker's repair rounds and their re-sync with the
+    segment's earlier list), as the flex_rx runs above must: 13 repairs and 1 replay at either depth when the assertion was added"""
     caps = CC.CAPTURES
     xs, cuts, who = [], [], []
     for i, c in enumerate(caps):
@@ -293,7 +294,9 @@ def test_detector_mode_at_cuts(fx, oracle, world):
                 assert np.array_equal(g["framesyms"], x[g["start"]:g["start"] + rd.N]), (c["name"], g["start"])
     for depth in (1, 3):
         ctx = fx.RxContext(len(xs), mode=fx.MODE_DETECTOR, threshold=0.5, want_framesyms=True, segment_len=4096)
-        got, _ = feed(ctx, xs, cuts, depth)
+        got, tm = feed(ctx, xs, cuts, depth)
         ctx.close()
+        print("\ndetector, depth %d: repairs %d replays %d" % (depth, tm["repairs"], tm["replays"]))
+        assert tm["replays"] + tm["repairs"] > 0, "nothing was repaired or replayed: the detector's re-walks did not run"
         for s, i in enumerate(who):
             assert [dkey(g) for g in got[s]] == [dkey(g) for g in one[i]], (caps[i]["name"], cuts[s])
