@@ -46,8 +46,12 @@ class Config(C.Structure):                  # fxrx_config
                 ("soft_header", C.c_int), ("soft_block", C.c_int)]
 
 
-class ConfigChain(Config):                  # the whole fxrx_config: Config is its part up to soft_block; fxrx_create takes this one
+class ConfigChain(Config):                  # fxrx_config up to soft_chain: Config is its part up to soft_block
     _fields_ = [("soft_chain", C.c_int)]
+
+
+class ConfigRs(ConfigChain):                # the whole fxrx_config: fxrx_create takes this one
+    _fields_ = [("soft_rs", C.c_int)]
 
 
 class Frame(C.Structure):                   # fxrx_frame
@@ -93,6 +97,7 @@ EXPORTS = [
     "fxtx_apply_channel", "fxrx_set_timing", "fxrx_debug_block_times", "fxrx_ready", "fxrx_inflight", "fxrx_debug_fail", "fxrx_debug_gang_stats", "fxrx_debug_prescan_stats", "fxrx_debug_prescan_words", "fxrx_debug_gang_open", "fxrx_debug_late_stats", "fxrx_pinned_alloc", "fxrx_pinned_free", "fxrx_sync_context",
     "fxrx_debug_header_decode", "fxrx_debug_block_decode", "fxrx_sync_set_soft_block",
     "fxrx_debug_block_siso", "fxrx_sync_set_soft_chain",
+    "fxrx_debug_rs_soft", "fxrx_sync_set_soft_rs",
     "fxrx_sync_set_streaming", "fxrx_qdet_flush", "fxrx_qdet_pending", "fxrx_qdet_set_block", "fxrx_qdet_context",
     "fxrx_iq_sample_bytes", "fxrx_set_iq_scale", "fxrx_submit_fmt", "fxrx_process_fmt", "fxrx_iq_convert_host", "fxtx_quantize",
 ]
@@ -241,6 +246,9 @@ def lib():
     L.fxrx_sync_set_soft_block.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_block.restype = C.c_int
     L.fxrx_sync_set_soft_chain.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_chain.restype = C.c_int
     L.fxrx_debug_block_siso.restype = C.c_int
+    L.fxrx_sync_set_soft_rs.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_rs.restype = C.c_int
+    L.fxrx_debug_rs_soft.restype = C.c_int
+    L.fxrx_debug_rs_soft.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fxrx_debug_block_siso.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
     L.flexframesync_decode_header_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_header_soft.restype = C.c_int
     L.flexframesync_decode_payload_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_payload_soft.restype = C.c_int

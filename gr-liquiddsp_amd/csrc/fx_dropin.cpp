@@ -78,7 +78,7 @@ bool alloc_ring(std::vector<fx_complex *> &ring, unsigned count, size_t samples)
 // (every few thousand samples) finds the oldest one done; their frames wait in `pending` and leave one per call.
 struct fxrx_sync_s {
     framesync_callback cb = nullptr; void *ud = nullptr;
-    fxrx_ctx *ctx = nullptr; float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0, soft_block = 0, soft_chain = 0;
+    fxrx_ctx *ctx = nullptr; float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0, soft_block = 0, soft_chain = 0, soft_rs = 0;
     unsigned block = kSyncBlockDefault, depth = kSyncDepthDefault;
     std::vector<fx_complex *> bufs; unsigned cur = 0; size_t fill = 0;     // ring of depth + 1 pinned input buffers of `block` samples
     std::deque<HeldFrame> pending; HeldFrame current;
@@ -152,7 +152,7 @@ static fxrx_ctx *sync_make_ctx(const fxrx_sync_s *q)
 {
     fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_FLEX_RX; cfg.n_streams = 1; cfg.want_framesyms = 1;
     if (q) { cfg.threshold = q->threshold; cfg.equalizer = q->equalizer; cfg.soft_decision = q->soft; cfg.soft_header = q->soft_header;
-            cfg.soft_block = q->soft && q->soft_block; cfg.soft_chain = q->soft && q->soft_block && q->soft_chain; }
+            cfg.soft_block = q->soft && q->soft_block; cfg.soft_chain = q->soft && q->soft_block && q->soft_chain; cfg.soft_rs = q->soft && q->soft_rs; }
     if (const char *d = std::getenv("FXRX_DEVICE")) cfg.device = std::atoi(d);
     fxrx_ctx *ctx = fxrx_create(&cfg);
     if (ctx && fxrx_set_depth(ctx, q ? q->depth : kSyncDepthDefault) != 0) { fxrx_destroy(ctx); return nullptr; }
@@ -251,6 +251,15 @@ int fxrx_sync_set_soft_chain(flexframesync q, int on)
         return -1;
     }
     return sync_set_option(q, &fxrx_sync_s::soft_chain, on, "fxrx_sync_set_soft_chain");
+}
+// (in force while soft payload decoding is on; turning it on without is refused, as fxrx_create would)
+int fxrx_sync_set_soft_rs(flexframesync q, int on)
+{
+    if (q && on && !q->soft) {
+        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs: needs soft payload decoding (setting unchanged)\n");
+        return -1;
+    }
+    return sync_set_option(q, &fxrx_sync_s::soft_rs, on, "fxrx_sync_set_soft_rs");
 }
 // [RECALLED liquid 1.3.x] flexframesync_decode_header_soft / flexframesync_decode_payload_soft (include/liquid/liquid.h)
 int flexframesync_decode_header_soft(flexframesync q, int soft) { return sync_set_option(q, &fxrx_sync_s::soft_header, soft, "flexframesync_decode_header_soft"); }

@@ -36,6 +36,7 @@
 #include "fx_device.h"
 #include "fx_launch.h"
 #include "fx_vbclean.h"
+#include "fx_rsgmd.h"
 
 // 8 waves: the 49 CFO-sweep transforms of a hop take 7 rounds instead of 13.  The 512-sample window is still
 // handled by the first 256 threads (HALF); reductions keep the 4-wave tree order of the canonical arithmetic.
@@ -3026,6 +3027,79 @@ __device__ __forceinline__ void block_fec_decode(unsigned fs, uint32_t n, const 
     }
 }
 
+// ===================================================================== payload: soft-decision Reed-Solomon (fxrx_config.soft_rs)
+// Generalized-minimum-distance decoding (the rule is this project's, in integers): the hard word with its f least
+// reliable bytes erased, f = 0, 2, ..., 32, goes through an errors-and-erasures decoder (fx_rsgmd.h: rsg_trial), and of the up to 17
+// codewords the one that changes the least bit margin wins, ties to the smallest f.  One wave per block, blocks of a frame one after
+// the other: lanes stride over the bytes for hard decisions, reliabilities and the erasure order, lanes 0..31 take a syndrome
+// each, lanes 0..16 a trial each (in private memory, like rs_decode_block), and a wave minimum picks the winner.  The working
+// set -- hard bytes, sort keys, GF tables -- is in LDS; the instances that use this run one wave per workgroup.
+struct RsgLds {
+    uint8_t  ex[512], lg[256];      // GF(2^8) tables (trials look up from LDS, not from global memory)
+    uint16_t key[256];              // (rho << 8) | j: distinct, so ranks are a permutation
+    uint8_t  h[256];                // hard bytes, then the corrected block
+    uint8_t  S[32], era[32];        // syndromes; the 32 least reliable positions in erasure order
+};
+
+// the GF tables into the workgroup's LDS, once per kernel (rs_decode_soft_wave's first barrier orders them before their use)
+__device__ __forceinline__ void rsg_load_tables(RsgLds *R, const FxTables *T, int lane)
+{
+    for (uint32_t i = lane; i < 512; i += DEC_THREADS) R->ex[i] = T->rsexp[i];
+    for (uint32_t i = lane; i < 256; i += DEC_THREADS) R->lg[i] = T->rslog[i];
+}
+
+// soft: 8 fec_enc_len(RS, n) soft values in codeword order (8-byte aligned, not written); dec: n bytes (another buffer);
+// chosen_f (tests, may be null): the winning f per block (255 would say "no candidate"; c_32 always exists, so it is never written)
+__device__ __noinline__ void rs_decode_soft_wave(uint32_t n, const uint8_t *soft, uint8_t *dec, uint8_t *chosen_f, const FxTables *T, RsgLds *R, int lane)
+{
+    uint32_t nb = (n + 222) / 223; if (nb == 0) nb = 1;
+    const uint32_t dl = (n + nb - 1) / nb, N = dl + 32;
+    for (uint32_t blk = 0; blk < nb; blk++) {
+        const uint8_t *s = soft + 8 * (size_t)blk * N;
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();                 // (the round before has read h)
+        for (uint32_t j = lane; j < N; j += DEC_THREADS) {
+            const unsigned long long w = *reinterpret_cast<const unsigned long long *>(s + 8 * (size_t)j);
+            uint8_t sv[8], h, rho;
+#pragma unroll
+            for (int b = 0; b < 8; b++) sv[b] = (uint8_t)(w >> (8 * b));
+            rsg_byte(sv, h, rho);
+            R->h[j] = h; R->key[j] = (uint16_t)(((unsigned)rho << 8) | j);
+        }
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        // erasure order by rank counting: position j goes to slot #{i: key_i < key_j}
+        for (uint32_t j = lane; j < N; j += DEC_THREADS) {
+            const unsigned mine = R->key[j]; unsigned rank = 0;
+            for (uint32_t i = 0; i < N; i++) rank += R->key[i] < mine ? 1u : 0u;
+            if (rank < 32u) R->era[rank] = (uint8_t)j;
+        }
+        uint8_t sy = 0;
+        if (lane < 32) {
+            for (uint32_t j = 0; j < N; j++) sy = (uint8_t)(rsg_mul_log(R->ex, R->lg, sy, (unsigned)lane + 1u) ^ R->h[j]);
+            R->S[lane] = sy;
+        }
+        const bool dirty = __ballot(sy != 0) != 0ull;
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        unsigned chosen = 0;
+        if (dirty) {                                                            // (a codeword is its own f = 0 candidate at cost 0)
+            RsgTrial tr; tr.cost = RSG_NO_COST; tr.np = 0;
+            if (lane < (int)RSG_TRIALS) rsg_trial(2u * (unsigned)lane, N, R->S, R->era, s, R->ex, R->lg, tr);
+            const uint32_t mykey = tr.cost == RSG_NO_COST ? RSG_NO_COST : (tr.cost << 8) | (uint32_t)lane;      // (cost < 2^16)
+            uint32_t best = mykey;
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, m, 64));
+            __builtin_amdgcn_wave_barrier();                                    // (every trial has read h's syndromes and era)
+            // (defensive only: c_32 always exists, so best is never RSG_NO_COST and chosen never 255; a trial changes at most 32 bytes)
+            if (best != RSG_NO_COST && mykey == best)
+                for (uint32_t i = 0; i < tr.np && i < 32u; i++) R->h[tr.pos[i]] ^= tr.val[i];
+            chosen = best == RSG_NO_COST ? 255u : 2u * (best & 255u);
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        }
+        const uint32_t off = blk * dl, len = off < n ? min(n - off, dl) : 0u;
+        for (uint32_t j = lane; j < len; j += DEC_THREADS) dec[off + j] = R->h[j];
+        if (chosen_f && lane == 0) chosen_f[blk] = (uint8_t)chosen;
+    }
+}
+
 // ===================================================================== payload: soft-input block decoders (fxrx_config.soft_block)
 // The rules are this project's, not liquid's fec_decode_soft.  Soft values: one byte per coded bit, 0 = surely 0
 // ... 255 = surely 1, de-interleaved, in codeword bit order.  Inside a decoder a codeword is a "position mask": bit b = codeword
@@ -3819,10 +3893,12 @@ __device__ __forceinline__ void deinterleave_staged(uint8_t *buf, uint32_t n, ui
 // SB (fxrx_config.soft_block): a block code (not Reed-Solomon) in a stage that decodes from soft values uses its soft-input decoder
 // SC (fxrx_config.soft_chain, with SB): a soft-block fec1 in front of a convolutional fec0 hands it soft values (block_fec_decode_siso,
 // in place in the soft arena), and fec0 decodes them as it does behind FEC_NONE: soft de-interleaver, soft-input Viterbi
-template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false>
+// SR (fxrx_config.soft_rs, with WITH_RS and SOFT): a Reed-Solomon code in a stage that decodes from soft values uses rs_decode_soft_wave
+// (R: its LDS); its output is hard bytes
+template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false, bool SR = false>
 __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob *jobs, const uint32_t *job_idx, const uint8_t *hard, uint8_t *bufA,
                                           uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res,
-                                          const FxTables *T, uint8_t *X)
+                                          const FxTables *T, uint8_t *X, RsgLds *R = nullptr)
 {
     const uint32_t jf = job_idx[ji];
     FxPayJob job = jobs[jf];
@@ -3846,6 +3922,7 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
         else if (job.fec1 == FX_FEC_NONE) still_soft = true;
         else if (SC && pc0 && sb_code(job.fec1)) { block_fec_decode_siso(job.fec1, job.l0, S, S, T, lane); still_soft = true; }
         else if (SB && sb_code(job.fec1)) block_fec_decode_soft(job.fec1, job.l0, S, B, T, lane);
+        else if (SR && job.fec1 == FX_FEC_RS_M8) rs_decode_soft_wave(job.l0, S, B, nullptr, T, R, lane);
         else {
             soft_to_hard_wave(S, A, job.l1, lane);
             __threadfence_block(); __builtin_amdgcn_wave_barrier();
@@ -3858,6 +3935,7 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
             FX_STAMP(3);
             if (pc0) viterbi27<2>(pc0, job.k, S, A, dw_arena + job.dw_off, B, lane, res ? &res[jf].stamp[6] : nullptr);
             else if (SB && sb_code(job.fec0)) block_fec_decode_soft(job.fec0, job.k, S, A, T, lane);
+            else if (SR && job.fec0 == FX_FEC_RS_M8) rs_decode_soft_wave(job.k, S, A, nullptr, T, R, lane);
             else {
                 soft_to_hard_wave(S, B, job.l0, lane);
                 __threadfence_block(); __builtin_amdgcn_wave_barrier();
@@ -3908,8 +3986,8 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
 
 // SB: the soft-block variant (fxrx_config.soft_block), soft-input block decoders; SC: the soft-chain variant (fxrx_config.soft_chain),
 // SB with soft-output block decoders in front of a convolutional fec0.  Template arguments of dec_frame: the default instances
-// carry none of their code.
-template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false>
+// carry none of their code.  SR: the soft Reed-Solomon variant (fxrx_config.soft_rs) of the Reed-Solomon instance, likewise.
+template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false, bool SR = false>
 __global__ __launch_bounds__(WITH_RS ? DEC_THREADS : DEC_THREADS * DEC_MAX_WAVES)
 void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA,
                       uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T,
@@ -3917,6 +3995,7 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
 {
     static_assert(!SB || SOFT, "soft-input block decoders need soft decisions");
     static_assert(!SC || SB, "soft-output block decoders are a variant of the soft-input ones");
+    static_assert(!SR || (WITH_RS && SOFT), "soft Reed-Solomon decoding is a variant of the Reed-Solomon instance with soft decisions");
     // The list's length is known on the device only.  The lean instance has no loop around its body (a grid-stride loop
     // doubles the register footprint): the host launches it over the list's capacity -- a grid sized from the previous block
     // plus a second, normally idle one for the rest -- and surplus waves leave at once.  The Reed-Solomon instance strides.
@@ -3929,7 +4008,11 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
     const uint32_t ji0 = __builtin_amdgcn_readfirstlane(first_wave + blockIdx.x * wpg + (threadIdx.x >> 6));
     if (ji0 >= njobs) return;
     __builtin_amdgcn_s_setprio(2);
-    if constexpr (WITH_RS) {
+    if constexpr (SR) {
+        __shared__ RsgLds Rs;                                                    // (one wave per workgroup)
+        rsg_load_tables(&Rs, T, lane);
+        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, SOFT, SB, SC, true>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X, &Rs);
+    } else if constexpr (WITH_RS) {
         for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, SOFT, SB, SC>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
     } else {
         dec_frame<false, SOFT, SB, SC>(ji0, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
@@ -3937,8 +4020,9 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
 }
 
 // soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input block decoders (SB), 3 those with soft-output block
-// decoders in front of a convolutional fec0 (SB and SC)
-extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
+// decoders in front of a convolutional fec0 (SB and SC); soft_rs: with soft decisions, the Reed-Solomon instance decodes Reed-Solomon
+// stages from soft values (SR)
+extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, int soft_rs, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host)
 {
@@ -3946,7 +4030,12 @@ extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, unsigned first_wav
     const unsigned w = with_rs ? 1u : (waves_per_wg < 1u ? 1u : (waves_per_wg > DEC_MAX_WAVES ? DEC_MAX_WAVES : waves_per_wg));
     const dim3 grid((grid_waves + w - 1) / w), block(DEC_THREADS * w);
 #define FX_DEC_LAUNCH(RS, SF, SB, SC) hipLaunchKernelGGL((fx_paydec_kernel<RS, SF, SB, SC>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
-    if (soft == 3) { if (with_rs) FX_DEC_LAUNCH(true, true, true, true); else FX_DEC_LAUNCH(false, true, true, true); }
+    if (with_rs && soft && soft_rs) {
+        if (soft == 3) hipLaunchKernelGGL((fx_paydec_kernel<true, true, true, true, true>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
+        else if (soft == 2) hipLaunchKernelGGL((fx_paydec_kernel<true, true, true, false, true>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
+        else hipLaunchKernelGGL((fx_paydec_kernel<true, true, false, false, true>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
+    }
+    else if (soft == 3) { if (with_rs) FX_DEC_LAUNCH(true, true, true, true); else FX_DEC_LAUNCH(false, true, true, true); }
     else if (soft == 2) { if (with_rs) FX_DEC_LAUNCH(true, true, true, false); else FX_DEC_LAUNCH(false, true, true, false); }
     else if (with_rs) { if (soft) FX_DEC_LAUNCH(true, true, false, false); else FX_DEC_LAUNCH(true, false, false, false); }
     else { if (soft) FX_DEC_LAUNCH(false, true, false, false); else FX_DEC_LAUNCH(false, false, false, false); }
@@ -3989,6 +4078,26 @@ extern "C" hipError_t fx_launch_blksiso(unsigned fs, unsigned n, unsigned count,
 {
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(fx_blksiso_kernel, dim3(count), dim3(DEC_THREADS), 0, st, fs, n, count, in, out, T);
+    return hipGetLastError();
+}
+
+// tests (fxrx_debug_rs_soft): the soft Reed-Solomon decoder on `count` crafted packets of n message bytes, one wave (one workgroup)
+// per packet: 8 fec_enc_len(RS, n) soft values in (codeword order), n bytes and one chosen f per Reed-Solomon block out
+__global__ __launch_bounds__(DEC_THREADS)
+void fx_rssoft_kernel(uint32_t n, uint32_t count, const uint8_t *in, uint8_t *out, uint8_t *chosen_f, const FxTables *T)
+{
+    __shared__ RsgLds Rs;
+    const uint32_t p = blockIdx.x;
+    if (p >= count) return;
+    uint32_t nb = (n + 222) / 223; if (nb == 0) nb = 1;
+    rsg_load_tables(&Rs, T, threadIdx.x);
+    rs_decode_soft_wave(n, in + 8 * (size_t)fec_enc_len(FX_FEC_RS_M8, n) * p, out + (size_t)n * p, chosen_f + (size_t)nb * p, T, &Rs, threadIdx.x);
+}
+
+extern "C" hipError_t fx_launch_rssoft(unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, uint8_t *chosen_f, const FxTables *T)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(fx_rssoft_kernel, dim3(count), dim3(DEC_THREADS), 0, st, n, count, in, out, chosen_f, T);
     return hipGetLastError();
 }
 

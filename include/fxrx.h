@@ -94,6 +94,9 @@ int  fxrx_sync_set_soft_block(flexframesync q, int on);
  * soft_block are on.  Re-creates the context; returns 0, or -1 if that failed or if, with on != 0, soft payload decoding or soft_block
  * is off, in which case the previous setting stays */
 int  fxrx_sync_set_soft_chain(flexframesync q, int on);
+/* soft-decision Reed-Solomon decoding (fxrx_config.soft_rs), in force while soft payload decoding is on.  Re-creates the context; returns
+ * 0, or -1 if that failed or if, with on != 0, soft payload decoding is off, in which case the previous setting stays */
+int  fxrx_sync_set_soft_rs(flexframesync q, int on);
 unsigned int fxrx_sync_pending(flexframesync q);     /* completed frames not yet delivered */
 /* the liquid signatures return void: when a block fails on the GPU its samples (and those of the blocks in flight with it) are
  * dropped -- never fed twice --, the synchroniser restarts freshly reset behind the gap, the text stays in fxrx_last_error(),
@@ -210,6 +213,22 @@ typedef struct {
                                     block does not transmit and padding bits past 8 l0 are not emitted.
                                     Needs soft_block = 1 (hence soft_decision = 1 and flex_rx mode; fxrx_create fails with FXRX_ERR_ARG
                                     otherwise).  0 (default): fec1 hands fec0 hard bytes */
+    int          soft_rs;        /* 1: a Reed-Solomon code RS(255,223) in a stage that decodes from soft values -- fec1, or fec0 when fec1 is
+                                    none -- decodes from them too, by generalized-minimum-distance decoding.  Per block of N = dl + 32
+                                    bytes, with s the soft values in codeword order (MSB first): hard byte h_j (bit set iff s > 127), bit
+                                    margin m = |2 s - 255|, byte reliability rho_j = the least margin of its bits; E_f = the first f
+                                    positions ascending by (rho_j, j).  For f = 0, 2, ..., 32 the candidate c_f is the codeword of the
+                                    shortened code that differs from h in at most (32 - f) / 2 positions outside E_f (unique if it exists;
+                                    a locator root outside the N transmitted positions: none; f = 0 is the hard decoder).  The candidate
+                                    with the least D(c) = sum of m over the bits where c and h differ wins, ties to the smallest f; its
+                                    data bytes are the stage's output, hard bytes (nothing soft is handed on to a stage behind it).  The
+                                    rule is this project's, integers only, not pinned to liquid.  It never gives up: c_32 always exists, so
+                                    a block far beyond the code's reach is replaced by a far codeword where the hard decoder hands it on
+                                    as received -- measured as a loss for Reed-Solomon in front of a convolutional fec0 at low SNR, a
+                                    gain for Reed-Solomon alone.  Independent of soft_block / soft_chain;
+                                    frames without a Reed-Solomon stage decode as with soft_rs = 0.  Needs soft_decision = 1 and flex_rx
+                                    mode (fxrx_create fails with FXRX_ERR_ARG otherwise).  0 (default): the bounded-distance decoder on the
+                                    hard decisions, radius 16 bytes */
 } fxrx_config;
 
 typedef struct {
@@ -335,6 +354,12 @@ int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned
  * out_soft receives 8 n soft values per packet, one per message bit, MSB first.  Synchronous, on the current HIP device; returns 0 or
  * FXRX_ERR_* */
 int fxrx_debug_block_siso(unsigned int fec, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out_soft);
+/* tests: the soft-decision Reed-Solomon decoder (fxrx_config.soft_rs) on the GPU over `count` packets of n message bytes: in_soft holds
+ * 8 fec_enc_len(RS, n) soft values per packet in codeword bit order, out receives n bytes per packet, chosen_f the winning f of every
+ * Reed-Solomon block (max(1, ceil(n / 223)) per packet; 255 would say "no candidate" and is never written: the f = 32
+ * candidate always exists).  Synchronous, on the current HIP device; returns 0 or
+ * FXRX_ERR_* */
+int fxrx_debug_rs_soft(unsigned int n, unsigned int count, const uint8_t *in_soft, uint8_t *out, uint8_t *chosen_f);
 /* diagnostic builds (-DFX_STAMPS) only: shader-clock deltas of the decode phases of payload job i */
 int fxrx_debug_stamps(const fxrx_ctx *c, unsigned int i, uint32_t out[8]);
 int fxrx_debug_chain_stamps(const fxrx_ctx *c, uint32_t out[8]);  /* chain kernel phase clocks (stream 0) of the last collected block */
