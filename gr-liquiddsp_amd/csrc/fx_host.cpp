@@ -354,6 +354,10 @@ bool is_block_fec(unsigned fec)
            fec == FX_FEC_SECDED2216 || fec == FX_FEC_SECDED3932 || fec == FX_FEC_SECDED7264;
 }
 
+// the longest packet the fxrx_debug_* decoders take: a stage's message is up to fec0's output for a 65535-byte payload and its CRC,
+// 131 080 bytes behind a rate-1/2 code; the kernels index in 32 bits up to 2^29 bytes
+constexpr unsigned kDebugMaxN = 1u << 18;
+
 // What the fxrx_debug_* decoders share: tables and input up, launch(d_in, d_out, d_out2, d_tables) on the null stream, outputs
 // back, everything freed on every path.  who: the entry point, for the error message; in_pad: spare bytes behind the input;
 // out2: a second output, or null.
@@ -1441,7 +1445,7 @@ int fxrx_debug_header_decode(int soft, const uint8_t *in, unsigned int n, uint8_
 
 int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out)
 {
-    if (!is_block_fec(fec) || !in || !out || n == 0 || n > 65535) { set_err("fxrx_debug_block_decode: bad argument"); return FXRX_ERR_ARG; }
+    if (!is_block_fec(fec) || !in || !out || n == 0 || n > kDebugMaxN) { set_err("fxrx_debug_block_decode: bad argument"); return FXRX_ERR_ARG; }
     if (count == 0) return 0;
     return debug_decode("fxrx_debug_block_decode", in, (size_t)count * fx::fec_enc_len(fec, n) * (soft ? 8 : 1), 0, out, (size_t)count * n, nullptr, 0,
                         [&](const uint8_t *d_in, uint8_t *d_out, uint8_t *, const FxTables *d_t) { return fx_launch_blkdec(soft ? 1 : 0, fec, n, count, nullptr, d_in, d_out, d_t); });
@@ -1449,7 +1453,7 @@ int fxrx_debug_block_decode(unsigned int fec, int soft, unsigned int n, unsigned
 
 int fxrx_debug_block_siso(unsigned int fec, unsigned int n, unsigned int count, const uint8_t *in, uint8_t *out_soft)
 {
-    if (!is_block_fec(fec) || !in || !out_soft || n == 0 || n > 65535) { set_err("fxrx_debug_block_siso: bad argument"); return FXRX_ERR_ARG; }
+    if (!is_block_fec(fec) || !in || !out_soft || n == 0 || n > kDebugMaxN) { set_err("fxrx_debug_block_siso: bad argument"); return FXRX_ERR_ARG; }
     if (count == 0) return 0;
     // (16 spare input bytes: the decoders load whole words)
     return debug_decode("fxrx_debug_block_siso", in, (size_t)count * fx::fec_enc_len(fec, n) * 8, 16, out_soft, (size_t)count * n * 8, nullptr, 0,
@@ -1458,7 +1462,7 @@ int fxrx_debug_block_siso(unsigned int fec, unsigned int n, unsigned int count, 
 
 int fxrx_debug_rs_soft(unsigned int n, unsigned int count, const uint8_t *in_soft, uint8_t *out, uint8_t *chosen_f)
 {
-    if (!in_soft || !out || !chosen_f || n == 0 || n > 65535) { set_err("fxrx_debug_rs_soft: bad argument"); return FXRX_ERR_ARG; }
+    if (!in_soft || !out || !chosen_f || n == 0 || n > kDebugMaxN) { set_err("fxrx_debug_rs_soft: bad argument"); return FXRX_ERR_ARG; }
     if (count == 0) return 0;
     const size_t nb = (n + 222) / 223;
     return debug_decode("fxrx_debug_rs_soft", in_soft, (size_t)count * fx::fec_enc_len(FX_FEC_RS_M8, n) * 8, 0, out, (size_t)count * n, chosen_f, (size_t)count * nb,

@@ -155,7 +155,7 @@ def test_library_exports_the_soft_rs_entry_points(fx):
     assert L.fxrx_debug_rs_soft(4, 1, None, buf, buf) == -1
     assert L.fxrx_debug_rs_soft(4, 1, buf, None, buf) == -1
     assert L.fxrx_debug_rs_soft(4, 1, buf, buf, None) == -1
-    assert L.fxrx_debug_rs_soft(70000, 1, buf, buf, buf) == -1
+    assert L.fxrx_debug_rs_soft((1 << 18) + 1, 1, buf, buf, buf) == -1       # (a stage of a 65535-byte frame is up to 131 080 bytes: taken)
 
 
 @pytest.mark.parametrize("mode,soft", [(0, 0), (1, 1), (1, 0)], ids=["no_soft_decision", "detector", "detector_hard"])
