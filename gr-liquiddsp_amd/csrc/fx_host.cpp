@@ -234,6 +234,7 @@ struct fxrx_ctx_s {
     // FXRX_INCHAIN_REPAIR=0: never, 1: while needed (default), 2: always.
     int inchain_repair = 1; unsigned inchain_left = 0;
     bool plan_fused = true;              // FXRX_PLAN_FUSED=0: the plan stage is two launches even when one workgroup plans the block
+    unsigned plan_threads = 512;         // FXRX_PLAN_THREADS: width of the one-workgroup plan kernel, 256 / 512 (anything else: this default)
     // FXRX_VB_EARLY_TAIL=0: the tail of clean frames runs in fx_vbfinish_kernel and the trellis kernels are launched with every block.
     // Otherwise fx_vbpre_kernel finishes clean frames, and the trellis kernels join the chain only while frames that need them keep turning
     // up (Traffic::trellis_left).  A block that meets one without them is completed when it is collected.
@@ -484,6 +485,7 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_VB_CLEAN")) c->vb_clean = std::atoi(e) != 0;
     if (const char *e = std::getenv("FXRX_INCHAIN_REPAIR")) c->inchain_repair = std::min(2, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_PLAN_FUSED")) c->plan_fused = std::atoi(e) != 0;
+    if (const char *e = std::getenv("FXRX_PLAN_THREADS")) { const int v = std::atoi(e); if (v == 256 || v == 512) c->plan_threads = (unsigned)v; }
     if (const char *e = std::getenv("FXRX_VB_EARLY_TAIL")) c->vb_early_tail = std::atoi(e) != 0;
     if (const char *e = std::getenv("FXRX_DEBUG_STOP_AFTER")) c->debug_stop_after = std::atoi(e);
     if (const char *e = std::getenv("FXRX_DEBUG_WALK_TWICE")) c->debug_walk_twice = std::atoi(e);
@@ -982,7 +984,7 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
         a.pll_list = sl.d_pll_list.p; a.dec_list = sl.dec_list(kDecPlain); a.list_cap = sl.list_cap();
         a.vb_items = sl.d_vb_items.p; a.vb_cap = sl.vb_cap;
         a.hdr = sl.hdr_walk(); a.hdr_pay = sl.hdr_pay(); a.hdr_host = sl.h_hdr.p; a.ws = sl.d_plan_ws.p;
-        HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->traffic.frames / 2048 + 1), c->plan_fused ? 1 : 0, a));
+        HIP_OK(fx_launch_plan(st, c->plan_grid ? c->plan_grid : (unsigned)std::min<uint64_t>(64, c->traffic.frames / 2048 + 1), c->plan_fused ? 1 : 0, c->plan_threads, a));
     }
     const int tl = sl.timing_level;
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvPlan], st));

@@ -1733,6 +1733,7 @@ __device__ __forceinline__ bool chain_state_in(const FxStreamDesc *streams, cons
 // a chip busy with the walkers and payload kernels of the other blocks in flight.  A stream that needs a repair is left
 // without a chain and without a state (FX_BLK_NEEDS_REPAIR): fxrx_collect then runs fx_chain_kernel -- the full-size one,
 // which can walk -- for the block and enqueues the blocks behind it again.
+// (512 and 1024 threads were measured: no shorter, DESIGN.md section 6, wide-workgroup log.)
 #define CHAINFAST_THREADS 256
 // In-chain repair round (fx_host.cpp:enqueue_back): pass 1 is this kernel with the request list -- a stream that only has
 // hand-off misses / fired skipped hops gets its segments queued and is left PENDING (stat[s] = 2) instead of being flagged;
@@ -1961,8 +1962,8 @@ __device__ __forceinline__ unsigned pll_class(unsigned ms)
     }
 }
 
-// exclusive scan of PLAN_NV values per thread over the workgroup, in one go (two barriers); v[] -> prefixes, tot[] -> totals
-__device__ __forceinline__ void plan_scan(uint32_t (&v)[PLAN_NV], uint32_t (&tot)[PLAN_NV], uint32_t (*ws)[PLAN_NV])
+// exclusive scan of PLAN_NV values per thread over the workgroup of NT threads, in one go (two barriers); v[] -> prefixes, tot[] -> totals
+template <int NT> __device__ __forceinline__ void plan_scan(uint32_t (&v)[PLAN_NV], uint32_t (&tot)[PLAN_NV], uint32_t (*ws)[PLAN_NV])
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t inc[PLAN_NV];
@@ -1979,7 +1980,7 @@ __device__ __forceinline__ void plan_scan(uint32_t (&v)[PLAN_NV], uint32_t (&tot
     for (int q = 0; q < PLAN_NV; q++) {
         uint32_t wb = 0, t = 0;
 #pragma unroll
-        for (int w = 0; w < PLAN_THREADS / 64; w++) { const uint32_t x = ws[w][q]; if (w < wave) wb += x; t += x; }
+        for (int w = 0; w < NT / 64; w++) { const uint32_t x = ws[w][q]; if (w < wave) wb += x; t += x; }
         tot[q] = t; v[q] = wb + inc[q] - v[q];
     }
 }
@@ -2077,14 +2078,34 @@ __device__ __forceinline__ uint32_t plan_stream_of(const uint32_t *base, uint32_
     return lo;
 }
 
-// One frame's job and host record: from its chain record, its stream, the size words (which the caller holds in registers: they are not
-// read again) and what plan_sizes made of them, the frame's offsets off[] (PV_*), its chain slot and the first of its trellis items.
-__device__ __forceinline__ void plan_emit(FxPayJob *__restrict__ job, FxOutRec *__restrict__ rec, const FxFrame *__restrict__ fp, const FxStreamDesc *__restrict__ sd,
+// What a job and a host record take from the chain record besides the size words, and from the stream: plain loads, so that a caller can have
+// those of several frames in flight before it stores anything (a load behind a store waits for that store, and the records go to host memory).
+struct PlanRest {
+    const float2 *x, *xa_end; int64_t abs_base;
+    int64_t start; int32_t offset; float rxy, tau, gamma, dphi, phi; uint32_t pfb; int32_t mfc0; uint32_t mix_th, mix_dl; float mf_scale;
+    float pilot_dphi, pilot_phi, pilot_gain; uint32_t pll_th; float pll_f; uint32_t header[FX_HDR_DEC / 4];
+};
+__device__ __forceinline__ PlanRest plan_rest(const FxFrame *__restrict__ fp, const FxStreamDesc *__restrict__ sd)
+{
+    PlanRest r;
+    r.x = sd->x; r.xa_end = sd->xa_end; r.abs_base = sd->abs_base;
+    r.start = fp->start; r.offset = fp->offset; r.rxy = fp->rxy; r.tau = fp->tau; r.gamma = fp->gamma; r.dphi = fp->dphi; r.phi = fp->phi;
+    r.pfb = fp->pfb; r.mfc0 = fp->mfc0; r.mix_th = fp->mix_th; r.mix_dl = fp->mix_dl; r.mf_scale = fp->mf_scale;
+    r.pilot_dphi = fp->pilot_dphi; r.pilot_phi = fp->pilot_phi; r.pilot_gain = fp->pilot_gain; r.pll_th = fp->pll_th; r.pll_f = fp->pll_f;
+    const uint32_t *hw = reinterpret_cast<const uint32_t *>(fp->header);
+#pragma unroll
+    for (int i = 0; i < FX_HDR_DEC / 4; i++) r.header[i] = hw[i];
+    return r;
+}
+// One frame's job and host record: from the rest of its chain record and its stream (fp: plan_rest), the size words (which the caller holds in
+// registers: they are not read again) and what plan_sizes made of them, the frame's offsets off[] (PV_*), its chain slot and the first of its
+// trellis items.
+__device__ __forceinline__ void plan_emit(FxPayJob *__restrict__ job, FxOutRec *__restrict__ rec, const PlanRest &fp,
                                           const PlanWords &w, const PlanFrame &f, const uint32_t (&off)[PLAN_NV], uint32_t eq, uint32_t slot, uint32_t vb_off)
 {
     FxPayJob j;
-    j.x = sd->x; j.xa_end = sd->xa_end; j.start = fp->start; j.mix_th = fp->mix_th; j.mix_dl = fp->mix_dl; j.mf_scale = fp->mf_scale;
-    j.pfb = fp->pfb; j.mfc0 = fp->mfc0; j.pll_th = fp->pll_th; j.pll_f = fp->pll_f; j.ms = w.ms; j.bps = f.bps;
+    j.x = fp.x; j.xa_end = fp.xa_end; j.start = fp.start; j.mix_th = fp.mix_th; j.mix_dl = fp.mix_dl; j.mf_scale = fp.mf_scale;
+    j.pfb = fp.pfb; j.mfc0 = fp.mfc0; j.pll_th = fp.pll_th; j.pll_f = fp.pll_f; j.ms = w.ms; j.bps = f.bps;
     j.nsym = f.valid ? w.nsym : 0u; j.sym_off = off[PV_SYM];
     j.pay_len = w.plen; j.check = w.check; j.fec0 = w.fec0; j.fec1 = w.fec1; j.k = f.k; j.l0 = f.l0; j.l1 = f.l1;
     j.byte_off = off[PV_BYTE]; j.dw_off = off[PV_DW]; j.out_off = off[PV_OUT]; j.pad_ = f.valid ? 1u : 0u;
@@ -2092,16 +2113,16 @@ __device__ __forceinline__ void plan_emit(FxPayJob *__restrict__ job, FxOutRec *
     *job = j;
     // the record goes to pinned host memory: assemble it in registers, send it as eight 16-byte stores
     union { FxOutRec r; uint4 q[sizeof(FxOutRec) / 16]; } u;
-    u.r.start = sd->abs_base + fp->start; u.r.stream = f.sidx; u.r.offset = fp->offset;
-    u.r.rxy = fp->rxy; u.r.tau = fp->tau; u.r.gamma = fp->gamma; u.r.dphi = fp->dphi; u.r.phi = fp->phi; u.r.pfb = fp->pfb;
-    u.r.pilot_dphi = fp->pilot_dphi; u.r.pilot_phi = fp->pilot_phi; u.r.pilot_gain = fp->pilot_gain;
+    u.r.start = fp.abs_base + fp.start; u.r.stream = f.sidx; u.r.offset = fp.offset;
+    u.r.rxy = fp.rxy; u.r.tau = fp.tau; u.r.gamma = fp.gamma; u.r.dphi = fp.dphi; u.r.phi = fp.phi; u.r.pfb = fp.pfb;
+    u.r.pilot_dphi = fp.pilot_dphi; u.r.pilot_phi = fp.pilot_phi; u.r.pilot_gain = fp.pilot_gain;
     u.r.flags = w.flags & FX_FLAG_HEADER_VALID;
     u.r.pay_len = f.valid ? w.plen : 0u; u.r.ms = w.ms; u.r.check = w.check; u.r.fec0 = w.fec0; u.r.fec1 = w.fec1;
     u.r.nsym = f.valid ? w.nsym : 0u; u.r.bps = f.bps; u.r.sym_off = off[PV_SYM]; u.r.out_off = off[PV_OUT];
     u.r.evm_sum = 0.0f; u.r.payload_valid = 0; u.r.status = 0;
-    const uint32_t *hw = reinterpret_cast<const uint32_t *>(fp->header); uint32_t *rw = reinterpret_cast<uint32_t *>(u.r.header);
+    uint32_t *rw = reinterpret_cast<uint32_t *>(u.r.header);
 #pragma unroll
-    for (int i = 0; i < FX_HDR_DEC / 4; i++) rw[i] = hw[i];
+    for (int i = 0; i < FX_HDR_DEC / 4; i++) rw[i] = fp.header[i];
     u.r.byte_off = off[PV_BYTE];
     uint4 *dst = reinterpret_cast<uint4 *>(rec);
 #pragma unroll
@@ -2130,13 +2151,13 @@ template <class Counts> __device__ __forceinline__ void plan_class_bases(const C
     for (int c = 0; c < 7; c++) { vbc_base[c] = vb; vb += (cnt.vbc(c) + 127u) & ~127u; }              // whole forward-pass waves: 128 slots
     vbc_base[7] = vb;
 }
-// padding slots of every class (one workgroup)
-template <class Counts> __device__ __forceinline__ void plan_pad_lists(const Counts &cnt, const uint32_t (&cls_base)[FX_PLL_CLASSES + 1], const uint32_t (&vbc_base)[8], const FxPlanArgs &a)
+// padding slots of every class (one workgroup of NT threads)
+template <int NT, class Counts> __device__ __forceinline__ void plan_pad_lists(const Counts &cnt, const uint32_t (&cls_base)[FX_PLL_CLASSES + 1], const uint32_t (&vbc_base)[8], const FxPlanArgs &a)
 {
     for (int c = 0; c < FX_PLL_CLASSES; c++)
-        for (uint32_t i = cls_base[c] + cnt.cls(c) + threadIdx.x; i < cls_base[c + 1] && i < a.list_cap; i += PLAN_THREADS) a.pll_list[i] = 0xFFFFFFFFu;
+        for (uint32_t i = cls_base[c] + cnt.cls(c) + threadIdx.x; i < cls_base[c + 1] && i < a.list_cap; i += NT) a.pll_list[i] = 0xFFFFFFFFu;
     for (int c = 0; c < 7; c++)
-        for (uint32_t i = vbc_base[c] + cnt.vbc(c) + threadIdx.x; i < vbc_base[c + 1] && i < a.vb_cap; i += PLAN_THREADS) a.vb_items[i] = 0xFFFFFFFFu;
+        for (uint32_t i = vbc_base[c] + cnt.vbc(c) + threadIdx.x; i < vbc_base[c + 1] && i < a.vb_cap; i += NT) a.vb_items[i] = 0xFFFFFFFFu;
 }
 // The block header, from the block's totals tot[] (PV_*), counts and class bases, on top of the walk-phase header h holds (one thread).  It
 // is put together in LDS -- a local struct indexed per class would live in scratch memory.
@@ -2152,11 +2173,11 @@ template <class Tot, class Counts> __device__ __forceinline__ void plan_fill_hdr
     h.done = 1;
 }
 // ... goes out to the payload kernels' copy and to the host's a word per thread, and the walk-phase header is zeroed for the slot's next block
-__device__ __forceinline__ void plan_mirror_hdr(const FxBlockHdr &h, const FxPlanArgs &a)
+template <int NT> __device__ __forceinline__ void plan_mirror_hdr(const FxBlockHdr &h, const FxPlanArgs &a)
 {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(&h);
     uint32_t *d0 = reinterpret_cast<uint32_t *>(a.hdr_pay), *d1 = reinterpret_cast<uint32_t *>(a.hdr_host), *z = reinterpret_cast<uint32_t *>(a.hdr);
-    for (int i = threadIdx.x; i < (int)(sizeof(FxBlockHdr) / 4); i += PLAN_THREADS) { const uint32_t w = src[i]; d0[i] = w; d1[i] = w; z[i] = 0u; }
+    for (int i = threadIdx.x; i < (int)(sizeof(FxBlockHdr) / 4); i += NT) { const uint32_t w = src[i]; d0[i] = w; d1[i] = w; z[i] = 0u; }
 }
 
 // ---- the pair ----
@@ -2176,15 +2197,15 @@ __device__ __forceinline__ void plan_range(uint32_t N, uint32_t &g0, uint32_t &g
     const uint32_t per = ((N + gridDim.x - 1) / gridDim.x + PLAN_THREADS - 1) / PLAN_THREADS * PLAN_THREADS;
     g0 = min(N, blockIdx.x * per); g1 = min(N, g0 + per);
 }
-__device__ __forceinline__ uint32_t plan_stream_bases(const uint32_t *chain_count, uint32_t nstreams, uint32_t *stream_base, uint32_t (*ws)[PLAN_NV])
+template <int NT> __device__ __forceinline__ uint32_t plan_stream_bases(const uint32_t *chain_count, uint32_t nstreams, uint32_t *stream_base, uint32_t (*ws)[PLAN_NV])
 {
     // frames before each stream (every workgroup computes and writes the same values)
     const int tid = threadIdx.x;
     uint32_t run = 0;
-    for (uint32_t s0 = 0; s0 < nstreams; s0 += PLAN_THREADS) {
+    for (uint32_t s0 = 0; s0 < nstreams; s0 += NT) {
         const uint32_t sidx = s0 + tid;
         uint32_t v[PLAN_NV] = { sidx < nstreams ? chain_count[sidx] : 0u, 0, 0, 0, 0, 0, 0 }, tot[PLAN_NV];
-        plan_scan(v, tot, ws);
+        plan_scan<NT>(v, tot, ws);
         if (sidx < nstreams) stream_base[sidx] = run + v[0];
         run += tot[0];
         __syncthreads();
@@ -2201,7 +2222,7 @@ void fx_plan_kernel(const FxPlanArgs a)
     __shared__ uint32_t base_s[PLAN_NV];
     uint32_t *const pw = a.ws;
     const int tid = threadIdx.x;
-    const uint32_t N = plan_stream_bases(a.chain_count, a.nstreams, a.stream_base, ws);
+    const uint32_t N = plan_stream_bases<PLAN_THREADS>(a.chain_count, a.nstreams, a.stream_base, ws);
     uint32_t g0, g1; plan_range(N, g0, g1);
     const uint32_t wg = blockIdx.x;
     // 1. totals of the range
@@ -2209,7 +2230,7 @@ void fx_plan_kernel(const FxPlanArgs a)
     for (uint32_t c0 = g0; c0 < g1; c0 += PLAN_THREADS) {
         uint32_t v[PLAN_NV], tot[PLAN_NV]; PlanWords w;
         (void)plan_frame(c0 + tid, c0 + tid < g1, a, w, v);
-        plan_scan(v, tot, ws);
+        plan_scan<PLAN_THREADS>(v, tot, ws);
 #pragma unroll
         for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
         __syncthreads();
@@ -2243,13 +2264,13 @@ void fx_plan_kernel(const FxPlanArgs a)
         const bool live = g < g1;
         uint32_t v[PLAN_NV], tot[PLAN_NV]; PlanWords w;
         PlanFrame f = plan_frame(g, live, a, w, v);
-        plan_scan(v, tot, ws);
+        plan_scan<PLAN_THREADS>(v, tot, ws);
 #pragma unroll
         for (int q = 0; q < PLAN_NV; q++) { v[q] += before[q]; before[q] += tot[q]; }   // v[]: the frame's offsets from here
         if (f.batch && plan_demote(v[PV_VB], f.vnb, a.vb_cap)) { f.batch = false; f.vnb = 0; }
         if (live) {
             // (vb_off: the frame's trellis items get their slots in fx_planlists_kernel, which stores it)
-            plan_emit(a.pjobs + g, a.recs + g, f.fp, a.streams + f.sidx, w, f, v, a.eq, (uint32_t)(f.fp - a.chain), 0u);
+            plan_emit(a.pjobs + g, a.recs + g, plan_rest(f.fp, a.streams + f.sidx), w, f, v, a.eq, (uint32_t)(f.fp - a.chain), 0u);
             for (uint32_t c = 0; c < f.nblk; c++) if (v[PV_MF] + c < a.mf_cap) { a.mf_job[v[PV_MF] + c] = g; a.mf_c0[v[PV_MF] + c] = c * 1024u; }
         }
         {   // counts per list (wave-aggregated: one atomic per wave and list)
@@ -2290,7 +2311,7 @@ void fx_planlists_kernel(const FxPlanArgs a)
             a.pjobs[g].vb_off = at;
         }
     }
-    if (blockIdx.x == 0) plan_pad_lists(cnt, sh.cls_base, sh.vbc_base, a);
+    if (blockIdx.x == 0) plan_pad_lists<PLAN_THREADS>(cnt, sh.cls_base, sh.vbc_base, a);
     // the workgroup that finishes last: block header for the payload kernels and for the host; counters, workspace and the
     // walk-phase header are zeroed for the slot's next block
     __threadfence(); __syncthreads();
@@ -2303,49 +2324,58 @@ void fx_planlists_kernel(const FxPlanArgs a)
         plan_fill_hdr(sh.h, N, (const volatile uint32_t *)(pw + PW_INC + 8 * (gridDim.x - 1)), cnt, sh.cls_base, sh.vbc_base, a);
     }
     __syncthreads();
-    plan_mirror_hdr(sh.h, a);
+    plan_mirror_hdr<PLAN_THREADS>(sh.h, a);
     for (int i = tid; i < PW_WORDS; i += PLAN_THREADS) pw[i] = 0u;
 }
 
 // ---- the plan stage of a block that ONE workgroup plans (launched as a grid of one: the usual case, a block of up to ~2048 frames).
 // What the pair does across workgroups with global counters, look-back flags and a kernel boundary is this workgroup's own here, so it
-// lives in LDS and registers, and the kernel never touches the workspace (it finds and leaves it zero, as the pair needs it):
-//   tile     PLAN_KEEP x PLAN_THREADS = 2048 frames; a thread owns `per` CONSECUTIVE frames of it (per = frames of the tile / 256, rounded up)
-//   sizes    the seven words of every frame of the thread that decide its sizes are loaded in one go (all loads in flight, one round trip),
-//            the thread adds its frames' seven sizes up, ONE workgroup scan runs over the 256 partial sums; offsets are running sums from there
+// lives in LDS and registers, and the kernel never touches the workspace (it finds and leaves it zero, as the pair needs it).  The workgroup
+// has NT threads (256 or 512: the block's stream is held by this one workgroup, so the wider it is the shorter the stretch; at 1024 threads
+// the 128 registers a thread may have do not hold a frame's job and record beside the size words -- 524 bytes of scratch a lane -- so there
+// is no such instance):
+//   tile     2048 frames; a thread owns `per` CONSECUTIVE frames of it (per = frames of the tile / NT, rounded up; at most KEEP = 2048 / NT)
+//   sizes    the seven words of every frame of the thread that decide its sizes are loaded in one go (all loads in flight, one round trip)
+//            and held to the end of the tile, the thread adds its frames' seven sizes up, ONE workgroup scan runs over the NT partial sums;
+//            offsets are running sums from there
 //   counts   frames per modulation class / decode list, trellis items per code class: LDS atomics.  The class bases need the counts of all
-//            frames, so a block of more than one tile gets a counting sweep first (the only case that reads the size words twice more)
-//   jobs     frame by frame in the thread: the rest of the frame record is read (its lines are the ones the size words came from), job and
-//            host record go out, list slots come from LDS cursors (any order within a class, as with the pair's atomics), and the frame's
-//            trellis / matched-filter runs are noted in LDS: keep[] = (first trellis item, trellis blocks, first filter item, filter blocks)
+//            frames, so a block of more than one tile gets a counting sweep first (the only case that reads the size words twice)
+//   jobs     in batches of up to PLAN_BATCH frames of the thread: the rest of every frame record of the batch is loaded (its lines are the
+//            ones the size words came from) BEFORE the first job or host record goes out -- memory operations complete in order, so a load
+//            issued behind a record's stores would wait until they have reached host memory.  List slots come from LDS cursors (any order
+//            within a class, as with the pair's atomics), and the frame's trellis / matched-filter runs are noted in LDS: keep[] = (first
+//            trellis item, trellis blocks, first filter item, filter blocks)
 //   items    16 lanes per frame write those runs, consecutive lanes consecutive slots
 //   header   read a word per thread at the start, filled from LDS, mirrored and zeroed a word per thread
 // The arena offsets, the matched-filter item order and the frames demoted at the end of the trellis arena are the pair's: all three depend
 // only on prefix sums in frame order.
-#define PLAN_KEEP 8
+#define PLAN_TILE 2048
+#define PLAN_BATCH 2
 #define PLAN_LDS_STREAMS 256            // stream bases of up to this many streams are searched in LDS (more: in stream_base, as the pair does)
 enum { PO_CLS = 0, PO_DEC = FX_PLL_CLASSES, PO_VBC = FX_PLL_CLASSES + 4, PO_N = FX_PLL_CLASSES + 12 };
-struct PlanOneShared {
+template <int NT> struct PlanOneShared {
     FxBlockHdr h;
-    uint32_t ws[PLAN_THREADS / 64][PLAN_NV];
+    uint32_t ws[NT / 64][PLAN_NV];
     uint32_t cnt[PO_N], fill[PO_N];     // frames (trellis items) per class, and the cursors that hand the slots out
     uint32_t cls_base[FX_PLL_CLASSES + 1], vbc_base[8];
     uint32_t sbase[PLAN_LDS_STREAMS + 1], cbase[PLAN_LDS_STREAMS];   // frames before each stream / its region of the chain table
 };
 // chain slot of frame g (stream order, then position) and its stream
-__device__ __forceinline__ uint32_t plan_one_slot(uint32_t g, const FxPlanArgs &a, const PlanOneShared &sh, uint32_t &sidx)
+template <int NT> __device__ __forceinline__ uint32_t plan_one_slot(uint32_t g, const FxPlanArgs &a, const PlanOneShared<NT> &sh, uint32_t &sidx)
 {
     if (a.nstreams <= PLAN_LDS_STREAMS) { sidx = plan_stream_of(sh.sbase, a.nstreams, g); return sh.cbase[sidx] + (g - sh.sbase[sidx]); }
     sidx = plan_stream_of(a.stream_base, a.nstreams, g);
     return a.streams[sidx].chain_base + (g - a.stream_base[sidx]);
 }
 
-extern "C" __global__ __launch_bounds__(PLAN_THREADS)
+template <int NT> __global__ __launch_bounds__(NT)
 void fx_planfused_kernel(const FxPlanArgs a)
 {
-    __shared__ PlanOneShared sh;
-    __shared__ uint4 keep[PLAN_KEEP * PLAN_THREADS];
-    constexpr uint32_t TILE = PLAN_KEEP * PLAN_THREADS;
+    constexpr uint32_t TILE = PLAN_TILE;
+    constexpr int KEEP = PLAN_TILE / NT, JB = PLAN_BATCH;
+    static_assert(NT % 64 == 0 && KEEP * NT == PLAN_TILE && KEEP % JB == 0, "whole waves; the tile is KEEP frames a thread, in whole batches");
+    __shared__ PlanOneShared<NT> sh;
+    __shared__ uint4 keep[PLAN_TILE];
     const PlanCounts<false> cnt{ sh.cnt + PO_CLS, sh.cnt + PO_DEC, sh.cnt + PO_VBC };
     const uint32_t tid = threadIdx.x, nstreams = a.nstreams;
     // diagnostic builds: thread 0's shader clocks per step, summed over tiles, in the header's free stamp words -- [1] header read, stream
@@ -2359,7 +2389,7 @@ void fx_planfused_kernel(const FxPlanArgs a)
     // the block's walk-phase header (complete: its writers ran before this kernel), a word per thread; counters and cursors
     {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(a.hdr); uint32_t *dst = reinterpret_cast<uint32_t *>(&sh.h);
-        for (int i = (int)tid; i < (int)(sizeof(FxBlockHdr) / 4); i += PLAN_THREADS) dst[i] = src[i];
+        for (int i = (int)tid; i < (int)(sizeof(FxBlockHdr) / 4); i += NT) dst[i] = src[i];
         if (tid < PO_N) { sh.cnt[tid] = 0u; sh.fill[tid] = 0u; }
         if (tid <= FX_PLL_CLASSES) sh.cls_base[tid] = 0u;
         if (tid < 8) sh.vbc_base[tid] = 0u;
@@ -2368,111 +2398,112 @@ void fx_planfused_kernel(const FxPlanArgs a)
     uint32_t N;
     if (nstreams <= PLAN_LDS_STREAMS) {
         uint32_t v[PLAN_NV] = { tid < nstreams ? a.chain_count[tid] : 0u, 0, 0, 0, 0, 0, 0 }, tot[PLAN_NV];
-        if (nstreams > 1) plan_scan(v, tot, sh.ws); else { tot[0] = v[0]; v[0] = 0u; }
+        if (nstreams > 1) plan_scan<NT>(v, tot, sh.ws); else { tot[0] = v[0]; v[0] = 0u; }
         if (tid < nstreams) { sh.sbase[tid] = v[0]; a.stream_base[tid] = v[0]; sh.cbase[tid] = a.streams[tid].chain_base; }
         if (tid == 0) { sh.sbase[nstreams] = tot[0]; a.stream_base[nstreams] = tot[0]; }
         __syncthreads();
         N = sh.sbase[nstreams];
-    } else N = plan_stream_bases(a.chain_count, nstreams, a.stream_base, sh.ws);
+    } else N = plan_stream_bases<NT>(a.chain_count, nstreams, a.stream_base, sh.ws);
 
     uint32_t run[PLAN_NV] = { 0, 0, 0, 0, 0, 0, 0 };                         // totals of the tiles done (after the last one: of the block)
     for (int pass = N > TILE ? 0 : 1; pass < 2; pass++) {                    // pass 0: the counting sweep of a block of several tiles
 #pragma unroll
         for (int q = 0; q < PLAN_NV; q++) run[q] = 0u;
         for (uint32_t t0 = 0; t0 < N; t0 += TILE) {
-            const uint32_t nt = min(TILE, N - t0), t1 = t0 + nt, per = (nt + PLAN_THREADS - 1) / PLAN_THREADS, f0 = t0 + tid * per;
+            const uint32_t nt = min(TILE, N - t0), t1 = t0 + nt, per = (nt + NT - 1) / NT, f0 = t0 + tid * per;
             // 1. sizes of my frames: every load is issued before any is used (frames that are not mine read the tile's first one)
-            uint32_t st[PLAN_NV], tot[PLAN_NV];
-            uint32_t info[PLAN_KEEP];                                        // vnb | list key (PlanKey::pack) << 16 | valid << 24 | batch << 25
-            {
-                PlanWords w[PLAN_KEEP];
+            uint32_t st[PLAN_NV];
+            PlanWords w[KEEP]; uint32_t slot[KEEP], sidx[KEEP];
 #pragma unroll
-                for (int i = 0; i < PLAN_KEEP; i++) {
-                    const bool live = (uint32_t)i < per && f0 + i < t1;
-                    uint32_t sidx;
-                    w[i] = plan_words(a.chain + plan_one_slot(live ? f0 + i : t0, a, sh, sidx));
-                }
-#pragma unroll
-                for (int q = 0; q < PLAN_NV; q++) st[q] = 0u;
-#pragma unroll
-                for (int i = 0; i < PLAN_KEEP; i++) {
-                    uint32_t v[PLAN_NV];
-                    const PlanFrame f = plan_sizes(w[i], (uint32_t)i < per && f0 + i < t1, a.detect, a.vb_blk, v);
-                    info[i] = f.valid ? f.vnb | plan_key(w[i].ms, w[i].fec0, w[i].fec1).pack() << 16 | 1u << 24 | (f.batch ? 1u << 25 : 0u) : 0u;
-#pragma unroll
-                    for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
-                }
+            for (int i = 0; i < KEEP; i++) {
+                const bool live = (uint32_t)i < per && f0 + i < t1;
+                slot[i] = plan_one_slot(live ? f0 + i : t0, a, sh, sidx[i]);
+                w[i] = plan_words(a.chain + slot[i]);
             }
-            // 2. one scan over the 256 partial sums: st[] = what lies before my first frame
-            plan_scan(st, tot, sh.ws);
 #pragma unroll
-            for (int q = 0; q < PLAN_NV; q++) st[q] += run[q];
+            for (int q = 0; q < PLAN_NV; q++) st[q] = 0u;
+#pragma unroll
+            for (int i = 0; i < KEEP; i++) {
+                uint32_t v[PLAN_NV];
+                (void)plan_sizes(w[i], (uint32_t)i < per && f0 + i < t1, a.detect, a.vb_blk, v);
+#pragma unroll
+                for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
+            }
+            // 2. one scan over the NT partial sums: st[] = what lies before my first frame
+            {
+                uint32_t tot[PLAN_NV];
+                plan_scan<NT>(st, tot, sh.ws);
+#pragma unroll
+                for (int q = 0; q < PLAN_NV; q++) { st[q] += run[q]; run[q] += tot[q]; }
+            }
             // 3. counts per list, where no counting sweep has done it
             if (pass == 0 || N <= TILE) {
                 uint32_t vb = st[PV_VB];
 #pragma unroll
-                for (int i = 0; i < PLAN_KEEP; i++) {
-                    const uint32_t vnb = info[i] & 0xffffu;
-                    const bool batch = ((info[i] >> 25) & 1u) && !plan_demote(vb, vnb, a.vb_cap);
-                    vb += vnb;
-                    if ((info[i] >> 24) & 1u) {
-                        const PlanKey key = PlanKey::unpack(info[i] >> 16);
+                for (int i = 0; i < KEEP; i++) {
+                    uint32_t v[PLAN_NV];
+                    const PlanFrame f = plan_sizes(w[i], (uint32_t)i < per && f0 + i < t1, a.detect, a.vb_blk, v);
+                    const bool batch = f.batch && !plan_demote(vb, f.vnb, a.vb_cap);
+                    vb += f.vnb;
+                    if (f.valid) {
+                        const PlanKey key = plan_key(w[i].ms, w[i].fec0, w[i].fec1);
                         atomicAdd(&sh.cnt[PO_CLS + key.cls], 1u);
                         atomicAdd(&sh.cnt[PO_DEC + key.dec(batch)], 1u);
-                        if (batch) atomicAdd(&sh.cnt[PO_VBC + key.vc], vnb);
+                        if (batch) atomicAdd(&sh.cnt[PO_VBC + key.vc], f.vnb);
                     }
                 }
             }
-            if (pass == 0) {
-#pragma unroll
-                for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
-                continue;
-            }
+            if (pass == 0) continue;
             if (t0 == 0) {                                                   // the counts are complete
                 __syncthreads();
                 if (tid == 0) plan_class_bases(cnt, sh.cls_base, sh.vbc_base);
                 __syncthreads();
             }
             PLAN_TICK(st1_);
-            // 4. jobs, records, list slots of my frames, one after the other; st[]: the frame's offsets
-            for (uint32_t i = 0; i < per && f0 + i < t1; i++) {
-                const uint32_t g = f0 + i;
-                uint32_t sidx, v[PLAN_NV];
-                const uint32_t slot = plan_one_slot(g, a, sh, sidx);
-                const FxFrame *fp = a.chain + slot;
-                const PlanWords w = plan_words(fp);
-                PlanFrame f = plan_sizes(w, true, a.detect, a.vb_blk, v);
-                f.fp = fp; f.sidx = sidx;
-                if (f.batch && plan_demote(st[PV_VB], f.vnb, a.vb_cap)) { f.batch = false; f.vnb = 0; }
-                uint32_t at = 0;
-                if (f.valid) {
-                    const PlanKey key = plan_key(w.ms, w.fec0, w.fec1);
-                    const uint32_t pp = sh.cls_base[key.cls] + atomicAdd(&sh.fill[PO_CLS + key.cls], 1u);
-                    if (pp < a.list_cap) a.pll_list[pp] = g;
-                    const uint32_t rs = key.dec(f.batch), dp = atomicAdd(&sh.fill[PO_DEC + rs], 1u);
-                    if (dp < a.list_cap) a.dec_list[(size_t)rs * a.list_cap + dp] = g;
-                    if (f.batch) at = sh.vbc_base[key.vc] + atomicAdd(&sh.fill[PO_VBC + key.vc], f.vnb);   // its trellis blocks, among those of the same code
-                }
-                keep[g - t0] = make_uint4(at, f.vnb, st[PV_MF], f.nblk);
-                plan_emit(a.pjobs + g, a.recs + g, fp, a.streams + sidx, w, f, st, a.eq, slot, at);
+            // 4. jobs, records, list slots of my frames, a batch at a time: all of its loads, then its stores; st[]: the frame's offsets
 #pragma unroll
-                for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
+            for (int b0 = 0; b0 < KEEP; b0 += JB) {
+                if ((uint32_t)b0 >= per) break;
+                PlanRest r[JB];
+#pragma unroll
+                for (int i = 0; i < JB; i++) r[i] = plan_rest(a.chain + slot[b0 + i], a.streams + sidx[b0 + i]);
+#pragma unroll
+                for (int i = 0; i < JB; i++) {
+                    const uint32_t g = f0 + b0 + i;
+                    if ((uint32_t)(b0 + i) >= per || g >= t1) break;
+                    const PlanWords &wi = w[b0 + i];
+                    uint32_t v[PLAN_NV];
+                    PlanFrame f = plan_sizes(wi, true, a.detect, a.vb_blk, v);
+                    f.fp = a.chain + slot[b0 + i]; f.sidx = sidx[b0 + i];
+                    if (f.batch && plan_demote(st[PV_VB], f.vnb, a.vb_cap)) { f.batch = false; f.vnb = 0; }
+                    uint32_t at = 0;
+                    if (f.valid) {
+                        const PlanKey key = plan_key(wi.ms, wi.fec0, wi.fec1);
+                        const uint32_t pp = sh.cls_base[key.cls] + atomicAdd(&sh.fill[PO_CLS + key.cls], 1u);
+                        if (pp < a.list_cap) a.pll_list[pp] = g;
+                        const uint32_t rs = key.dec(f.batch), dp = atomicAdd(&sh.fill[PO_DEC + rs], 1u);
+                        if (dp < a.list_cap) a.dec_list[(size_t)rs * a.list_cap + dp] = g;
+                        if (f.batch) at = sh.vbc_base[key.vc] + atomicAdd(&sh.fill[PO_VBC + key.vc], f.vnb);   // its trellis blocks, among those of the same code
+                    }
+                    keep[g - t0] = make_uint4(at, f.vnb, st[PV_MF], f.nblk);
+                    plan_emit(a.pjobs + g, a.recs + g, r[i], wi, f, st, a.eq, slot[b0 + i], at);
+#pragma unroll
+                    for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
+                }
             }
             __syncthreads();
             PLAN_TICK(st2_);
             // 5. the trellis and matched-filter runs of the tile's frames: 16 lanes per frame, consecutive lanes consecutive slots
-            for (uint32_t k = tid >> 4; k < nt; k += PLAN_THREADS / 16) {
+            for (uint32_t k = tid >> 4; k < nt; k += NT / 16) {
                 const uint4 kp = keep[k];
                 const uint32_t g = t0 + k, sub = tid & 15u;
                 for (uint32_t b = sub; b < kp.y; b += 16u) if (kp.x + b < a.vb_cap) { a.vb_items[kp.x + b] = g; a.vb_items[a.vb_cap + kp.x + b] = b; }
                 for (uint32_t c = sub; c < kp.w; c += 16u) if (kp.z + c < a.mf_cap) { a.mf_job[kp.z + c] = g; a.mf_c0[kp.z + c] = c * 1024u; }
             }
-#pragma unroll
-            for (int q = 0; q < PLAN_NV; q++) run[q] += tot[q];
             __syncthreads();                                                 // (keep[] belongs to the next tile from here)
         }
     }
-    plan_pad_lists(cnt, sh.cls_base, sh.vbc_base, a);
+    plan_pad_lists<NT>(cnt, sh.cls_base, sh.vbc_base, a);
     // block header for the payload kernels and for the host (behind everything written above)
     PLAN_TICK(st6_);
     __threadfence(); __syncthreads();
@@ -2484,14 +2515,18 @@ void fx_planfused_kernel(const FxPlanArgs a)
         plan_fill_hdr(sh.h, N, run, cnt, sh.cls_base, sh.vbc_base, a);
     }
     __syncthreads();
-    plan_mirror_hdr(sh.h, a);
+    plan_mirror_hdr<NT>(sh.h, a);
 }
 
-extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, int fused, const FxPlanArgs &a)
+// (threads: the one-workgroup kernel's width, 256 or 512)
+extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, int fused, unsigned threads, const FxPlanArgs &a)
 {
     const unsigned g = grid < 1u ? 1u : (grid > PLAN_MAXG ? PLAN_MAXG : grid);
-    if (fused && g == 1u) hipLaunchKernelGGL(fx_planfused_kernel, dim3(1), dim3(PLAN_THREADS), 0, st, a);
-    else {
+    if (fused && g == 1u) {
+        if (threads == 512u) hipLaunchKernelGGL((fx_planfused_kernel<512>), dim3(1), dim3(512), 0, st, a);
+        else if (threads == 256u) hipLaunchKernelGGL((fx_planfused_kernel<256>), dim3(1), dim3(256), 0, st, a);
+        else return hipErrorInvalidValue;
+    } else {
         hipLaunchKernelGGL(fx_plan_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, a);
         hipLaunchKernelGGL(fx_planlists_kernel, dim3(g), dim3(PLAN_THREADS), 0, st, a);
     }

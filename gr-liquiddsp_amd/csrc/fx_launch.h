@@ -25,8 +25,8 @@ extern "C" hipError_t fx_launch_rssoft(unsigned n, unsigned count, hipStream_t s
 extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, const FxWalkResult *results,
                                           const FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxBlockHdr *hdr, uint32_t force_repair,
                                           FxWalkJob *jobs_rw, uint32_t *req_list, uint32_t *stat, uint32_t pass);
-// (grid workgroups, clamped; fused: a grid of one takes the one-workgroup kernel)
-extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, int fused, const FxPlanArgs &a);
+// (grid workgroups, clamped; fused: a grid of one takes the one-workgroup kernel, of `threads` threads: 256 or 512)
+extern "C" hipError_t fx_launch_plan(hipStream_t st, unsigned grid, int fused, unsigned threads, const FxPlanArgs &a);
 extern "C" unsigned fx_plan_ws_words(void);
 // (gang launches, fx_common.h: one launch for up to FX_GANG_MAX blocks; members without waves are left out)
 extern "C" hipError_t fx_launch_vbpre(const FxVbpreGang *gang, hipStream_t st, const FxTables *T, int clean_on, int early_tail);
