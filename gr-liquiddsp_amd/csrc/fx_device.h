@@ -445,6 +445,8 @@ FX_DEV bool fec_supported(unsigned fs)
     return fs == FX_FEC_NONE || fs == FX_FEC_HAMMING84 || fs == FX_FEC_SECDED7264 || fs == FX_FEC_SECDED2216 ||
            fs == FX_FEC_SECDED3932 || fs == FX_FEC_RS_M8 || blk_spec(fs, k, n) || conv_p(fs) != 0;
 }
+// Reed-Solomon: n message bytes in nb blocks of at most 223, dl message bytes each (the last may hold fewer), 32 parity bytes behind each
+FX_DEV void rs_dims(unsigned n, unsigned &nb, unsigned &dl) { nb = (n + 222) / 223; if (nb == 0) nb = 1; dl = (n + nb - 1) / nb; }
 FX_DEV unsigned fec_enc_len(unsigned fs, unsigned n)
 {
     int p = conv_p(fs);
@@ -455,7 +457,7 @@ FX_DEV unsigned fec_enc_len(unsigned fs, unsigned n)
     }
     unsigned bk, bn;
     if (blk_spec(fs, bk, bn)) { unsigned nb = (8 * n + bk - 1) / bk; return (nb * bn + 7) / 8; }
-    if (fs == FX_FEC_RS_M8) { unsigned nb = (n + 222) / 223; if (nb == 0) nb = 1; const unsigned dl = (n + nb - 1) / nb; return nb * (dl + 32); }
+    if (fs == FX_FEC_RS_M8) { unsigned nb, dl; rs_dims(n, nb, dl); return nb * (dl + 32); }
     if (fs == FX_FEC_SECDED2216) return 3 * (n / 2) + ((n % 2) ? (n % 2) + 1 : 0);
     if (fs == FX_FEC_SECDED3932) return 5 * (n / 4) + ((n % 4) ? (n % 4) + 1 : 0);
     if (fs == FX_FEC_HAMMING84) return 2 * n;

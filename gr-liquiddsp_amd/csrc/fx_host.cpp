@@ -1466,7 +1466,7 @@ int fxrx_debug_rs_soft(unsigned int n, unsigned int count, const uint8_t *in_sof
 {
     if (!in_soft || !out || !chosen_f || n == 0 || n > kDebugMaxN) { set_err("fxrx_debug_rs_soft: bad argument"); return FXRX_ERR_ARG; }
     if (count == 0) return 0;
-    const size_t nb = (n + 222) / 223;
+    unsigned nb, dl; fx::rs_dims(n, nb, dl);
     return debug_decode("fxrx_debug_rs_soft", in_soft, (size_t)count * fx::fec_enc_len(FX_FEC_RS_M8, n) * 8, 0, out, (size_t)count * n, chosen_f, (size_t)count * nb,
                         [&](const uint8_t *d_in, uint8_t *d_out, uint8_t *d_f, const FxTables *d_t) { return fx_launch_rssoft(n, count, nullptr, d_in, d_out, d_f, d_t); });
 }

@@ -2863,15 +2863,21 @@ __device__ __forceinline__ void permute_bits(const uint8_t *src, uint8_t *dst, c
 // m Np + nn (m = 0..M-1 fastest, nn starting at n/3 and wrapping mod Np) skipping values >= n/2.  Within a pass no byte is
 // touched twice, so the lanes take 64 candidates at a time and rank the valid ones with a ballot; de-interleaving applies
 // the passes in reverse order.  No table, hence nothing for the host to prepare when a new packet length shows up.
-__device__ __forceinline__ void deinterleave_wave(uint8_t *x, uint32_t n, int lane)
+// One walk for both element types: E = uint8_t is a packet byte under the bit mask; E = unsigned long long is a packet byte's eight
+// soft values (MSB first), where bit mask ff / 0f / 55 / 33 becomes the bytes of the word that change places.
+template <typename E>
+__device__ __forceinline__ void deinterleave_elems(E *x, uint32_t n, int lane)
 {
+    constexpr bool BYTES = sizeof(E) == 1;
     if (n < 2) return;
     const uint32_t M = 1u + (uint32_t)floorf(sqrtf((float)n));
     uint32_t N = n / M; while (n >= M * N) N++;
     const uint32_t n2 = n / 2, nn0 = n / 3, step_q = 64u / M, step_m = 64u % M;
     for (int p = 3; p >= 0; p--) {
         const uint32_t Np = N + (p == 0 ? 0u : (p == 1 ? 2u : (p == 2 ? 4u : 8u)));
-        const uint32_t mk = p == 0 ? 0xffu : (p == 1 ? 0x0fu : (p == 2 ? 0x55u : 0x33u));
+        const E mk = (E)(BYTES ? (p == 0 ? 0xffull : (p == 1 ? 0x0full : (p == 2 ? 0x55ull : 0x33ull)))
+                               : (p == 0 ? 0xFFFFFFFFFFFFFFFFull : (p == 1 ? 0xFFFFFFFF00000000ull : (p == 2 ? 0xFF00FF00FF00FF00ull : 0xFFFF0000FFFF0000ull))));
+        const E nmk = (E)~mk;
         uint32_t m = (uint32_t)lane % M, q = (uint32_t)lane / M, i_base = 0;
         const uint32_t max_iter = (M * (Np + 1u)) / 64u + 2u;                     // every (m, nn) pair at most once: cannot be reached
         for (uint32_t it = 0; i_base < n2 && it < max_iter; it++) {
@@ -2882,8 +2888,8 @@ __device__ __forceinline__ void deinterleave_wave(uint8_t *x, uint32_t n, int la
             const uint32_t i = i_base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
             if (valid && i < n2) {
                 const uint32_t a = 2u * i, b = 2u * j + 1u;
-                const uint32_t va = x[a], vb = x[b];
-                x[a] = (uint8_t)((va & ~mk) | (vb & mk)); x[b] = (uint8_t)((va & mk) | (vb & ~mk));
+                const E va = x[a], vb = x[b];
+                x[a] = (E)((va & nmk) | (vb & mk)); x[b] = (E)((va & mk) | (vb & nmk));
             }
             i_base += (uint32_t)__popcll(mask);
             m += step_m; q += step_q;
@@ -2892,39 +2898,8 @@ __device__ __forceinline__ void deinterleave_wave(uint8_t *x, uint32_t n, int la
         __threadfence_block(); __builtin_amdgcn_wave_barrier();
     }
 }
-
-// the same swaps on an array of soft values, eight bytes per packet byte (MSB first): a masked swap of two 64-bit words
-__device__ __forceinline__ void deinterleave_soft_wave(uint8_t *xs, uint32_t n, int lane)
-{
-    if (n < 2) return;
-    unsigned long long *x = reinterpret_cast<unsigned long long *>(xs);
-    const uint32_t M = 1u + (uint32_t)floorf(sqrtf((float)n));
-    uint32_t N = n / M; while (n >= M * N) N++;
-    const uint32_t n2 = n / 2, nn0 = n / 3, step_q = 64u / M, step_m = 64u % M;
-    for (int p = 3; p >= 0; p--) {
-        const uint32_t Np = N + (p == 0 ? 0u : (p == 1 ? 2u : (p == 2 ? 4u : 8u)));
-        // bit mask ff / 0f / 55 / 33 -> the bytes (soft values) of the word that change places
-        const unsigned long long mk = p == 0 ? 0xFFFFFFFFFFFFFFFFull : (p == 1 ? 0xFFFFFFFF00000000ull : (p == 2 ? 0xFF00FF00FF00FF00ull : 0xFFFF0000FFFF0000ull));
-        uint32_t m = (uint32_t)lane % M, q = (uint32_t)lane / M, i_base = 0;
-        const uint32_t max_iter = (M * (Np + 1u)) / 64u + 2u;
-        for (uint32_t it = 0; i_base < n2 && it < max_iter; it++) {
-            const uint32_t nn = q == 0 ? nn0 : (nn0 + q) % Np;
-            const uint32_t j = m * Np + nn;
-            const bool valid = j < n2;
-            const unsigned long long mask = __ballot(valid);
-            const uint32_t i = i_base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-            if (valid && i < n2) {
-                const uint32_t a = 2u * i, b = 2u * j + 1u;
-                const unsigned long long va = x[a], vb = x[b];
-                x[a] = (va & ~mk) | (vb & mk); x[b] = (va & mk) | (vb & ~mk);
-            }
-            i_base += (uint32_t)__popcll(mask);
-            m += step_m; q += step_q;
-            if (m >= M) { m -= M; q++; }
-        }
-        __threadfence_block(); __builtin_amdgcn_wave_barrier();
-    }
-}
+__device__ __forceinline__ void deinterleave_wave(uint8_t *x, uint32_t n, int lane) { deinterleave_elems(x, n, lane); }
+__device__ __forceinline__ void deinterleave_soft_wave(uint8_t *xs, uint32_t n, int lane) { deinterleave_elems(reinterpret_cast<unsigned long long *>(xs), n, lane); }
 // hard decisions of n packet bytes from their soft values (value > 127 = 1)
 __device__ __forceinline__ void soft_to_hard_wave(const uint8_t *soft, uint8_t *out, uint32_t n, int lane)
 {
@@ -2934,6 +2909,22 @@ __device__ __forceinline__ void soft_to_hard_wave(const uint8_t *soft, uint8_t *
 #pragma unroll
         for (int b = 0; b < 8; b++) v = (v << 1) | ((((unsigned)(w >> (8 * b)) & 255u) > 127u) ? 1u : 0u);
         out[j] = (uint8_t)v;
+    }
+}
+
+// hard symbols (bps bits each) -> n packet bytes, MSB first: bit 8 j of the packet is bit bps - 1 - (8 j mod bps) of symbol 8 j / bps
+// (one division per byte, then the bits are walked)
+__device__ __forceinline__ void pack_bytes_wave(const uint8_t *hs, unsigned bps, uint32_t n, uint8_t *dst, int lane)
+{
+    for (uint32_t j = lane; j < n; j += DEC_THREADS) {
+        uint32_t sidx = (8u * j) / bps; int sb = (int)(bps - 1u - (8u * j - sidx * bps));
+        unsigned v = 0, cur = hs[sidx];
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            v = (v << 1) | ((cur >> sb) & 1u);
+            if (--sb < 0 && b < 7) { sb = (int)bps - 1; cur = hs[++sidx]; }
+        }
+        dst[j] = (uint8_t)v;
     }
 }
 
@@ -3023,8 +3014,7 @@ __device__ __forceinline__ void block_fec_decode(unsigned fs, uint32_t n, const 
         secded_decode(T->sd22col, 2, n, enc, dec, lane);
     } else if (WITH_RS && fs == FX_FEC_RS_M8) {
         // one lane per 255-byte block; the block is corrected in place in the (mutable) encoded buffer
-        uint32_t nb = (n + 222) / 223; if (nb == 0) nb = 1;
-        const uint32_t dl = (n + nb - 1) / nb;
+        unsigned nb, dl; rs_dims(n, nb, dl);
         for (uint32_t blk = lane; blk < nb; blk += DEC_THREADS) {
             uint8_t *r = const_cast<uint8_t *>(enc) + (size_t)blk * (dl + 32);
             rs_decode_block(r, dl + 32, T);
@@ -3087,8 +3077,8 @@ __device__ __forceinline__ void rsg_load_tables(RsgLds *R, const FxTables *T, in
 // chosen_f (tests, may be null): the winning f per block (255 would say "no candidate"; c_32 always exists, so it is never written)
 __device__ __noinline__ void rs_decode_soft_wave(uint32_t n, const uint8_t *soft, uint8_t *dec, uint8_t *chosen_f, const FxTables *T, RsgLds *R, int lane)
 {
-    uint32_t nb = (n + 222) / 223; if (nb == 0) nb = 1;
-    const uint32_t dl = (n + nb - 1) / nb, N = dl + 32;
+    unsigned nb, dl; rs_dims(n, nb, dl);
+    const uint32_t N = dl + 32;
     for (uint32_t blk = 0; blk < nb; blk++) {
         const uint8_t *s = soft + 8 * (size_t)blk * N;
         __threadfence_block(); __builtin_amdgcn_wave_barrier();                 // (the round before has read h)
@@ -3171,6 +3161,13 @@ __device__ __forceinline__ void sb_load(const uint8_t *p, uint32_t nvalid, uint3
 {
 #pragma unroll
     for (int i = 0; i < W; i++) sw[i] = (uint32_t)i < nvalid ? reinterpret_cast<const uint32_t *>(p)[i] : 0u;
+}
+// the seven soft values of a Hamming(7,4) codeword at p (codewords follow each other without padding: no alignment)
+__device__ __forceinline__ void sb_load7(const uint8_t *p, uint32_t (&sw)[2])
+{
+    sw[0] = sw[1] = 0u;
+#pragma unroll
+    for (int i = 0; i < 7; i++) sw[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
 }
 
 // hard position mask of the soft values
@@ -3370,10 +3367,8 @@ __device__ __forceinline__ void block_fec_decode_soft(unsigned fs, uint32_t n, c
     } else if (fs == FX_FEC_HAMMING74) {
         // two 7-bit codewords per output byte: positions 14 j .. 14 j + 13, not word aligned
         for (uint32_t j = lane; j < n; j += DEC_THREADS) {
-            const uint8_t *p = S + 14 * (size_t)j;
-            uint32_t a[2] = { 0, 0 }, b[2] = { 0, 0 };
-#pragma unroll
-            for (int i = 0; i < 7; i++) { a[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3)); b[i >> 2] |= (uint32_t)p[7 + i] << (8 * (i & 3)); }
+            uint32_t a[2], b[2];
+            sb_load7(S + 14 * (size_t)j, a); sb_load7(S + 14 * (size_t)j + 7, b);
             dec[j] = (uint8_t)((sb_ml<4, 7>(a, T->h74enc) << 4) | sb_ml<4, 7>(b, T->h74enc));
         }
     } else if (fs == FX_FEC_HAMMING128) {
@@ -3527,12 +3522,7 @@ __device__ __forceinline__ void block_fec_decode_siso(unsigned fs, uint32_t n, c
             if (j < ncw) {
                 uint32_t a[2] = { 0, 0 };
                 if (fs == FX_FEC_HAMMING84) { sb_load<2>(Sin + 8 * (size_t)j, 2u, a); sb_ml_siso<4, 8>(a, T->h84enc, o); }
-                else {
-                    const uint8_t *p = Sin + 7 * (size_t)j;
-#pragma unroll
-                    for (int i = 0; i < 7; i++) a[i >> 2] |= (uint32_t)p[i] << (8 * (i & 3));
-                    sb_ml_siso<4, 7>(a, T->h74enc, o);
-                }
+                else { sb_load7(Sin + 7 * (size_t)j, a); sb_ml_siso<4, 7>(a, T->h74enc, o); }
             }
             __threadfence_block(); __builtin_amdgcn_wave_barrier();
             if (j < ncw) out[j] = o[0];
@@ -3908,15 +3898,21 @@ __device__ __forceinline__ void dec_tail(const FxPayJob &job, uint32_t jf, uint8
     }
 }
 
-// one frame, one wave.  SOFT: decoding from per-bit soft values (fx_softdemod_kernel wrote them, 8 per packet byte):
-// a convolutional stage decodes from soft values as long as nothing before it took hard decisions -- the stage nearest the
-// channel (fec1), and fec0 too when fec1 is FEC_NONE; every other stage takes hard decisions (value > 127).
-// de-interleave n bytes at buf through the wave's LDS buffer X when they fit (see fx_vbpre_kernel: the passes are dependent byte
-// swaps, slow through global memory), else in place
+// LDS staging of the one-wave workgroups (fx_paydec_kernel's lean instance, fx_vbpre_kernel).  The de-interleaver is four passes of
+// dependent byte swaps: through global memory every one of its ~17 rounds per pass is a memory round trip (fx_vbpre_kernel took 113 us
+// for 2-KB packets, nearly all of it waiting), so a packet that fits is de-interleaved in LDS.  One size for both kernels: packets up
+// to ~4.5 KB -- 2 KB payloads at rate 1/2 -- fit; at 12 KB a CU held only 13 of these workgroups.
 #define DEC_LDS 4608
+// deinterleave_staged: n bytes go in and come out in 16-byte pieces, so up to 15 bytes behind them travel along
+__device__ __forceinline__ bool dec_lds_fits(uint32_t n) { return n + 16u <= DEC_LDS; }
+// fx_vbpre_kernel: both stages' bytes (l1, then l0) live there; behind the l0 coded bytes it zeroes 16, of which the trellis window and
+// the clean check read 8, and l0 + 8 bytes go out in 16-byte pieces
+__device__ __forceinline__ bool vbpre_lds_fits(uint32_t l1, uint32_t l0) { return l1 + 32u <= DEC_LDS && l0 + 32u <= DEC_LDS; }
+
+// de-interleave n bytes at buf through the wave's LDS buffer X when they fit, else in place
 __device__ __forceinline__ void deinterleave_staged(uint8_t *buf, uint32_t n, uint8_t *X, int lane)
 {
-    if (!X || n + 16u > DEC_LDS) { deinterleave_wave(buf, n, lane); return; }
+    if (!X || !dec_lds_fits(n)) { deinterleave_wave(buf, n, lane); return; }
     const uint32_t n16 = (n + 15u) / 16u;                                       // (buffers are 16-byte aligned with slack behind the packet)
     for (uint32_t j = lane; j < n16; j += DEC_THREADS) reinterpret_cast<uint4 *>(X)[j] = reinterpret_cast<const uint4 *>(buf)[j];
     __builtin_amdgcn_wave_barrier();
@@ -3925,6 +3921,39 @@ __device__ __forceinline__ void deinterleave_staged(uint8_t *buf, uint32_t n, ui
     __threadfence_block(); __builtin_amdgcn_wave_barrier();
 }
 
+// One FEC stage of a frame from hard bytes: fs's coded bytes at enc (de-interleaved; Viterbi's scratch, Reed-Solomon corrects in them)
+// -> n bytes at dec, visible to the whole wave on return
+template <bool WITH_RS>
+__device__ __forceinline__ void stage_hard(unsigned fs, uint32_t n, uint8_t *enc, uint8_t *dec, unsigned long long *dw, uint32_t *stamp_fwd, const FxTables *T, int lane)
+{
+    const int pc = conv_p(fs);
+    if (pc == 1) viterbi27<0>(1, n, enc, dec, dw, enc, lane, stamp_fwd);
+    else if (pc) viterbi27<1>(pc, n, enc, dec, dw, enc, lane, stamp_fwd);
+    else block_fec_decode<WITH_RS>(fs, n, enc, dec, T, lane);
+    __threadfence_block(); __builtin_amdgcn_wave_barrier();
+}
+// The same stage from soft values: 8 n_enc of them at S (de-interleaved) -> n hard bytes at dec.  A code without a soft-input decoder
+// in this instance takes hard decisions (value > 127) into hb, the stage's hard input buffer (Viterbi's scratch otherwise).
+template <bool WITH_RS, bool SB, bool SR>
+__device__ __forceinline__ void stage_soft(unsigned fs, uint32_t n, uint32_t n_enc, const uint8_t *S, uint8_t *dec, uint8_t *hb, unsigned long long *dw, uint32_t *stamp_fwd,
+                                           const FxTables *T, RsgLds *R, int lane)
+{
+    const int pc = conv_p(fs);
+    if (pc) viterbi27<2>(pc, n, S, dec, dw, hb, lane, stamp_fwd);
+    else if (SB && sb_code(fs)) block_fec_decode_soft(fs, n, S, dec, T, lane);
+    else if (SR && fs == FX_FEC_RS_M8) rs_decode_soft_wave(n, S, dec, nullptr, T, R, lane);
+    else {
+        soft_to_hard_wave(S, hb, n_enc, lane);
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        block_fec_decode<WITH_RS>(fs, n, hb, dec, T, lane);
+    }
+    __threadfence_block(); __builtin_amdgcn_wave_barrier();
+}
+
+// one frame, one wave: packet bytes; for fec1, then fec0: de-interleave, decode the stage; the tail (A and B take turns as a stage's
+// input and output).  SOFT: decoding from per-bit soft values (fx_softdemod_kernel wrote them, 8 per packet byte): a stage decodes
+// from soft values as long as nothing before it took hard decisions -- the stage nearest the channel (fec1), and fec0 too when
+// fec1 is FEC_NONE (or handed soft values on, SC); every other stage decodes hard bytes.
 // SB (fxrx_config.soft_block): a block code (not Reed-Solomon) in a stage that decodes from soft values uses its soft-input decoder
 // SC (fxrx_config.soft_chain, with SB): a soft-block fec1 in front of a convolutional fec0 hands it soft values (block_fec_decode_siso,
 // in place in the soft arena), and fec0 decodes them as it does behind FEC_NONE: soft de-interleaver, soft-input Viterbi
@@ -3943,78 +3972,43 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
     job.fec0 = __builtin_amdgcn_readfirstlane(job.fec0); job.fec1 = __builtin_amdgcn_readfirstlane(job.fec1);
     job.bps = __builtin_amdgcn_readfirstlane(job.bps); job.check = __builtin_amdgcn_readfirstlane(job.check);
     uint8_t *A = bufA + job.byte_off, *B = bufB + job.byte_off;
-    const uint8_t *hs = hard + job.sym_off;
-    const unsigned bps = job.bps;
+    unsigned long long *dw = dw_arena + job.dw_off;
+    uint32_t *stamp_fwd = res ? &res[jf].stamp[6] : nullptr;                    // (FX_STAMPS builds: fec0's Viterbi forward pass)
     FX_STAMP_INIT;
     uint32_t status = 0;
-    const int pc1 = conv_p(job.fec1), pc0 = conv_p(job.fec0);
+    bool still_soft = false;                                                    // fec0 decodes from soft values, not from B
     if constexpr (SOFT) {
+        // outer code (fec1): de-interleave the 8 l1 soft values in place, decode -> l0 bytes, or 8 l0 soft values left or made in place
         uint8_t *S = soft_arena + 8 * (size_t)job.byte_off;
         deinterleave_soft_wave(S, job.l1, lane);
         FX_STAMP(1);
-        bool still_soft = false;
-        if (pc1) viterbi27<2>(pc1, job.l0, S, B, dw_arena + job.dw_off, A, lane, nullptr);
-        else if (job.fec1 == FX_FEC_NONE) still_soft = true;
-        else if (SC && pc0 && sb_code(job.fec1)) { block_fec_decode_siso(job.fec1, job.l0, S, S, T, lane); still_soft = true; }
-        else if (SB && sb_code(job.fec1)) block_fec_decode_soft(job.fec1, job.l0, S, B, T, lane);
-        else if (SR && job.fec1 == FX_FEC_RS_M8) rs_decode_soft_wave(job.l0, S, B, nullptr, T, R, lane);
-        else {
-            soft_to_hard_wave(S, A, job.l1, lane);
-            __threadfence_block(); __builtin_amdgcn_wave_barrier();
-            block_fec_decode<WITH_RS>(job.fec1, job.l0, A, B, T, lane);
-        }
-        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        const bool siso = SC && conv_p(job.fec0) && sb_code(job.fec1);
+        still_soft = siso || job.fec1 == FX_FEC_NONE;
+        if (siso) { block_fec_decode_siso(job.fec1, job.l0, S, S, T, lane); __threadfence_block(); __builtin_amdgcn_wave_barrier(); }
+        else if (!still_soft) stage_soft<WITH_RS, SB, SR>(job.fec1, job.l0, job.l1, S, B, A, dw, nullptr, T, R, lane);
         FX_STAMP(2);
         if (still_soft) {
             deinterleave_soft_wave(S, job.l0, lane);
             FX_STAMP(3);
-            if (pc0) viterbi27<2>(pc0, job.k, S, A, dw_arena + job.dw_off, B, lane, res ? &res[jf].stamp[6] : nullptr);
-            else if (SB && sb_code(job.fec0)) block_fec_decode_soft(job.fec0, job.k, S, A, T, lane);
-            else if (SR && job.fec0 == FX_FEC_RS_M8) rs_decode_soft_wave(job.k, S, A, nullptr, T, R, lane);
-            else {
-                soft_to_hard_wave(S, B, job.l0, lane);
-                __threadfence_block(); __builtin_amdgcn_wave_barrier();
-                block_fec_decode<WITH_RS>(job.fec0, job.k, B, A, T, lane);
-            }
-        } else {
-            deinterleave_staged(B, job.l0, X, lane);
-            FX_STAMP(3);
-            if (pc0 == 1) viterbi27<0>(1, job.k, B, A, dw_arena + job.dw_off, B, lane, res ? &res[jf].stamp[6] : nullptr);
-            else if (pc0) viterbi27<1>(pc0, job.k, B, A, dw_arena + job.dw_off, B, lane, res ? &res[jf].stamp[6] : nullptr);
-            else block_fec_decode<WITH_RS>(job.fec0, job.k, B, A, T, lane);
+            stage_soft<WITH_RS, SB, SR>(job.fec0, job.k, job.l0, S, A, B, dw, stamp_fwd, T, R, lane);
         }
-        __threadfence_block(); __builtin_amdgcn_wave_barrier();
-        FX_STAMP(4);
     } else {
-    // 1. hard symbols -> packet bytes (MSB first)
-    for (uint32_t j = lane; j < job.l1; j += DEC_THREADS) {
-        unsigned v = 0;
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const uint32_t k = 8 * j + b, sidx = k / bps, sb = bps - 1 - (k % bps);
-            v = (v << 1) | ((hs[sidx] >> sb) & 1u);
-        }
-        A[j] = (uint8_t)v;
+        // hard symbols -> packet bytes; outer code (fec1): de-interleave l1 bytes in place, decode -> l0 bytes
+        pack_bytes_wave(hard + job.sym_off, job.bps, job.l1, A, lane);
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        FX_STAMP(0);
+        deinterleave_staged(A, job.l1, X, lane);
+        FX_STAMP(1);
+        stage_hard<WITH_RS>(job.fec1, job.l0, A, B, dw, nullptr, T, lane);
+        FX_STAMP(2);
     }
-    __threadfence_block(); __builtin_amdgcn_wave_barrier();
-    FX_STAMP(0);
-    // 2. outer plan (fec1): de-interleave l1 bytes in place, decode -> l0 bytes
-    deinterleave_staged(A, job.l1, X, lane);
-    FX_STAMP(1);
-    if (pc1 == 1) viterbi27<0>(1, job.l0, A, B, dw_arena + job.dw_off, A, lane, nullptr);
-    else if (pc1) viterbi27<1>(pc1, job.l0, A, B, dw_arena + job.dw_off, A, lane, nullptr);
-    else block_fec_decode<WITH_RS>(job.fec1, job.l0, A, B, T, lane);
-    __threadfence_block(); __builtin_amdgcn_wave_barrier();
-    FX_STAMP(2);
-    // 3. inner plan (fec0): de-interleave l0 bytes in place, decode -> k bytes
-    deinterleave_staged(B, job.l0, X, lane);
-    FX_STAMP(3);
-    if (pc0 == 1) viterbi27<0>(1, job.k, B, A, dw_arena + job.dw_off, B, lane, res ? &res[jf].stamp[6] : nullptr);
-    else if (pc0) viterbi27<1>(pc0, job.k, B, A, dw_arena + job.dw_off, B, lane, res ? &res[jf].stamp[6] : nullptr);
-    else block_fec_decode<WITH_RS>(job.fec0, job.k, B, A, T, lane);
-    __threadfence_block(); __builtin_amdgcn_wave_barrier();
+    if (!still_soft) {
+        // inner code (fec0): de-interleave l0 bytes in place, decode -> k bytes
+        deinterleave_staged(B, job.l0, X, lane);
+        FX_STAMP(3);
+        stage_hard<WITH_RS>(job.fec0, job.k, B, A, dw, stamp_fwd, T, lane);
+    }
     FX_STAMP(4);
-    }
     dec_tail(job, jf, A, lane, out, recs, status);
     FX_STAMP(5);
 }
@@ -4054,9 +4048,17 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
     }
 }
 
-// soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input block decoders (SB), 3 those with soft-output block
-// decoders in front of a convolutional fec0 (SB and SC); soft_rs: with soft decisions, the Reed-Solomon instance decodes Reed-Solomon
-// stages from soft values (SR)
+// The instance of a set of options, the rule written once.  soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input
+// block decoders (SB), 3 those with soft-output block decoders in front of a convolutional fec0 (SB and SC); sr (with_rs, soft and
+// fxrx_config.soft_rs): the Reed-Solomon instance decodes Reed-Solomon stages from soft values (SR).  Eleven instances: 2 x 4, and 3 with SR.
+using PaydecKernel = decltype(&fx_paydec_kernel<false, false>);
+template <int SOFT>
+static PaydecKernel paydec_instance(bool with_rs, bool sr)
+{
+    constexpr bool SF = SOFT >= 1, SB = SOFT >= 2, SC = SOFT == 3;
+    if constexpr (SF) if (sr) return fx_paydec_kernel<true, SF, SB, SC, true>;
+    return with_rs ? fx_paydec_kernel<true, SF, SB, SC> : fx_paydec_kernel<false, SF, SB, SC>;
+}
 extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, int soft_rs, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host)
@@ -4064,17 +4066,9 @@ extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, int soft_rs, unsig
     if (grid_waves == 0) return hipSuccess;
     const unsigned w = with_rs ? 1u : (waves_per_wg < 1u ? 1u : (waves_per_wg > DEC_MAX_WAVES ? DEC_MAX_WAVES : waves_per_wg));
     const dim3 grid((grid_waves + w - 1) / w), block(DEC_THREADS * w);
-#define FX_DEC_LAUNCH(RS, SF, SB, SC) hipLaunchKernelGGL((fx_paydec_kernel<RS, SF, SB, SC>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host)
-    if (with_rs && soft && soft_rs) {
-        if (soft == 3) hipLaunchKernelGGL((fx_paydec_kernel<true, true, true, true, true>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
-        else if (soft == 2) hipLaunchKernelGGL((fx_paydec_kernel<true, true, true, false, true>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
-        else hipLaunchKernelGGL((fx_paydec_kernel<true, true, false, false, true>), grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
-    }
-    else if (soft == 3) { if (with_rs) FX_DEC_LAUNCH(true, true, true, true); else FX_DEC_LAUNCH(false, true, true, true); }
-    else if (soft == 2) { if (with_rs) FX_DEC_LAUNCH(true, true, true, false); else FX_DEC_LAUNCH(false, true, true, false); }
-    else if (with_rs) { if (soft) FX_DEC_LAUNCH(true, true, false, false); else FX_DEC_LAUNCH(true, false, false, false); }
-    else { if (soft) FX_DEC_LAUNCH(false, true, false, false); else FX_DEC_LAUNCH(false, false, false, false); }
-#undef FX_DEC_LAUNCH
+    const bool rs = with_rs != 0, sr = rs && soft && soft_rs;
+    const PaydecKernel kernel = soft == 3 ? paydec_instance<3>(rs, sr) : (soft == 2 ? paydec_instance<2>(rs, sr) : (soft ? paydec_instance<1>(rs, sr) : paydec_instance<0>(rs, sr)));
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
     return hipGetLastError();
 }
 
@@ -4124,7 +4118,7 @@ void fx_rssoft_kernel(uint32_t n, uint32_t count, const uint8_t *in, uint8_t *ou
     __shared__ RsgLds Rs;
     const uint32_t p = blockIdx.x;
     if (p >= count) return;
-    uint32_t nb = (n + 222) / 223; if (nb == 0) nb = 1;
+    unsigned nb, dl; rs_dims(n, nb, dl);
     rsg_load_tables(&Rs, T, threadIdx.x);
     rs_decode_soft_wave(n, in + 8 * (size_t)fec_enc_len(FX_FEC_RS_M8, n) * p, out + (size_t)n * p, chosen_f + (size_t)nb * p, T, &Rs, threadIdx.x);
 }
@@ -4160,22 +4154,20 @@ __device__ __forceinline__ constexpr unsigned vb_expect(unsigned j)      // expe
     return ((unsigned)__builtin_popcount(sr & 0x6du) & 1u) | (((unsigned)__builtin_popcount(sr & 0x4fu) & 1u) << 1);
 }
 
-struct VbState {
-    uint32_t P[64];            // path metrics
-};
-
-// metric differences to the smallest, as bytes (a K = 7 trellis keeps them within a dozen once every state is reachable)
-__device__ __forceinline__ void vb_save_vec(const uint32_t (&P)[64], uint8_t *dst)
+// metric differences to the smallest, as bytes (a K = 7 trellis keeps them within a dozen once every state is reachable);
+// metric(i): state i's path metric out of the caller's registers
+template <typename F>
+__device__ __forceinline__ void vb_save_vec(F metric, uint8_t *dst)
 {
-    uint32_t mn = P[0];
+    uint32_t mn = metric(0);
 #pragma unroll
-    for (int i = 1; i < 64; i++) mn = min(mn, P[i]);
+    for (int i = 1; i < 64; i++) mn = min(mn, metric(i));
     uint32_t *d = reinterpret_cast<uint32_t *>(dst);
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         uint32_t w = 0;
 #pragma unroll
-        for (int b = 0; b < 4; b++) w |= min(P[4 * i + b] - mn, 255u) << (8 * b);
+        for (int b = 0; b < 4; b++) w |= min(metric(4 * i + b) - mn, 255u) << (8 * b);
         d[i] = w;
     }
 }
@@ -4212,22 +4204,36 @@ __device__ __forceinline__ void vb_punct(int p, unsigned &pa, unsigned &pb)
     }
 }
 
-// One trellis step of one lane: P -> N.  Returns the 64 decision bits.
-__device__ __forceinline__ unsigned long long vb_step(const uint32_t (&P)[64], uint32_t (&N)[64], unsigned pa, unsigned pb, unsigned up, uint32_t &col, uint32_t &nb,
-                                                      uint32_t w0, uint32_t w1, uint32_t wbase, bool adv)
+// the coded-bit stream of one trellis block: position, puncturing column, a 64-bit window
+struct VbStream { uint32_t col, nb, w0, w1, wbase; };
+// the stream in front of trellis step ts of a code punctured with period p: its column, the coded bits before it; the window empty
+__device__ __forceinline__ VbStream vb_stream_at(uint32_t ts, unsigned p)
 {
-    const unsigned hasA = (pa >> col) & 1u, hasB = (pb >> col) & 1u;
-    const unsigned long long w64 = ((unsigned long long)w0 << 32) | w1;
-    const unsigned top2 = (unsigned)((w64 << ((nb - wbase) & 63u)) >> 62);
+    VbStream s;
+    s.col = ts % p; s.nb = (p == 1u) ? 2u * ts : ts + (ts + p - 1u) / p; s.w0 = s.w1 = s.wbase = 0;
+    return s;
+}
+// 2 x cost of the four expected pairs e = A | B << 1 against what was received at this step (punctured positions cost nothing)
+__device__ __forceinline__ void vb_costs(VbStream &s, unsigned pa, unsigned pb, unsigned up, bool adv, uint32_t (&c2)[4])
+{
+    const unsigned hasA = (pa >> s.col) & 1u, hasB = (pb >> s.col) & 1u;
+    const unsigned long long w64 = ((unsigned long long)s.w0 << 32) | s.w1;
+    const unsigned top2 = (unsigned)((w64 << ((s.nb - s.wbase) & 63u)) >> 62);
     const unsigned ra = top2 >> 1, rb = hasA ? (top2 & 1u) : (top2 >> 1);
-    // 2 x cost of the expected pair e = A | B << 1 against what was received (punctured positions cost nothing)
     const uint32_t a0 = (hasA & ra) << 1, a1 = (hasA & (ra ^ 1u)) << 1, b0 = (hasB & rb) << 1, b1 = (hasB & (rb ^ 1u)) << 1;
-    const uint32_t c2[4] = { a0 + b0, a1 + b0, a0 + b1, a1 + b1 };
+    c2[0] = a0 + b0; c2[1] = a1 + b0; c2[2] = a0 + b1; c2[3] = a1 + b1;
+    if (adv) { s.nb += hasA + hasB; s.col = s.col + 1u == up ? 0u : s.col + 1u; }
+}
+
+// One trellis step of one lane: P -> N.  Returns the 64 decision bits.
+__device__ __forceinline__ unsigned long long vb_step(const uint32_t (&P)[64], uint32_t (&N)[64], unsigned pa, unsigned pb, unsigned up, VbStream &s, bool adv)
+{
+    uint32_t c2[4];
+    vb_costs(s, pa, pb, up, adv, c2);
     const uint32_t c2p[4] = { c2[0] | 1u, c2[1] | 1u, c2[2] | 1u, c2[3] | 1u };
     uint32_t h0 = 0, h1 = 0;
     vb_half<0>(P, N, c2, c2p, h0);
     vb_half<16>(P, N, c2, c2p, h1);
-    if (adv) { nb += hasA + hasB; col = col + 1u == up ? 0u : col + 1u; }
     return ((unsigned long long)h1 << 32) | h0;
 }
 
@@ -4251,11 +4257,9 @@ __device__ __forceinline__ void vb_forward(const uint8_t *enc, int p, uint32_t t
     for (int i = 0; i < 64; i++) P[i] = 0u;
     unsigned pa, pb; vb_punct(p, pa, pb);
     const unsigned up = (unsigned)p;
-    const uint32_t ts = init == 0 ? t_reg - reg_at : t_reg;               // first step this lane really runs
-    uint32_t col = ts % up;
-    uint32_t nb = (p == 1) ? 2u * ts : ts + (ts + up - 1u) / up;          // coded bits before step ts
+    VbStream s = vb_stream_at(init == 0 ? t_reg - reg_at : t_reg, up);    // (the first step this lane really runs)
     const uint32_t *enc32 = reinterpret_cast<const uint32_t *>(enc);      // (byte_off is a multiple of 16)
-    uint32_t w0 = 0, w1 = 0, wbase = 0;
+    const auto metric = [&](int i) { return P[i]; };
     for (uint32_t u = 0; u < nsteps; u += 2) {
         if (u == reg_at) {
             if (init == 1) {
@@ -4266,21 +4270,21 @@ __device__ __forceinline__ void vb_forward(const uint8_t *enc, int p, uint32_t t
 #pragma unroll
                 for (int i = 0; i < 64; i++) P[i] = init_vec[i];
             }
-            if (init != 1 && lane_on && start_vec) vb_save_vec(P, start_vec);
+            if (init != 1 && lane_on && start_vec) vb_save_vec(metric, start_vec);
         }
         if ((u & 15u) == 0u) {                                             // refill the 64-bit window of coded bits
-            const uint32_t idx = nb >> 5;
+            const uint32_t idx = s.nb >> 5;
             const uint32_t x0 = lane_on ? enc32[idx] : 0u, x1 = lane_on ? enc32[idx + 1] : 0u;
-            w0 = __builtin_bswap32(x0); w1 = __builtin_bswap32(x1); wbase = idx << 5;
+            s.w0 = __builtin_bswap32(x0); s.w1 = __builtin_bswap32(x1); s.wbase = idx << 5;
         }
         const bool run = u >= reg_at || init == 0;                          // (a lane that idles keeps its stream position)
-        const unsigned long long d0 = vb_step(P, N, pa, pb, up, col, nb, w0, w1, wbase, run);
-        const unsigned long long d1 = vb_step(N, P, pa, pb, up, col, nb, w0, w1, wbase, run);
+        const unsigned long long d0 = vb_step(P, N, pa, pb, up, s, run);
+        const unsigned long long d1 = vb_step(N, P, pa, pb, up, s, run);
         // (regions are an even number of steps long within the slab: step ur + 1 is inside it whenever ur is)
         const uint32_t ur = u - reg_at, t = t_reg + ur;
         if (lane_on && u >= reg_at && t < t1) { __builtin_nontemporal_store(d0, dwl + (size_t)ur * 64u); __builtin_nontemporal_store(d1, dwl + (size_t)(ur + 1u) * 64u); }
     }
-    if (lane_on && end_vec) vb_save_vec(P, end_vec);
+    if (lane_on && end_vec) vb_save_vec(metric, end_vec);
 }
 
 // per work item, after the forward pass: [7:0] the end state its traceback started from, [15:8] the state it arrived at
@@ -4332,19 +4336,6 @@ __device__ __forceinline__ uint32_t vb2_group(const uint32_t (&Q)[64], uint32_t 
     return h;
 }
 
-// the coded-bit stream of one trellis block: position, puncturing column, a 64-bit window
-struct VbStream { uint32_t col, nb, w0, w1, wbase; };
-// 2 x cost of the four expected pairs e = A | B << 1 against what was received at this step (punctured positions cost nothing)
-__device__ __forceinline__ void vb_costs(VbStream &s, unsigned pa, unsigned pb, unsigned up, bool adv, uint32_t (&c2)[4])
-{
-    const unsigned hasA = (pa >> s.col) & 1u, hasB = (pb >> s.col) & 1u;
-    const unsigned long long w64 = ((unsigned long long)s.w0 << 32) | s.w1;
-    const unsigned top2 = (unsigned)((w64 << ((s.nb - s.wbase) & 63u)) >> 62);
-    const unsigned ra = top2 >> 1, rb = hasA ? (top2 & 1u) : (top2 >> 1);
-    const uint32_t a0 = (hasA & ra) << 1, a1 = (hasA & (ra ^ 1u)) << 1, b0 = (hasB & rb) << 1, b1 = (hasB & (rb ^ 1u)) << 1;
-    c2[0] = a0 + b0; c2[1] = a1 + b0; c2[2] = a0 + b1; c2[3] = a1 + b1;
-    if (adv) { s.nb += hasA + hasB; s.col = s.col + 1u == up ? 0u : s.col + 1u; }
-}
 // One trellis step of both blocks: Q -> N; the decision words of the low-half and of the high-half block.
 __device__ __forceinline__ void vb2_step(const uint32_t (&Q)[64], uint32_t (&N)[64], unsigned pa, unsigned pb, unsigned up, VbStream &sa, VbStream &sb, bool adv_a, bool adv_b,
                                          unsigned long long &da, unsigned long long &db)
@@ -4378,22 +4369,6 @@ __device__ __forceinline__ uint32_t vb_make_guess(const unsigned long long *dwl,
     return (S & 63u) << 24;
 }
 
-// metric differences of one half to its smallest, as bytes (see vb_save_vec; the halves hold doubled metrics)
-__device__ __forceinline__ void vb2_save_vec(const uint32_t (&Q)[64], int half, uint8_t *dst)
-{
-    uint32_t mn = 0xFFFFu;
-#pragma unroll
-    for (int i = 0; i < 64; i++) mn = min(mn, (Q[i] >> (16 * half)) & 0xFFFFu);
-    uint32_t *d = reinterpret_cast<uint32_t *>(dst);
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int b = 0; b < 4; b++) w |= min((((Q[4 * i + b] >> (16 * half)) & 0xFFFFu) - mn) >> 1, 255u) << (8 * b);
-        d[i] = w;
-    }
-}
-
 struct VbHalf {                       // one of a lane's two work items
     const uint8_t *enc; uint32_t t_reg, t1; bool on, first; unsigned long long *dwl; uint8_t *vec;
 };
@@ -4425,12 +4400,10 @@ __device__ __forceinline__ void vb2_forward(int p, uint32_t blk, const VbHalf &A
     unsigned pa, pb; vb_punct(p, pa, pb);
     const unsigned up = (unsigned)p;
     const uint32_t warm = vb_warm(p);
-    VbStream sa, sb;
-    {
-        const uint32_t tsa = A.first ? A.t_reg : A.t_reg - warm, tsb = B.first ? B.t_reg : B.t_reg - warm;
-        sa.col = tsa % up; sa.nb = (p == 1) ? 2u * tsa : tsa + (tsa + up - 1u) / up; sa.w0 = sa.w1 = sa.wbase = 0;
-        sb.col = tsb % up; sb.nb = (p == 1) ? 2u * tsb : tsb + (tsb + up - 1u) / up; sb.w0 = sb.w1 = sb.wbase = 0;
-    }
+    VbStream sa = vb_stream_at(A.first ? A.t_reg : A.t_reg - warm, up), sb = vb_stream_at(B.first ? B.t_reg : B.t_reg - warm, up);
+    // a half's metrics: the halves hold doubled metrics, their lowest bit clear
+    const auto lo = [&](int i) { return (Q[i] & 0xFFFFu) >> 1; };
+    const auto hi = [&](int i) { return Q[i] >> 17; };
     uint32_t *rowa = lds + (threadIdx.x & 63) * VB_ROW, *rowb = lds + (64 + (threadIdx.x & 63)) * VB_ROW;
     uint32_t la = 0, lb = 0;
     const uint32_t nsteps = warm + blk;
@@ -4441,11 +4414,11 @@ __device__ __forceinline__ void vb2_forward(int p, uint32_t blk, const VbHalf &A
             if (A.first) {
 #pragma unroll
                 for (int i = 0; i < 64; i++) Q[i] = (Q[i] & 0xFFFF0000u) | (i ? 1024u : 0u);
-            } else if (A.on) vb2_save_vec(Q, 0, A.vec);
+            } else if (A.on) vb_save_vec(lo, A.vec);
             if (B.first) {
 #pragma unroll
                 for (int i = 0; i < 64; i++) Q[i] = (Q[i] & 0x0000FFFFu) | (i ? 1024u << 16 : 0u);
-            } else if (B.on) vb2_save_vec(Q, 1, B.vec);
+            } else if (B.on) vb_save_vec(hi, B.vec);
         }
         if ((u & 127u) == 0u) { vb_stage(A.enc, sa.nb, A.on, rowa, la); vb_stage(B.enc, sb.nb, B.on, rowb, lb); }
         if ((u & 15u) == 0u) {                                             // refill the 64-bit windows of coded bits (own row: no barrier needed)
@@ -4470,8 +4443,8 @@ __device__ __forceinline__ void vb2_forward(int p, uint32_t blk, const VbHalf &A
             if (B.on && in_reg && B.t_reg + ur < B.t1) { __builtin_nontemporal_store(b0, B.dwl + (size_t)ur * 64u); __builtin_nontemporal_store(b1, B.dwl + (size_t)(ur + 1u) * 64u); }
         }
     }
-    if (A.on) vb2_save_vec(Q, 0, A.vec + 64);
-    if (B.on) vb2_save_vec(Q, 1, B.vec + 64);
+    if (A.on) vb_save_vec(lo, A.vec + 64);
+    if (B.on) vb_save_vec(hi, B.vec + 64);
 }
 
 // ---- forward pass: one lane per (frame, trellis block) work item; the items of a wave share their puncturing code ----
@@ -4637,9 +4610,8 @@ void fx_vbtrace_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t 
     const FxPayJob &job = jobs[it.g];
     const uint32_t len = it.on ? it.t1 - it.t_reg : 0u;
     uint32_t old = it.on ? vb_st[slot] : 0u;
-    uint32_t flags = 0u;
+    const uint32_t flags = old & VB_ST_REP;
     const unsigned long long *dwl = vb_slab(dwv, slot, blk);
-    flags = old & VB_ST_REP;
     // the end state: 0 behind the flushed tail; elsewhere the guess the next block's forward pass left (its first FX_VB_TWARM
     // steps traced back from state 0)
     const bool has_next = it.on && it.b + 1u < it.nblk;
@@ -4688,23 +4660,34 @@ __device__ __forceinline__ unsigned vb_retrace_block(const unsigned long long *d
 }
 
 // ---- front part, one wave per frame: symbols -> packet bytes, de-interleave, fec1 (not convolutional), de-interleave ----
-// The de-interleaver is four passes of dependent byte swaps: through global memory every one of its ~17 rounds per pass is
-// a memory round trip (the kernel took 113 us for 2-KB packets, nearly all of it waiting).  Packets that fit are therefore
-// packed and de-interleaved in LDS and written out once; longer ones take the same steps in place in global memory.
-#define VBPRE_LDS 4608           // (packets up to ~4.5 KB -- 2 KB payloads at rate 1/2 -- stay in LDS; at 12 KB a CU held only 13 of these one-wave workgroups)
-__device__ __forceinline__ void vb_pack_bytes(const uint8_t *hs, unsigned bps, uint32_t nbytes, uint8_t *dst, int lane)
+// Packets that fit (vbpre_lds_fits, at DEC_LDS) are packed and de-interleaved in LDS and written out once; longer ones take the same
+// steps in place in global memory.
+// The steps, on either working buffer.  IN_LDS: X, for both stages' bytes -- fec1 decodes from A to B in global memory, so its input
+// goes out and its output comes back; without an outer code the bytes are the inner code's already (l0 = l1) and stay where they
+// are.  Else the frame's own A, then B, where the l0 coded bytes end up.  Zeros behind them: the 8 bytes that the forward pass's
+// window (and, in LDS, the clean check) reads past them, 16 in LDS, where l0 + 8 bytes go out in 16-byte pieces.
+template <bool IN_LDS>
+__device__ __forceinline__ void vbpre_front(const FxPayJob &job, const uint8_t *hs, uint8_t *X, uint8_t *A, uint8_t *B, const FxTables *T, int lane)
 {
-    // (bit 8 j of the packet is bit bps - 1 - (8 j mod bps) of symbol 8 j / bps: one division per byte, then the bits are walked)
-    for (uint32_t j = lane; j < nbytes; j += DEC_THREADS) {
-        uint32_t sidx = (8u * j) / bps; int sb = (int)(bps - 1u - (8u * j - sidx * bps));
-        unsigned v = 0, cur = hs[sidx];
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            v = (v << 1) | ((cur >> sb) & 1u);
-            if (--sb < 0 && b < 7) { sb = (int)bps - 1; cur = hs[++sidx]; }
+    uint8_t *W = IN_LDS ? X : A;
+    pack_bytes_wave(hs, job.bps, job.l1, W, lane);
+    if (!IN_LDS) __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+    deinterleave_wave(W, job.l1, lane);
+    if (!IN_LDS || job.fec1 != FX_FEC_NONE) {
+        if (IN_LDS) {
+            for (uint32_t j = lane; j < job.l1; j += DEC_THREADS) A[j] = X[j];
+            __threadfence_block(); __builtin_amdgcn_wave_barrier();
         }
-        dst[j] = (uint8_t)v;
+        block_fec_decode<false>(job.fec1, job.l0, A, B, T, lane);
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        if (IN_LDS) {
+            for (uint32_t j = lane; j < job.l0; j += DEC_THREADS) X[j] = B[j];
+            __builtin_amdgcn_wave_barrier();
+        } else W = B;
     }
+    deinterleave_wave(W, job.l0, lane);
+    if (lane < (IN_LDS ? 16 : 8)) W[job.l0 + lane] = 0;
 }
 // coded-bit word w (8 bytes, big-endian) of a packet de-interleaved in LDS
 __device__ __forceinline__ uint64_t vb_lds_word(const uint8_t *X, uint32_t w)
@@ -4743,7 +4726,7 @@ __device__ __forceinline__ bool vb_clean_check(FxPayJob *jobs, uint32_t jf, uint
 extern "C" __global__ __launch_bounds__(DEC_THREADS)
 void fx_vbpre_kernel(const FxVbpreGang g, const FxTables *T, uint32_t clean_on, uint32_t early_tail)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t X[VBPRE_LDS];
+    __shared__ __attribute__((aligned(16))) uint8_t X[DEC_LDS];
     // (a gang of blocks, FxVbpreGang in fx_common.h: blockIdx.y is the member, the grid's x extent the largest member's)
     const FxVbpreMember m = g.m[blockIdx.y];
     if (blockIdx.x >= m.n_waves) return;
@@ -4759,27 +4742,10 @@ void fx_vbpre_kernel(const FxVbpreGang g, const FxTables *T, uint32_t clean_on, 
     job.fec1 = __builtin_amdgcn_readfirstlane(job.fec1); job.bps = __builtin_amdgcn_readfirstlane(job.bps);
     uint8_t *A = bufA + job.byte_off, *B = bufB + job.byte_off;
     const uint8_t *hs = hard + job.sym_off;
-    const bool in_lds = job.l1 + 32u <= VBPRE_LDS && job.l0 + 32u <= VBPRE_LDS;
-    if (in_lds) {
-        vb_pack_bytes(hs, job.bps, job.l1, X, lane);
+    if (vbpre_lds_fits(job.l1, job.l0)) {
+        vbpre_front<true>(job, hs, X, A, B, T, lane);
         __builtin_amdgcn_wave_barrier();
-        deinterleave_wave(X, job.l1, lane);
-        if (job.fec1 == FX_FEC_NONE) {
-            // (no outer code: the packet bytes are the inner code's already -- l0 = l1 -- and stay where they are)
-            deinterleave_wave(X, job.l0, lane);
-        } else {
-            for (uint32_t j = lane; j < job.l1; j += DEC_THREADS) A[j] = X[j];
-            __threadfence_block(); __builtin_amdgcn_wave_barrier();
-            block_fec_decode<false>(job.fec1, job.l0, A, B, T, lane);
-            __threadfence_block(); __builtin_amdgcn_wave_barrier();
-            for (uint32_t j = lane; j < job.l0; j += DEC_THREADS) X[j] = B[j];
-            __builtin_amdgcn_wave_barrier();
-            deinterleave_wave(X, job.l0, lane);
-        }
-        // out in 16-byte pieces (byte_off is a multiple of 16; the buffer has that much slack behind the packet), with the
-        // eight defined bytes behind the coded bits that the forward pass's window reads run into
-        if (lane < 16) X[job.l0 + lane] = 0;
-        __builtin_amdgcn_wave_barrier();
+        // out in 16-byte pieces (byte_off is a multiple of 16; the buffer has that much slack behind the packet)
         const uint32_t n16 = (job.l0 + 8u + 15u) / 16u;
         for (uint32_t j = lane; j < n16; j += DEC_THREADS) reinterpret_cast<uint4 *>(B)[j] = reinterpret_cast<const uint4 *>(X)[j];
         // (the check reads up to 8 bytes past the coded bits: zeroed above; packets on the global-memory branch below keep the trellis)
@@ -4792,14 +4758,7 @@ void fx_vbpre_kernel(const FxVbpreGang g, const FxTables *T, uint32_t clean_on, 
         dec_tail(job, jf, A, lane, out, recs, FX_REC_VB_CLEAN);
         return;
     }
-    vb_pack_bytes(hs, job.bps, job.l1, A, lane);
-    __threadfence_block(); __builtin_amdgcn_wave_barrier();
-    deinterleave_wave(A, job.l1, lane);
-    block_fec_decode<false>(job.fec1, job.l0, A, B, T, lane);
-    __threadfence_block(); __builtin_amdgcn_wave_barrier();
-    deinterleave_wave(B, job.l0, lane);
-    // (the window reads of the forward pass run up to 8 bytes past the coded bits: keep them defined)
-    if (lane < 8) B[job.l0 + lane] = 0;
+    vbpre_front<false>(job, hs, nullptr, A, B, T, lane);
     if (early_tail && lane == 0) hdr_host->vb_dirty = 1u;
 }
 
@@ -4822,7 +4781,7 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
     // a frame fx_vbpre_kernel decoded itself: its message is in A, and its trellis records are stale (no trellis ran); with
     // early_tail the frame is finished already
     if (job.vb_clean) { if (!early_tail) dec_tail(job, jf, A, lane, out, recs, FX_REC_VB_CLEAN); return; }
-    const uint32_t Tn = 8u * job.k + 6u, at = job.vb_off, nblk = job.vb_nblk;
+    const uint32_t at = job.vb_off, nblk = job.vb_nblk;
     bool bad = false, mism = false; uint32_t rep = 0;
     for (uint32_t base = 0; base < nblk; base += 64) {
         const uint32_t b = base + (uint32_t)lane;
@@ -4846,7 +4805,6 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
             else need = (v >> 8) & 0xffu;
         }
     }
-    (void)Tn;
     __threadfence_block(); __builtin_amdgcn_wave_barrier();
     dec_tail(job, jf, A, lane, out, recs, rep << 8);
 }

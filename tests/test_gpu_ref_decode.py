@@ -191,7 +191,7 @@ def reference(fx, traffic):
     return got, tm, {(g["stream"], g["start"]): Ref(g) for g in got if g["header_valid"]}
 
 
-def _compare_hard(got, refs):
+def _compare_hard(got, refs, cases=CASES):
     n, excluded, bad = 0, 0, []
     for g in got:
         if not g["header_valid"]:
@@ -203,7 +203,7 @@ def _compare_hard(got, refs):
             excluded += 1
             continue
         if (g["payload"], g["payload_valid"]) != (r.payload, r.valid):
-            bad.append((g["stream"], g["start"], CASES[g["stream"]][:3], g["payload_valid"], r.valid))
+            bad.append((g["stream"], g["start"], cases[g["stream"]][:3], g["payload_valid"], r.valid))
     assert not bad, "payloads differ from the reference (stream, start, case, gpu valid, ref valid): %s" % bad[:10]
     assert excluded < 0.01 * n, (excluded, n)
     return n, excluded
@@ -251,11 +251,7 @@ def test_hard_decode_paths(fx, monkeypatch, traffic, reference, env):
         assert tm["vb_fallbacks"] > 0
 
 
-def test_soft_decode(fx, monkeypatch, traffic, reference):
-    """soft instance: soft bytes within 1 of the reference demapper; the reference soft chain on the GPU's soft bytes gives
-    the GPU's payloads and validity"""
-    got, tm = _run(fx, monkeypatch, traffic[0], {}, soft=True)
-    refs = reference[2]
+def _compare_soft(got, refs, cases=CASES):
     n, excluded, bad, off = 0, 0, [], 0
     for g in got:
         if not g["header_valid"]:
@@ -269,13 +265,21 @@ def test_soft_decode(fx, monkeypatch, traffic, reference):
         sb = g["soft_bits"]
         assert sb is not None and len(sb) == 8 * r.l1
         d = np.abs(sb.astype(np.int64) - r.soft.astype(np.int64))
-        assert d.max() <= 1, (g["stream"], CASES[g["stream"]][:3], int(d.max()))
+        assert d.max() <= 1, (g["stream"], cases[g["stream"]][:3], int(d.max()))
         off += int((d == 1).sum())
         if (g["payload"], g["payload_valid"]) != r.soft_decode(sb):
-            bad.append((g["stream"], g["start"], CASES[g["stream"]][:3]))
-    print("\nsoft frames compared %d, excluded %d, soft bytes off by one %d, vb_blocks %d" % (n, excluded, off, tm["vb_blocks"]))
+            bad.append((g["stream"], g["start"], cases[g["stream"]][:3]))
     assert not bad, bad[:10]
     assert excluded < 0.01 * n
+    return n, excluded, off
+
+
+def test_soft_decode(fx, monkeypatch, traffic, reference):
+    """soft instance: soft bytes within 1 of the reference demapper; the reference soft chain on the GPU's soft bytes gives
+    the GPU's payloads and validity"""
+    got, tm = _run(fx, monkeypatch, traffic[0], {}, soft=True)
+    n, excluded, off = _compare_soft(got, reference[2])
+    print("\nsoft frames compared %d, excluded %d, soft bytes off by one %d, vb_blocks %d" % (n, excluded, off, tm["vb_blocks"]))
     assert tm["vb_blocks"] == 0                     # soft decisions run on the wave-per-frame decoder
 
 
@@ -309,3 +313,65 @@ def test_maximum_length_with_errors(fx, monkeypatch, soft):
     assert cov["viterbi frames"] == 2 and cov["viterbi frames with channel errors"] == 2
     if not soft:
         assert tm["vb_blocks"] > 0 and tm["vb_clean"] == 0
+
+
+# The LDS staging size of the one-wave decode workgroups: mirrors DEC_LDS in csrc/fx_kernels.hip.  fx_vbpre_kernel (batch Viterbi
+# path) keeps a packet in LDS when both coded lengths + 32 fit, deinterleave_staged (wave-per-frame path) when the length + 16 does.
+LDS_STAGE = 4608
+# (fec0, fec1, snr_db, slack, the payload lengths the rule gives: the last two whose packet fits, the first two that do not).
+# QAM16, CRC_24; SNRs: those of QAM16 with the same fec0 in CASES (V27 alone, V27 over a Hamming code, a Hamming code alone)
+LDS_EDGES = [
+    (R.FEC_V27, R.FEC_NONE, 9.0, 32, [2283, 2284, 2285, 2286]),           # l = 2 k + 2: 4576 is the last that fits
+    (R.FEC_V27, R.FEC_H84, 9.5, 32, None),                                # l1 = 2 l0 straddles the limit while l0 fits
+    (R.FEC_H84, R.FEC_NONE, 14.0, 16, [2292, 2293, 2294, 2295]),          # l = 2 k: 4592 is the last that fits
+]
+
+
+def _lds_edge_cases():
+    cases = []
+    for f0, f1, snr, slack, want in LDS_EDGES:
+        last = max(n for n in range(1, 4096) if R.packet_dims(n, R.CRC_24, f0, f1)[2] + slack <= LDS_STAGE)
+        ns = [last - 1, last, last + 1, last + 2]
+        assert want is None or ns == want, (ns, want)
+        for i, n in enumerate(ns):
+            k, l0, l1 = R.packet_dims(n, R.CRC_24, f0, f1)
+            assert k == n + 3
+            assert (l1 + slack <= LDS_STAGE) == (i < 2), (n, l1)
+            if f1 != R.FEC_NONE:
+                assert l0 + 32 <= LDS_STAGE, (n, l0)                          # (fx_vbpre_kernel's rule is on both lengths: here l1 alone decides)
+            cases.append((R.QAM16, f0, f1, R.CRC_24, n, snr))
+    assert R.packet_dims(2284, R.CRC_24, R.FEC_V27, R.FEC_NONE)[2] == 4576 and R.packet_dims(2293, R.CRC_24, R.FEC_H84, R.FEC_NONE)[2] == 4592
+    return cases
+
+
+def test_lds_fit_boundaries(fx, monkeypatch):
+    """one frame per stream at the payload lengths either side of each LDS-fit rule, with channel errors: the batch path's front
+    kernel (default and without the clean-frame short cut) and the wave-per-frame decoder, hard and soft, against the reference"""
+    cases = _lds_edge_cases()
+    xs, inj = [], []
+    for i, (m, f0, f1, chk, n, snr) in enumerate(cases):
+        g = fx.FrameGen(m, f0, f1, chk)
+        flen = len(g.frame(np.zeros(n, np.uint8)))
+        g.close()
+        x, fr = fx.synth_stream(flen + 2000, stream_id=4400 + i, mod=m, fec0=f0, fec1=f1, check=chk, payload_len=n, snr_db=snr, lead=500)
+        assert len(fr) == 1
+        xs.append(x)
+        inj.append(fr)
+    got, tm = _run(fx, monkeypatch, xs, {})
+    assert [g["stream"] for g in got] == list(range(len(cases)))
+    assert all(g["header_valid"] and len(g["payload"]) == c[4] and (g["fec0"], g["fec1"]) == c[1:3] for g, c in zip(got, cases))
+    refs = {(g["stream"], g["start"]): Ref(g) for g in got}
+    assert not any(r.tie for r in refs.values()), "a frame would be excluded as a tie: choose another stream_id"
+    cov = collections.Counter()
+    for g in got:
+        _coverage(refs[(g["stream"], g["start"])], np.frombuffer(inj[g["stream"]][0][1], np.uint8), cov)
+    print("\n", dict(cov), "valid payloads %d of %d" % (sum(g["payload_valid"] for g in got), len(got)))
+    assert cov["viterbi frames with channel errors"] == 8 and cov["h84 words, 1 error"] > 0
+    assert _compare_hard(got, refs, cases) == (len(cases), 0)
+    assert tm["vb_blocks"] > 0
+    got, tm = _run(fx, monkeypatch, xs, dict(FXRX_VB_CLEAN=0))
+    assert _compare_hard(got, refs, cases) == (len(cases), 0)
+    assert tm["vb_blocks"] > 0 and tm["vb_clean"] == 0
+    got, tm = _run(fx, monkeypatch, xs, {}, soft=True)
+    assert _compare_soft(got, refs, cases)[:2] == (len(cases), 0)
+    assert tm["vb_blocks"] == 0
