@@ -15,8 +15,9 @@
 //                       (fx_chain_kernel: the full-size fallback that can walk by itself).
 //   fx_plan_kernel, fx_planlists_kernel   arena offsets, jobs, result records, work lists of the payload stage
 //                       (fx_planfused_kernel: the same by one workgroup, in LDS, when one workgroup plans the block).
-//   fx_paymf_kernel     per frame, data parallel: closed-form NCO mix (32-bit phase) + fixed-branch
-//                       polyphase matched filter + decimate-by-2 over the payload span.
+//   fx_paymf4_kernel    per frame, data parallel: closed-form NCO mix (32-bit phase) + fixed-branch
+//                       polyphase matched filter + decimate-by-2 over the payload span
+//                       (fx_paymf_kernel: the same at every sample, then the frame's equaliser taps, when the equaliser stage is on).
 //   fx_paypll_kernel    one lane per frame: the decision-directed payload PLL (the only true
 //                       sample-to-sample recurrence of the path), hard demod, EVM.
 //   fx_vbpre / fx_vbfwd / fx_vbfix / fx_vbtrace / fx_vbfinish   packet decode with the K=7 Viterbi run a lane per trellis
@@ -140,6 +141,45 @@ template <int NT, int N> __device__ __forceinline__ void load_span(float2 *dst, 
     for (int k = 0; k < NLD; k++) { const int i = tid + NT * k; ld[k] = i < N ? xv(xs, p0 + i, floor_) : make_float2(0.0f, 0.0f); }
 #pragma unroll
     for (int k = 0; k < NLD; k++) { const int i = tid + NT * k; if (i < N) dst[i] = ld[k]; }
+}
+
+// ---- the exact detector's sliding window (walk_run, fx_seekverify_kernel): L.win = overlap half [0, 256) + new half [256, 512)
+// this thread's sample of the 256-sample half x[p0, p0 + 256) (threads >= HALF: zero, as the reductions want it)
+__device__ __forceinline__ float2 half_load(const XSrc &xs, int64_t p0, int64_t floor_, int tid)
+{
+    return tid < HALF ? xv(xs, p0 + tid, floor_) : make_float2(0.0f, 0.0f);
+}
+// h (a thread's sample of a half, half_load's or an LDS copy's) into the overlap half; not published
+template <class LDS> __device__ __forceinline__ void win_store(LDS &L, float2 h, int tid) { if (tid < HALF) L.win[tid] = h; }
+// Re-arm: h becomes the overlap half; returns its energy (x2_0).  The caller's barrier stands between the last reader of L.win[0, 256)
+// and this; block_sum256's two barriers publish the half.  Whole workgroup.
+template <class LDS> __device__ __forceinline__ float win_rearm(LDS &L, float2 h, int tid)
+{
+    win_store(L, h, tid);
+    return block_sum256(cm2(h), L, tid & 63, __builtin_amdgcn_readfirstlane(tid >> 6));
+}
+// Slide by one hop: the new half nw (energy x2_1) becomes the overlap half.  The first barrier waits for the sweep's readers of L.win,
+// the second publishes the half.  Whole workgroup.
+template <class LDS> __device__ __forceinline__ void win_slide(LDS &L, float2 nw, float &x2_0, float x2_1, int64_t &pos, int tid)
+{
+    __syncthreads();
+    win_store(L, nw, tid);
+    x2_0 = x2_1; pos += FX_HOP;
+    __syncthreads();
+}
+
+// The matched filter's 28-tap sum at sample nc of v: taps ascending, unscaled (the caller applies mf_scale).  UNROLL: the site's unroll
+// factor; ZERO_BELOW: samples below v[0] read as zero.
+template <int UNROLL, bool ZERO_BELOW = false>
+__device__ __forceinline__ float2 mf_sum(const float2 *v, const float *taps, int nc)
+{
+    float ar = 0.0f, ai = 0.0f;
+#pragma unroll UNROLL
+    for (int t = 0; t < FX_MF_TAPS; t++) {
+        const float2 w = (!ZERO_BELOW || nc - t >= 0) ? v[nc - t] : make_float2(0.0f, 0.0f); const float h = taps[t];
+        ar = fmaf(h, w.x, ar); ai = fmaf(h, w.y, ai);
+    }
+    return make_float2(ar, ai);
 }
 
 // One hop of the exact detector (qdetector SEEK): L.win holds the 512-sample window (overlap half + new half,
@@ -835,6 +875,288 @@ __device__ __forceinline__ bool coarse_hop(const float2 *w, float2 *scr, const F
     return coarse_pass(bv, e, T);
 }
 
+// The walk state every thread of the workgroup holds alike (scalar registers: walk_run says so at the top of every turn).
+struct WalkState {
+    int64_t pos, floor_;                // the hop about to be taken: new half x[pos, pos + 256); samples below floor_ read as zero
+    bool fresh, locked;                 // detector freshly reset (overlap half = zeros); walker locked onto the chain
+    uint32_t exact_left;                // hops the exact detector still owes a coarse-scan candidate
+    float x2_0;                         // energy of the overlap half
+    uint32_t hops, hops_cheap;          // exact / coarse hops taken
+    int64_t span_pos, span_floor; uint32_t span_flags;   // the seek in progress: where it began, FX_FLAG_SEEK_FRESH / FX_FLAG_SPAN_EXACT
+};
+
+// ---- the two rounds of the coarse scan (a walker not yet locked, or a locked one that may skip hops; w.exact_left == 0)
+// Four hops (one per wave) at w.pos: same differential correlator as the single-hop round, one window per wave, no block barriers
+// inside a hop.  Needs nothing published; borrows L.cw, L.scr, L.cand.  Leaves L.win[0, 256), the overlap half of the hop at the new
+// w.pos, published, and w.x2_0 its energy (a walker not yet locked takes none: it re-arms on a hit).  Every outcome carries on
+// seeking; the exact hops a candidate is owed are the following turns' (w.exact_left).  Whole workgroup.
+template <class LDS>
+__device__ __forceinline__ void coarse_round4(LDS &L, WalkState &w, const XSrc &xs, const FxTables *T, const float2 (&twA)[7], const float2 (&twB)[7], int tid)
+{
+    constexpr int WAVES = LDS::WAVES;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __syncthreads();
+    load_span<64 * WAVES, (WAVES + 1) * FX_HOP>(L.cw, xs, w.pos - FX_HOP, w.floor_, tid);
+    __syncthreads();
+    w.hops_cheap += WAVES;
+    {
+        uint32_t bk;
+        const bool hit = coarse_hop(L.cw + FX_HOP * wave, L.scr[wave], T, lane, twA, twB, bk);   // this wave's 512-sample window
+        if (lane == 0) L.cand[wave] = hit ? bk : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    int hw = -1;
+#pragma unroll
+    for (int k = WAVES - 1; k >= 0; k--) if (L.cand[k] != 0xFFFFFFFFu) hw = k;
+    if (hw >= 0 && w.locked) {
+        // candidate in the window of grid hop hw: resume the exact detector there (one hop earlier when the
+        // candidate sits at the very start of the window -- the two correlators may disagree by a sample)
+        // The exact detector accepts a peak at lags below 512 - 156 only, like this one: a candidate well inside that range is
+        // this very hop's detection or nobody's (a false alarm of the cheap correlator costs ONE sweep of 50 transforms, not
+        // three); near either end of the range the two correlators may place it in the neighbouring hop.  Whatever this misjudges,
+        // the seek verifier finds (every hop of the span is checked there anyway) and the chain kernel repairs.
+        const uint32_t cl_ = L.cand[hw];
+        w.exact_left = cl_ >= FX_NFFT - FX_S_LEN - 12u ? 2 : 1;
+        if (cl_ < 8u && hw > 0) { hw--; w.exact_left = 2; }
+        w.hops_cheap -= WAVES - hw;
+        if (hw > 0) {
+            w.x2_0 = win_rearm(L, tid < HALF ? L.cw[FX_HOP * hw + tid] : make_float2(0.0f, 0.0f), tid);
+            w.pos += (int64_t)FX_HOP * hw; w.fresh = false;
+        }
+    } else if (hw >= 0) {
+        // candidate preamble at p: the exact detector takes over on the hop whose new half starts at p, behind a
+        // synchroniser reset at p - 256 (the hop before it -- zeros and x[p-256, p) -- cannot hold the preamble)
+        const int64_t p = w.pos - FX_HOP + (int64_t)FX_HOP * hw + (int64_t)L.cand[hw];
+        w.pos = p; w.floor_ = p - FX_HOP; w.fresh = false; w.exact_left = 2;
+        w.x2_0 = win_rearm(L, half_load(xs, w.pos - FX_HOP, w.floor_, tid), tid);
+    } else {
+        const float2 h = tid < HALF ? L.cw[WAVES * FX_HOP + tid] : make_float2(0.0f, 0.0f);   // last hop becomes the overlap half
+        if (w.locked) w.x2_0 = win_rearm(L, h, tid); else win_store(L, h, tid);
+        w.pos += WAVES * FX_HOP; w.fresh = false;
+    }
+    __syncthreads();
+}
+
+// One hop at w.pos, by wave 0 (fewer than four hops left before the segment's end / the end of the data).  Until a speculative
+// walker has locked onto the chain, nothing it produces is kept, so it may look for its first preamble any way it likes.  A CFO-blind
+// differential correlator needs 2 FFTs per hop instead of the 50 of the real detector: d[i] = w[i+1] conj(w[i]) against the
+// zero-mean td[k] = s[k+1] conj(s[k]).  Needs L.win written (overlap half published, new half nw stored by this thread: the first
+// barrier here publishes it); borrows L.X, L.scr[0], L.f[4], L.u[8].  Returns true when the exact detector is to run on this very
+// hop (a locked walker's hit; L.win stays).  Else carry on seeking: the overlap half of the hop at the new w.pos is published (a hit
+// of a walker not yet locked re-arms the exact detector one hop before the candidate).  Whole workgroup.
+template <class LDS>
+__device__ __forceinline__ bool coarse_round1(LDS &L, WalkState &w, const XSrc &xs, float2 nw, const FxTables *T, const float2 (&twA)[7], const float2 (&twB)[7], int tid)
+{
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool lo = tid < HALF;
+    __syncthreads();
+    w.hops_cheap++;
+    float2 d0 = lo ? cmulc(L.win[tid + 1], L.win[tid]) : make_float2(0.0f, 0.0f);
+    float2 d1 = (tid < 255) ? cmulc(L.win[tid + 257], L.win[tid + 256]) : make_float2(0.0f, 0.0f);
+    if (lo) { L.X[tid] = d0; L.X[tid + 256] = d1; }
+    // energy of d about its mean: oversampled signals give d a large DC term that is not information
+    float ed = block_sum256(cm2(d0) + cm2(d1), L, lane, wave);
+    const float2 dsum = block_csum256(cadd(d0, d1), L, lane, wave);
+    ed -= cm2(dsum) * (1.0f / (float)FX_NFFT);
+    if (wave == 0) {
+        float2 a[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) a[q] = L.X[lane + 64 * q];
+        float bv; uint32_t bk;
+        coarse_peak(a, L.X, L.scr[0], T, lane, twA, twB, bv, bk);
+        if (lane == 0) { L.f[4] = bv; L.u[8] = bk; }
+    }
+    __syncthreads();
+    const float cpk = L.f[4]; const uint32_t cl = L.u[8];
+    if (coarse_pass(cpk, ed, T)) {
+        if (w.locked) { w.exact_left = cl >= FX_NFFT - FX_S_LEN - 12u ? 2 : 1; w.hops_cheap--; return true; }   // run the exact detector on this very hop
+        // candidate preamble at p: the exact detector takes over on the hop whose new half starts at p (see coarse_round4)
+        const int64_t p = w.pos - FX_HOP + (int64_t)cl;
+        w.pos = p; w.floor_ = p - FX_HOP; w.fresh = false; w.exact_left = 2;
+        __syncthreads();
+        w.x2_0 = win_rearm(L, half_load(xs, w.pos - FX_HOP, w.floor_, tid), tid);
+        __syncthreads();
+        return false;
+    }
+    if (w.locked) w.x2_0 = win_rearm(L, nw, tid); else win_store(L, nw, tid);
+    w.pos += FX_HOP; w.fresh = false;
+    __syncthreads();
+    return false;
+}
+
+// ---- the header stage of a flex_rx detection, in walk_run's order.  All called by the whole workgroup; fr: the detection's frame
+// head after ALIGN (start, mix_th, mix_dl) with pfb, mfc0 and mf_scale set.
+// The <= 640 samples x[fr.start, fr.start + nh] mixed down into L.v (all of a thread's loads issued before the first is needed), the
+// filter branch's taps into L.taps.  Needs the last readers of L.v (ALIGN's are behind its barriers) done; leaves both written, not
+// published: the caller's barrier follows.
+template <class LDS>
+__device__ __forceinline__ void header_span_load(LDS &L, const XSrc &xs, const FxFrameHead &fr, int nh, int64_t floor_, const FxTables *T, const float2 *sc, int tid)
+{
+    constexpr int NT = 64 * LDS::WAVES, NLD = (640 + NT - 1) / NT;        // (nh < 640: the preamble + header span)
+    float2 ld[NLD];
+#pragma unroll
+    for (int k = 0; k < NLD; k++) { const int m = tid + NT * k; ld[k] = m <= nh ? xv(xs, fr.start + m, floor_) : make_float2(0.0f, 0.0f); }
+#pragma unroll
+    for (int k = 0; k < NLD; k++) { const int m = tid + NT * k; if (m <= nh) L.v[m] = derot(ld[k], fr.mix_th + fr.mix_dl * (uint32_t)m, sc); }
+    if (tid < FX_MF_TAPS) L.taps[tid] = T->proto[fr.pfb + FX_NPFB * tid];
+}
+
+// Equaliser training (liquid: eqlms, normalised LMS, mu = 0.05) by wave 0 on the 64 p/n symbols of the matched-filter outputs mfo
+// (published), frozen from the header on: lane i < 13 owns tap i, sums are 16-lane xor butterflies.  Leaves L.eqw written, not published.
+template <class LDS>
+__device__ __forceinline__ void eq_train(LDS &L, const float2 *mfo, const FxTables *T, int mfc0, int lane)
+{
+    constexpr int dly = FX_EQ_DELAY;
+    float2 w = lane < FX_EQ_TAPS ? make_float2(T->eq0[lane], 0.0f) : make_float2(0.0f, 0.0f);
+    for (int c = 2 * FX_M + dly; c < FX_SYM0_HDR + dly; c++) {
+        const int nc = (int)sym_sample(c, mfc0);
+        const float2 r = lane < FX_EQ_TAPS ? mfo[nc - (FX_EQ_TAPS - 1) + lane] : make_float2(0.0f, 0.0f);
+        float2 y = cmulc(r, w); float x2 = cm2(r);
+#pragma unroll
+        for (int mk = 1; mk < 16; mk <<= 1) { y.x += __shfl_xor(y.x, mk, 64); y.y += __shfl_xor(y.y, mk, 64); x2 += __shfl_xor(x2, mk, 64); }
+        if (x2 > 0.0f) {
+            const float2 d = T->pn[c - 2 * FX_M - dly];
+            const float2 e = make_float2(d.x - y.x, d.y - y.y);
+            const float g = FX_EQ_MU / x2;
+            const float2 cc = cmulc(r, e);
+            w.x = fmaf(g, cc.x, w.x); w.y = fmaf(g, cc.y, w.y);
+        }
+    }
+    if (lane < 16) L.eqw[lane] = w;
+}
+
+// The 295 header symbols into L.hdr.  Needs L.v[0, nh] and L.taps published; leaves L.hdr written, not published: the caller's barrier
+// follows.  EQ off: the matched filter at the symbols' samples, no barrier.  EQ on (liquid: FLEXFRAMESYNC_ENABLE_EQ): the matched
+// filter at every sample of the span into mfo (which borrows the coarse scan's window L.cw), barrier, eq_train, barrier (L.eqw
+// published, and stays for the frame record), then the 13-tap equaliser at 2 samples/symbol, three symbols later.
+template <bool EQ, class LDS>
+__device__ __forceinline__ void header_mf(LDS &L, const FxTables *T, const FxFrameHead &fr, int nh, int tid)
+{
+    if (!EQ) {
+        if (tid < FX_HDR_SYM) {
+            const float2 y = mf_sum<4>(L.v, L.taps, (int)sym_sample(FX_SYM0_HDR + tid, fr.mfc0));
+            L.hdr[tid] = make_float2(y.x * fr.mf_scale, y.y * fr.mf_scale);
+        }
+    } else {
+        float2 *mfo = L.cw;
+        for (int m = tid; m <= nh; m += 64 * LDS::WAVES) {
+            const float2 y = mf_sum<4, true>(L.v, L.taps, m);
+            mfo[m] = make_float2(y.x * fr.mf_scale, y.y * fr.mf_scale);
+        }
+        __syncthreads();
+        if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) eq_train(L, mfo, T, fr.mfc0, tid & 63);
+        __syncthreads();
+        if (tid < FX_HDR_SYM) {
+            const int nc = (int)sym_sample(FX_SYM0_HDR + FX_EQ_DELAY + tid, fr.mfc0);
+            L.hdr[tid] = eq_sum16(mfo + nc - (FX_EQ_TAPS - 1), L.eqw);
+        }
+    }
+}
+
+// Pilot sync: 32-point DFT of the 15 de-rotated pilots, peak and parabolic fit (frequency), then phase and gain of the pilots at that
+// frequency.  Needs L.hdr published; two barriers (after L.pb, after the DFT's |.|^2 in L.m2[0, 32)), both left published.  Result
+// on every thread; dl, ph: dphi, phi as 32-bit phase.
+struct PilotSync { float dphi, phi, gain; uint32_t dl, ph; };
+template <class LDS>
+__device__ __forceinline__ PilotSync pilot_sync(LDS &L, const FxTables *T, const float2 *sc, int tid)
+{
+    PilotSync ps;
+    if (tid < FX_HDR_PILOTS) L.pb[tid] = cmulc(L.hdr[FX_PILOT_SPACING * tid], T->pilots[tid]);
+    __syncthreads();
+    if (tid < 32) {
+        float ar = 0.0f, ai = 0.0f;
+        for (int p = 0; p < FX_HDR_PILOTS; p++) {
+            const float2 w = T->tw[16 * ((tid * p) & 31)], b = L.pb[p];
+            ar = fmaf(b.x, w.x, ar); ar = fmaf(-b.y, w.y, ar);
+            ai = fmaf(b.x, w.y, ai); ai = fmaf(b.y, w.x, ai);
+        }
+        L.m2[tid] = fmaf(ar, ar, ai * ai);
+    }
+    __syncthreads();
+    {
+        float best = -1.0f; unsigned i0 = 0;
+        for (unsigned k = 0; k < 32; k++) { float m = L.m2[k]; if (m > best) { best = m; i0 = k; } }
+        float y0 = sqrtf(L.m2[i0]), yneg = sqrtf(L.m2[(i0 + 31) & 31]), ypos = sqrtf(L.m2[(i0 + 1) & 31]);
+        float qa = 0.5f * (ypos + yneg) - y0, qb = 0.5f * (ypos - yneg);
+        float idx = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
+        float index = i0 < 16 ? (float)i0 : (float)i0 - 32.0f;
+        ps.dphi = (index + idx) * (6.28318531f / 512.0f);
+    }
+    ps.dl = rad2u32(ps.dphi);
+    {
+        float mr = 0.0f, mi = 0.0f;
+        for (unsigned p = 0; p < FX_HDR_PILOTS; p++) {
+            float2 t = derot(L.pb[p], ps.dl * (FX_PILOT_SPACING * p), sc);
+            mr += t.x; mi += t.y;
+        }
+        ps.phi = atan2c(mi, mr);
+        ps.gain = sqrtf(fmaf(mr, mr, mi * mi)) / (float)FX_HDR_PILOTS;
+    }
+    ps.ph = rad2u32(ps.phi);
+    return ps;
+}
+
+// The header's data symbols, de-rotated and scaled by the pilots' estimates, to bits and through the header's code.  Needs L.hdr
+// published.  SH off: hard QPSK labels (L.hs), barrier, packed to the 54 received bytes (L.b0), barrier, decode_header_bytes.  SH on:
+// the 432 soft values (L.hsoft(), the payload demapper's QPSK rule), barrier, decode_header_soft.  Leaves the 20 header bytes in
+// L.b1 and the CRC verdict in L.u[1], published.
+template <bool SH, class LDS>
+__device__ __forceinline__ void header_demod(LDS &L, const FxTables *T, const float2 *sc, const PilotSync &ps, int tid)
+{
+    const float pg = 1.0f / ps.gain;
+    if constexpr (SH) {
+        // MSB (y.y) then LSB (y.x) of data symbol nn (fx_softdemod_kernel)
+        if (tid < FX_HDR_SYM && (tid % FX_PILOT_SPACING) != 0) {
+            float2 y = derot(L.hdr[tid], ps.ph + ps.dl * (uint32_t)tid, sc);
+            y.x *= pg; y.y *= pg;
+            const int nn = tid - 1 - tid / FX_PILOT_SPACING;
+            constexpr float gamma16 = 1.2f * 4.0f * 16.0f;
+            soft_axis(-y.y, 1, 0.70710678118654752f, gamma16, L.hsoft() + 2 * nn);
+            soft_axis(-y.x, 1, 0.70710678118654752f, gamma16, L.hsoft() + 2 * nn + 1);
+        }
+        __syncthreads();
+        decode_header_soft(L, T, tid);
+    } else {
+        if (tid < FX_HDR_SYM && (tid % FX_PILOT_SPACING) != 0) {
+            float2 y = derot(L.hdr[tid], ps.ph + ps.dl * (uint32_t)tid, sc);
+            y.x *= pg; y.y *= pg;
+            const int nn = tid - 1 - tid / FX_PILOT_SPACING;           // data index (pilots removed)
+            L.hs[nn] = (uint8_t)((y.x > 0.0f ? 0u : 1u) | (y.y > 0.0f ? 0u : 2u));
+        }
+        __syncthreads();
+        if (tid < FX_HDR_ENC)
+            L.b0[tid] = (uint8_t)((L.hs[4 * tid] << 6) | (L.hs[4 * tid + 1] << 4) | (L.hs[4 * tid + 2] << 2) | L.hs[4 * tid + 3]);
+        __syncthreads();
+        decode_header_bytes(L, T, tid);
+    }
+}
+
+// The header's fields, by thread 0: protocol, modem, CRC and FEC ids checked, the payload's symbol count derived.  Needs L.b1 and
+// L.u[1] (CRC verdict) published; leaves L.u[1] (header valid), L.u[2..7] (pay_len, ms, check, fec0, fec1, nsym) published: the
+// barrier is the last thing here.
+template <class LDS>
+__device__ __forceinline__ void header_parse(LDS &L, int tid)
+{
+    if (tid == 0) {
+        int ok = (int)L.u[1];
+        unsigned pay_len = 0, ms = 0, check = 0, fec0 = 0, fec1 = 0, nsym = 0;
+        if (ok) {
+            const uint8_t *h = L.b1 + FX_HDR_USER;
+            pay_len = ((unsigned)h[1] << 8) | h[2]; ms = h[3];
+            check = (h[4] >> 5) & 7; fec0 = h[4] & 0x1f; fec1 = h[5] & 0x1f;
+            const unsigned bps = modem_bps(ms);
+            if (h[0] != FX_PROTOCOL || bps == 0 || check == FX_CRC_UNKNOWN || check > FX_CRC_32 ||
+                !fec_supported(fec0) || !fec_supported(fec1)) ok = 0;
+            else {
+                unsigned bits = 8 * fec_enc_len(fec1, fec_enc_len(fec0, pay_len + crc_len(check)));
+                nsym = (bits + bps - 1) / bps;
+            }
+        }
+        L.u[1] = (uint32_t)ok; L.u[2] = pay_len; L.u[3] = ms; L.u[4] = check; L.u[5] = fec0; L.u[6] = fec1; L.u[7] = nsym;
+    }
+    __syncthreads();
+}
+
 // One walk: the synchroniser's state machine from (start, floor, fresh) of `job` until the job's stop / hand-off / end of
 // data.  Called by the whole workgroup (fx_walk_kernel: once; fx_chain_kernel: for every repair).  L.S (template spectrum)
 // must be loaded; the result record and the frames go to global memory (thread 0), verification runs to `runs`.
@@ -851,16 +1173,18 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
     constexpr int WALK_WAVES = WW, WALK_THREADS = 64 * WW;
     const FxTables *T = T_in;
     const int tid_in = threadIdx.x;
-    const int tid = tid_in, lane = tid & 63, wave = tid >> 6;
+    const int tid = tid_in;
     const XSrc xs = make_xsrc(job.x, job.xa_end, job.n);
     const int64_t n = job.n;
 
-    int64_t pos = job.start, floor_ = job.floor, stop = job.stop;
+    WalkState w;
+    w.pos = job.start; w.floor_ = job.floor; w.fresh = job.fresh != 0; w.locked = job.prelock == 0;
+    w.exact_left = 0; w.x2_0 = 0.0f; w.hops = 0; w.hops_cheap = 0;
+    int64_t stop = job.stop;
     int ext_left = 6;
-    bool fresh = job.fresh != 0, in_handoff = false, locked = job.prelock == 0;
-    uint32_t nfr = 0, hops = 0, hops_cheap = 0, exact_left = 0, exit_code = FX_EXIT_STOP;
+    bool in_handoff = false;
+    uint32_t nfr = 0, exit_code = FX_EXIT_STOP;
     WalkHandoff ho;
-    float x2_0 = 0.0f;
     if (job.state_in) {
         // true walker of a continuing stream: the previous block's chain kernel left the resume state on the device
         const FxStreamState st = *job.state_in;
@@ -868,18 +1192,18 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
             if (tid == 0) write_invalid_result(result);
             return;
         }
-        pos = st.pos; floor_ = st.floor; fresh = st.fresh != 0;
+        w.pos = st.pos; w.floor_ = st.floor; w.fresh = st.fresh != 0;
     }
     // A locked flex_rx walker may skip hops its coarse scan finds empty (job.no_skip == 0): it stays on the true hop
     // grid and runs the exact detector only around coarse-scan candidates; every hop between span_pos and the next
     // detection is re-checked by fx_seekverify_kernel (the walker emits the runs itself when the span closes).
     const bool may_skip = job.no_skip == 0;
-    int64_t span_pos = pos, span_floor = floor_;
+    w.span_pos = w.pos; w.span_floor = w.floor_;
     // the span is the chain's business only if the walker was locked when the seek began
-    uint32_t span_flags = (fresh ? FX_FLAG_SEEK_FRESH : 0u) | ((!may_skip || !locked) ? FX_FLAG_SPAN_EXACT : 0u);
+    w.span_flags = (w.fresh ? FX_FLAG_SEEK_FRESH : 0u) | ((!may_skip || !w.locked) ? FX_FLAG_SPAN_EXACT : 0u);
     auto emit_runs = [&](int64_t end, uint32_t owner) {          // thread 0: hops [span_pos, end) to the verifier
-        if (span_flags & FX_FLAG_SPAN_EXACT) return false;
-        const int64_t nh = (end - span_pos) / FX_HOP;
+        if (w.span_flags & FX_FLAG_SPAN_EXACT) return false;
+        const int64_t nh = (end - w.span_pos) / FX_HOP;
         if (nh <= 0) return false;
         const uint32_t per = job.verify_per ? job.verify_per : 4u;
         const uint32_t nr = (uint32_t)((nh + per - 1) / per);
@@ -887,7 +1211,7 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         atomicAdd(&hdr->verify_hops, (uint32_t)nh);
         if ((uint64_t)base + nr > run_cap) return true;          // no room: the caller marks the span bad (walked again, exactly)
         for (uint32_t r = 0; r < nr; r++) {
-            FxVerifyRun v; v.pos = span_pos + (int64_t)r * per * FX_HOP; v.floor = span_floor; v.job = job_index; v.owner = owner;
+            FxVerifyRun v; v.pos = w.span_pos + (int64_t)r * per * FX_HOP; v.floor = w.span_floor; v.job = job_index; v.owner = owner;
             v.nhops = (uint32_t)min((int64_t)per, nh - (int64_t)r * per); v.pad_ = 0;
             runs[base + r] = v;
         }
@@ -910,16 +1234,15 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
     if (!EXT && job.prelock && job.prescan && !job.state_in) {
         int64_t p; uint32_t scanned;
         const bool took = fx_prescan_entry(job.prescan, job.prescan_words, job.prescan_hops, job.start, &p, &scanned);
-        if (took) { pos = p; floor_ = p - FX_HOP; fresh = false; exact_left = 2; }
-        else if (scanned) { pos = p; fresh = false; }
-        hops_cheap += scanned;
+        if (took) { w.pos = p; w.floor_ = p - FX_HOP; w.fresh = false; w.exact_left = 2; }
+        else if (scanned) { w.pos = p; w.fresh = false; }
+        w.hops_cheap += scanned;
         if (tid == 0) atomicAdd(took ? &hdr->ps_taken : &hdr->ps_fallback, 1u);
     }
 
-    const bool lo = tid < HALF;            // threads that own one sample of a 256-sample half
     __syncthreads();
-    if (fresh) { if (lo) L.win[tid] = make_float2(0.0f, 0.0f); }
-    else { float2 w = lo ? xv(xs, pos - FX_HOP + tid, floor_) : make_float2(0.0f, 0.0f); if (lo) L.win[tid] = w; x2_0 = block_sum256(cm2(w), L, lane, wave); }
+    if (w.fresh) win_store(L, make_float2(0.0f, 0.0f), tid);
+    else w.x2_0 = win_rearm(L, half_load(xs, w.pos - FX_HOP, w.floor_, tid), tid);
     __syncthreads();
 
     for (;;) {
@@ -932,157 +1255,59 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         const FxTables *T = T_in; asm volatile("" : "+s"(T));
         int tid = tid_in; asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const bool lo = tid < HALF;
         // the walk state is uniform across the workgroup: say so, so that it lives in scalar registers
-        pos = uniform64(pos); floor_ = uniform64(floor_); span_pos = uniform64(span_pos); span_floor = uniform64(span_floor);
-        x2_0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x2_0)));
-        nfr = __builtin_amdgcn_readfirstlane(nfr); hops = __builtin_amdgcn_readfirstlane(hops); hops_cheap = __builtin_amdgcn_readfirstlane(hops_cheap);
-        exact_left = __builtin_amdgcn_readfirstlane(exact_left);
-        if (pos >= stop && !in_handoff) {
+        w.pos = uniform64(w.pos); w.floor_ = uniform64(w.floor_); w.span_pos = uniform64(w.span_pos); w.span_floor = uniform64(w.span_floor);
+        w.x2_0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w.x2_0)));
+        nfr = __builtin_amdgcn_readfirstlane(nfr); w.hops = __builtin_amdgcn_readfirstlane(w.hops); w.hops_cheap = __builtin_amdgcn_readfirstlane(w.hops_cheap);
+        w.exact_left = __builtin_amdgcn_readfirstlane(w.exact_left);
+        if (w.pos >= stop && !in_handoff) {
             // a speculative walker that never locked has nothing to hand off (its state is not the chain's)
-            if (job.handoff && locked) in_handoff = true; else { exit_code = FX_EXIT_STOP; break; }
+            if (job.handoff && w.locked) in_handoff = true; else { exit_code = FX_EXIT_STOP; break; }
         }
-        if (pos + FX_HOP > n) { exit_code = FX_EXIT_NEED_DATA; break; }
+        if (w.pos + FX_HOP > n) { exit_code = FX_EXIT_NEED_DATA; break; }
 
-        // ------------------------------------------------------------ pre-lock coarse scan, four hops at a time
-        // (same differential correlator as the single-hop form below, one window per wave, no block barriers
-        // inside; used while at least four hops remain before the segment end / end of data)
-        if ((!locked || may_skip) && exact_left == 0 && pos + WALK_WAVES * FX_HOP <= n &&
-            (in_handoff || pos + (WALK_WAVES - 1) * FX_HOP < stop)) {
-            __syncthreads();
-            load_span<WALK_THREADS, (WALK_WAVES + 1) * FX_HOP>(L.cw, xs, pos - FX_HOP, floor_, tid);
-            __syncthreads();
-            hops_cheap += WALK_WAVES;
-            {
-                uint32_t bk;
-                const bool hit = coarse_hop(L.cw + FX_HOP * wave, L.scr[wave], T, lane, twA, twB, bk);   // this wave's 512-sample window
-                if (lane == 0) L.cand[wave] = hit ? bk : 0xFFFFFFFFu;
-            }
-            __syncthreads();
-            int hw = -1;
-#pragma unroll
-            for (int w = WALK_WAVES - 1; w >= 0; w--) if (L.cand[w] != 0xFFFFFFFFu) hw = w;
-            if (hw >= 0 && locked) {
-                // candidate in the window of grid hop hw: resume the exact detector there (one hop earlier when the
-                // candidate sits at the very start of the window -- the two correlators may disagree by a sample)
-                // The exact detector accepts a peak at lags below 512 - 156 only, like this one: a candidate well inside that range is
-                // this very hop's detection or nobody's (a false alarm of the cheap correlator costs ONE sweep of 50 transforms, not
-                // three); near either end of the range the two correlators may place it in the neighbouring hop.  Whatever this misjudges,
-                // the seek verifier finds (every hop of the span is checked there anyway) and the chain kernel repairs.
-                const uint32_t cl_ = L.cand[hw];
-                exact_left = cl_ >= FX_NFFT - FX_S_LEN - 12u ? 2 : 1;
-                if (cl_ < 8u && hw > 0) { hw--; exact_left = 2; }
-                hops_cheap -= WALK_WAVES - hw;
-                if (hw > 0) {
-                    const float2 w = lo ? L.cw[FX_HOP * hw + tid] : make_float2(0.0f, 0.0f);
-                    if (lo) L.win[tid] = w;
-                    x2_0 = block_sum256(cm2(w), L, lane, wave);
-                    pos += (int64_t)FX_HOP * hw; fresh = false;
-                }
-            } else if (hw >= 0) {
-                // candidate preamble at p: the exact detector takes over on the hop whose new half starts at p, behind a
-                // synchroniser reset at p - 256 (the hop before it -- zeros and x[p-256, p) -- cannot hold the preamble)
-                const int64_t p = pos - FX_HOP + (int64_t)FX_HOP * hw + (int64_t)L.cand[hw];
-                pos = p; floor_ = p - FX_HOP; fresh = false; exact_left = 2;
-                const float2 w = lo ? xv(xs, pos - FX_HOP + tid, floor_) : make_float2(0.0f, 0.0f);
-                if (lo) L.win[tid] = w;
-                x2_0 = block_sum256(cm2(w), L, lane, wave);
-            } else {
-                const float2 w = lo ? L.cw[WALK_WAVES * FX_HOP + tid] : make_float2(0.0f, 0.0f);
-                if (lo) L.win[tid] = w;                                  // last hop becomes the overlap half
-                if (locked) x2_0 = block_sum256(cm2(w), L, lane, wave);  // (a walker not yet locked re-arms fresh on a hit)
-                pos += WALK_WAVES * FX_HOP; fresh = false;
-            }
-            __syncthreads();
+        // ------------------------------------------------------------ coarse scan, four hops at a time
+        // (while at least four hops remain before the segment end / end of data)
+        const bool coarse = (!w.locked || may_skip) && w.exact_left == 0;
+        if (coarse && w.pos + WALK_WAVES * FX_HOP <= n && (in_handoff || w.pos + (WALK_WAVES - 1) * FX_HOP < stop)) {
+            coarse_round4(L, w, xs, T, twA, twB, tid);
             WSTAMP(0);
             continue;
         }
 
-        float2 nw = lo ? xv(xs, pos + tid, floor_) : make_float2(0.0f, 0.0f);
-        if (lo) L.win[FX_HOP + tid] = nw;
+        const float2 nw = half_load(xs, w.pos, w.floor_, tid);
+        if (tid < HALF) L.win[FX_HOP + tid] = nw;
 
-        // ------------------------------------------------------------ pre-lock coarse scan (speculative walkers only)
-        // Until a speculative walker has locked onto the chain, nothing it produces is kept, so it may look
-        // for its first preamble any way it likes.  A CFO-blind differential correlator needs 2 FFTs per hop
-        // instead of the 50 of the real detector: d[i] = w[i+1] conj(w[i]) against the zero-mean td[k] = s[k+1] conj(s[k]).
-        // A hit at lag l re-arms the exact detector (fresh) one hop before the candidate.
-        bool coarse_hit = false;
-        if ((!locked || may_skip) && exact_left == 0) {
-            __syncthreads();
-            hops_cheap++;
-            float2 d0 = lo ? cmulc(L.win[tid + 1], L.win[tid]) : make_float2(0.0f, 0.0f);
-            float2 d1 = (tid < 255) ? cmulc(L.win[tid + 257], L.win[tid + 256]) : make_float2(0.0f, 0.0f);
-            if (lo) { L.X[tid] = d0; L.X[tid + 256] = d1; }
-            // energy of d about its mean: oversampled signals give d a large DC term that is not information
-            float ed = block_sum256(cm2(d0) + cm2(d1), L, lane, wave);
-            const float2 dsum = block_csum256(cadd(d0, d1), L, lane, wave);
-            ed -= cm2(dsum) * (1.0f / (float)FX_NFFT);
-            if (wave == 0) {
-                float2 a[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) a[q] = L.X[lane + 64 * q];
-                float bv; uint32_t bk;
-                coarse_peak(a, L.X, L.scr[0], T, lane, twA, twB, bv, bk);
-                if (lane == 0) { L.f[4] = bv; L.u[8] = bk; }
-            }
-            __syncthreads();
-            const float cpk = L.f[4]; const uint32_t cl = L.u[8];
-            if (coarse_pass(cpk, ed, T)) {
-                if (locked) { coarse_hit = true; exact_left = cl >= FX_NFFT - FX_S_LEN - 12u ? 2 : 1; hops_cheap--; }   // run the exact detector on this very hop
-                else {
-                    // candidate preamble at p: the exact detector takes over on the hop whose new half starts at p (see above)
-                    const int64_t p = pos - FX_HOP + (int64_t)cl;
-                    pos = p; floor_ = p - FX_HOP; fresh = false; exact_left = 2;
-                    __syncthreads();
-                    const float2 w = lo ? xv(xs, pos - FX_HOP + tid, floor_) : make_float2(0.0f, 0.0f);
-                    if (lo) L.win[tid] = w;
-                    x2_0 = block_sum256(cm2(w), L, lane, wave);
-                    __syncthreads();
-                    continue;
-                }
-            }
-            if (!coarse_hit) {
-                if (lo) L.win[tid] = nw;
-                if (locked) x2_0 = block_sum256(cm2(nw), L, lane, wave);
-                pos += FX_HOP; fresh = false;
-                __syncthreads();
-                continue;
-            }
-        }
-        if (exact_left) exact_left--;
+        // ------------------------------------------------------------ coarse scan, one hop
+        if (coarse && !coarse_round1(L, w, xs, nw, T, twA, twB, tid)) continue;
+        if (w.exact_left) w.exact_left--;
 
         // ------------------------------------------------------------ SEEK: one 256-sample hop
         const float x2_1 = block_sum256(cm2(nw), L, lane, wave);     // barriers inside publish win[]
-        hops++;
+        w.hops++;
         bool det; uint32_t bidx; int boff; float peak;
-        det = seek_sweep(L, x2_0, x2_1, job.threshold, s2sum, twA, twB, lane, wave, bidx, boff, peak);
+        det = seek_sweep(L, w.x2_0, x2_1, job.threshold, s2sum, twA, twB, lane, wave, bidx, boff, peak);
         WSTAMP(1);
-        if (!det) {                                                    // slide the window by one hop
-            __syncthreads();
-            if (lo) L.win[tid] = nw;
-            x2_0 = x2_1; pos += FX_HOP; fresh = false;
-            __syncthreads();
-            continue;
-        }
+        if (!det) { win_slide(L, nw, w.x2_0, x2_1, w.pos, tid); w.fresh = false; continue; }
 
-        const int64_t a0 = pos - FX_HOP + (int64_t)bidx;
+        const int64_t a0 = w.pos - FX_HOP + (int64_t)bidx;
         if (in_handoff) {
             bool extend = false;
             if constexpr (EXT)
-                if (ext_left > 0 && all_jobs && handoff_extend<WALK_THREADS>(job, job_index, all_jobs, all_results, n_jobs_total, frames, a0, boff, floor_, nfr, FX_FLEX_SPACING, tid, stop)) { extend = true; ext_left--; in_handoff = false; }
-            if (!extend) { ho.has = 1; ho.start = a0; ho.off = boff; ho.rxy = peak; ho.pos = pos; ho.clear = floor_ <= a0 ? 1u : 0u; exit_code = FX_EXIT_STOP; break; }
+                if (ext_left > 0 && all_jobs && handoff_extend<WALK_THREADS>(job, job_index, all_jobs, all_results, n_jobs_total, frames, a0, boff, w.floor_, nfr, FX_FLEX_SPACING, tid, stop)) { extend = true; ext_left--; in_handoff = false; }
+            if (!extend) { ho.has = 1; ho.start = a0; ho.off = boff; ho.rxy = peak; ho.pos = w.pos; ho.clear = w.floor_ <= a0 ? 1u : 0u; exit_code = FX_EXIT_STOP; break; }
         }
         if (nfr >= job.max_frames) { exit_code = FX_EXIT_TABLE_FULL; break; }
         if (a0 + FX_NFFT > n) { exit_code = FX_EXIT_NEED_DATA; break; }
 
         // ------------------------------------------------------------ ALIGN on x[a0, a0+512)
         __syncthreads();
-        load_span<WALK_THREADS, FX_NFFT>(L.win, xs, a0, floor_, tid);
+        load_span<WALK_THREADS, FX_NFFT>(L.win, xs, a0, w.floor_, tid);
         __syncthreads();
         float tau, gamma, dphi, phi; uint32_t mix_dl;
         align_estimate(L.win, L.X, L.P, L.m2, L.scr[0], L, boff, s2sum, T, sc, twA, twB, tid, tau, gamma, dphi, mix_dl, phi);
         WSTAMP(2);
-        FxFrameHead fr = detection_head(a0, boff, peak, tau, gamma, dphi, mix_dl, phi, span_pos, span_floor, span_flags, pos, floor_);
+        FxFrameHead fr = detection_head(a0, boff, peak, tau, gamma, dphi, mix_dl, phi, w.span_pos, w.span_floor, w.span_flags, w.pos, w.floor_);
         // ------------------------------------------------------------ flex_rx: preamble + header span
         if (tau > 0.0f) { fr.pfb = (unsigned)f2i_sat(tau * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 0; }
         else { fr.pfb = (unsigned)f2i_sat((1.0f + tau) * (float)FX_NPFB) % FX_NPFB; fr.mfc0 = 1; }
@@ -1090,149 +1315,16 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         constexpr int dly = EQ ? FX_EQ_DELAY : 0;                      // the equaliser moves every symbol instant 3 symbols later
         const int nh = (int)sym_sample(FX_SYM0_PAY + dly - 1, fr.mfc0);  // sample of the last header symbol
         if (a0 + nh + 1 > n) { exit_code = FX_EXIT_NEED_DATA; break; }
-        {
-            constexpr int NLD = (640 + WALK_THREADS - 1) / WALK_THREADS;        // (nh < 640: the preamble + header span)
-            float2 ld[NLD];
-#pragma unroll
-            for (int k = 0; k < NLD; k++) { const int m = tid + WALK_THREADS * k; ld[k] = m <= nh ? xv(xs, a0 + m, floor_) : make_float2(0.0f, 0.0f); }
-#pragma unroll
-            for (int k = 0; k < NLD; k++) { const int m = tid + WALK_THREADS * k; if (m <= nh) L.v[m] = derot(ld[k], fr.mix_th + mix_dl * (uint32_t)m, sc); }
-        }
-        if (tid < FX_MF_TAPS) L.taps[tid] = T->proto[fr.pfb + FX_NPFB * tid];
+        header_span_load(L, xs, fr, nh, w.floor_, T, sc, tid);
         __syncthreads();
-        if (!EQ) {
-            if (tid < FX_HDR_SYM) {
-                const int nc = (int)sym_sample(FX_SYM0_HDR + tid, fr.mfc0);
-                float ar = 0.0f, ai = 0.0f;
-#pragma unroll 4
-                for (int t = 0; t < FX_MF_TAPS; t++) {
-                    const float2 w = L.v[nc - t]; const float h = L.taps[t];
-                    ar = fmaf(h, w.x, ar); ai = fmaf(h, w.y, ai);
-                }
-                L.hdr[tid] = make_float2(ar * fr.mf_scale, ai * fr.mf_scale);
-            }
-        } else {
-            // Equaliser stage (liquid: FLEXFRAMESYNC_ENABLE_EQ): the matched filter is evaluated at every sample, a 13-tap
-            // eqlms at 2 samples/symbol follows it, trained on the 64 p/n symbols (normalised LMS, mu = 0.05) and frozen
-            // from the header on.  mfo[] (matched-filter outputs of the whole span) borrows the coarse scan's window.
-            float2 *mfo = L.cw;
-            for (int m = tid; m <= nh; m += WALK_THREADS) {
-                float ar = 0.0f, ai = 0.0f;
-#pragma unroll 4
-                for (int t = 0; t < FX_MF_TAPS; t++) {
-                    const float2 w = (m - t >= 0) ? L.v[m - t] : make_float2(0.0f, 0.0f); const float h = L.taps[t];
-                    ar = fmaf(h, w.x, ar); ai = fmaf(h, w.y, ai);
-                }
-                mfo[m] = make_float2(ar * fr.mf_scale, ai * fr.mf_scale);
-            }
-            __syncthreads();
-            if (wave == 0) {                                               // lane i < 13 owns tap i; sums are 16-lane xor butterflies
-                float2 w = lane < FX_EQ_TAPS ? make_float2(T->eq0[lane], 0.0f) : make_float2(0.0f, 0.0f);
-                for (int c = 2 * FX_M + dly; c < FX_SYM0_HDR + dly; c++) {
-                    const int nc = (int)sym_sample(c, fr.mfc0);
-                    const float2 r = lane < FX_EQ_TAPS ? mfo[nc - (FX_EQ_TAPS - 1) + lane] : make_float2(0.0f, 0.0f);
-                    float2 y = cmulc(r, w); float x2 = cm2(r);
-#pragma unroll
-                    for (int mk = 1; mk < 16; mk <<= 1) { y.x += __shfl_xor(y.x, mk, 64); y.y += __shfl_xor(y.y, mk, 64); x2 += __shfl_xor(x2, mk, 64); }
-                    if (x2 > 0.0f) {
-                        const float2 d = T->pn[c - 2 * FX_M - dly];
-                        const float2 e = make_float2(d.x - y.x, d.y - y.y);
-                        const float g = FX_EQ_MU / x2;
-                        const float2 cc = cmulc(r, e);
-                        w.x = fmaf(g, cc.x, w.x); w.y = fmaf(g, cc.y, w.y);
-                    }
-                }
-                if (lane < 16) L.eqw[lane] = w;
-            }
-            __syncthreads();
-            if (tid < FX_HDR_SYM) {
-                const int nc = (int)sym_sample(FX_SYM0_HDR + dly + tid, fr.mfc0);
-                L.hdr[tid] = eq_sum16(mfo + nc - (FX_EQ_TAPS - 1), L.eqw);
-            }
-        }
+        header_mf<EQ>(L, T, fr, nh, tid);
         __syncthreads();
-        // pilot sync: 32-point DFT of the 15 de-rotated pilots
-        if (tid < FX_HDR_PILOTS) L.pb[tid] = cmulc(L.hdr[FX_PILOT_SPACING * tid], T->pilots[tid]);
-        __syncthreads();
-        if (tid < 32) {
-            float ar = 0.0f, ai = 0.0f;
-            for (int p = 0; p < FX_HDR_PILOTS; p++) {
-                const float2 w = T->tw[16 * ((tid * p) & 31)], b = L.pb[p];
-                ar = fmaf(b.x, w.x, ar); ar = fmaf(-b.y, w.y, ar);
-                ai = fmaf(b.x, w.y, ai); ai = fmaf(b.y, w.x, ai);
-            }
-            L.m2[tid] = fmaf(ar, ar, ai * ai);
-        }
-        __syncthreads();
-        float pdphi, pphi, pgain;
-        {
-            float best = -1.0f; unsigned i0 = 0;
-            for (unsigned k = 0; k < 32; k++) { float m = L.m2[k]; if (m > best) { best = m; i0 = k; } }
-            float y0 = sqrtf(L.m2[i0]), yneg = sqrtf(L.m2[(i0 + 31) & 31]), ypos = sqrtf(L.m2[(i0 + 1) & 31]);
-            float qa = 0.5f * (ypos + yneg) - y0, qb = 0.5f * (ypos - yneg);
-            float idx = qa == 0.0f ? 0.0f : -qb / (2.0f * qa);
-            float index = i0 < 16 ? (float)i0 : (float)i0 - 32.0f;
-            pdphi = (index + idx) * (6.28318531f / 512.0f);
-        }
-        const uint32_t pdl = rad2u32(pdphi);
-        {
-            float mr = 0.0f, mi = 0.0f;
-            for (unsigned p = 0; p < FX_HDR_PILOTS; p++) {
-                float2 t = derot(L.pb[p], pdl * (FX_PILOT_SPACING * p), sc);
-                mr += t.x; mi += t.y;
-            }
-            pphi = atan2c(mi, mr);
-            pgain = sqrtf(fmaf(mr, mr, mi * mi)) / (float)FX_HDR_PILOTS;
-        }
-        const uint32_t pph = rad2u32(pphi);
-        const float pg = 1.0f / pgain;
-        if constexpr (SH) {
-            // soft header: the payload demapper's QPSK rule (fx_softdemod_kernel), MSB (y.y) then LSB (y.x) of data symbol nn
-            if (tid < FX_HDR_SYM && (tid % FX_PILOT_SPACING) != 0) {
-                float2 y = derot(L.hdr[tid], pph + pdl * (uint32_t)tid, sc);
-                y.x *= pg; y.y *= pg;
-                const int nn = tid - 1 - tid / FX_PILOT_SPACING;
-                constexpr float gamma16 = 1.2f * 4.0f * 16.0f;
-                soft_axis(-y.y, 1, 0.70710678118654752f, gamma16, L.hsoft() + 2 * nn);
-                soft_axis(-y.x, 1, 0.70710678118654752f, gamma16, L.hsoft() + 2 * nn + 1);
-            }
-            __syncthreads();
-            decode_header_soft(L, T, tid);
-        } else {
-            if (tid < FX_HDR_SYM && (tid % FX_PILOT_SPACING) != 0) {
-                float2 y = derot(L.hdr[tid], pph + pdl * (uint32_t)tid, sc);
-                y.x *= pg; y.y *= pg;
-                const int nn = tid - 1 - tid / FX_PILOT_SPACING;           // data index (pilots removed)
-                L.hs[nn] = (uint8_t)((y.x > 0.0f ? 0u : 1u) | (y.y > 0.0f ? 0u : 2u));
-            }
-            __syncthreads();
-            if (tid < FX_HDR_ENC)
-                L.b0[tid] = (uint8_t)((L.hs[4 * tid] << 6) | (L.hs[4 * tid + 1] << 4) | (L.hs[4 * tid + 2] << 2) | L.hs[4 * tid + 3]);
-            __syncthreads();
-            decode_header_bytes(L, T, tid);
-        }
-        if (tid == 0) {
-            const uint8_t *hd = L.b1;
-            int ok = (int)L.u[1];
-            unsigned pay_len = 0, ms = 0, check = 0, fec0 = 0, fec1 = 0, nsym = 0;
-            if (ok) {
-                const uint8_t *h = hd + FX_HDR_USER;
-                pay_len = ((unsigned)h[1] << 8) | h[2]; ms = h[3];
-                check = (h[4] >> 5) & 7; fec0 = h[4] & 0x1f; fec1 = h[5] & 0x1f;
-                const unsigned bps = modem_bps(ms);
-                if (h[0] != FX_PROTOCOL || bps == 0 || check == FX_CRC_UNKNOWN || check > FX_CRC_32 ||
-                    !fec_supported(fec0) || !fec_supported(fec1)) ok = 0;
-                else {
-                    unsigned bits = 8 * fec_enc_len(fec1, fec_enc_len(fec0, pay_len + crc_len(check)));
-                    nsym = (bits + bps - 1) / bps;
-                }
-            }
-            L.u[1] = (uint32_t)ok; L.u[2] = pay_len; L.u[3] = ms; L.u[4] = check; L.u[5] = fec0; L.u[6] = fec1; L.u[7] = nsym;
-        }
-        __syncthreads();
+        const PilotSync ps = pilot_sync(L, T, sc, tid);
+        header_demod<SH>(L, T, sc, ps, tid);
+        header_parse(L, tid);
         const bool hv = L.u[1] != 0;
-        fr.pilot_dphi = pdphi; fr.pilot_phi = pphi; fr.pilot_gain = pgain;
-        fr.pll_f = pdphi; fr.pll_th = pph + pdl * (uint32_t)FX_HDR_SYM;
+        fr.pilot_dphi = ps.dphi; fr.pilot_phi = ps.phi; fr.pilot_gain = ps.gain;
+        fr.pll_f = ps.dphi; fr.pll_th = ps.ph + ps.dl * (uint32_t)FX_HDR_SYM;
 #pragma unroll
         for (int j = 0; j < FX_HDR_DEC; j++) fr.header[j] = L.b1[j];
         int64_t last_c = FX_SYM0_PAY + dly - 1;
@@ -1243,19 +1335,16 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         }
         fr.next = a0 + sym_sample(last_c, fr.mfc0) + 1;
         WSTAMP(3);
-        if (!locked && !hv) {
+        if (!w.locked && !hv) {
             // speculative walker, header did not check out: most likely a false alarm on payload data.
             // Do not skip the 618 samples a real invalid frame would consume (a true preamble may sit
             // there); resume seeking on the same grid.  Nothing before the lock is ever spliced.
             if (tid == 0) static_cast<FxFrameHead &>(frames[job.frame_base + nfr]) = fr;
             nfr++;
-            __syncthreads();
-            if (lo) L.win[tid] = nw;
-            x2_0 = x2_1; pos += FX_HOP; fresh = false;
-            __syncthreads();
+            win_slide(L, nw, w.x2_0, x2_1, w.pos, tid); w.fresh = false;
             continue;
         }
-        locked = true; fr.flags |= FX_FLAG_EXACT;
+        w.locked = true; fr.flags |= FX_FLAG_EXACT;
         bool incomplete = fr.next > n;
         if (incomplete) fr.flags |= FX_FLAG_INCOMPLETE;
         if (tid == 0) {
@@ -1266,18 +1355,18 @@ __device__ __forceinline__ void walk_run(const FxWalkJob &job, uint32_t job_inde
         nfr++;
         if (incomplete) { exit_code = FX_EXIT_PAYLOAD; break; }
         // synchroniser reset: fresh detector right after the frame's last symbol
-        pos = fr.next; floor_ = fr.next; fresh = true; x2_0 = 0.0f;
-        span_pos = pos; span_floor = floor_; span_flags = FX_FLAG_SEEK_FRESH | (may_skip ? 0u : FX_FLAG_SPAN_EXACT);
+        w.pos = fr.next; w.floor_ = fr.next; w.fresh = true; w.x2_0 = 0.0f;
+        w.span_pos = w.pos; w.span_floor = w.floor_; w.span_flags = FX_FLAG_SEEK_FRESH | (may_skip ? 0u : FX_FLAG_SPAN_EXACT);
         __syncthreads();
-        if (lo) L.win[tid] = make_float2(0.0f, 0.0f);
+        win_store(L, make_float2(0.0f, 0.0f), tid);
         __syncthreads();
     }
 
     if (tid == 0) {
-        uint32_t tail_flags = span_flags;
-        if (emit_runs(ho.has ? ho.pos : pos, 0x80000000u | job_index)) tail_flags |= FX_FLAG_SPAN_BAD;
-        write_walk_result(result, hdr, nfr, exit_code, pos, floor_, fresh, ho, hops, hops_cheap, span_pos, span_floor, tail_flags, wst_);
-        atomicAdd(&hdr->hops_cheap, hops_cheap);
+        uint32_t tail_flags = w.span_flags;
+        if (emit_runs(ho.has ? ho.pos : w.pos, 0x80000000u | job_index)) tail_flags |= FX_FLAG_SPAN_BAD;
+        write_walk_result(result, hdr, nfr, exit_code, w.pos, w.floor_, w.fresh, ho, w.hops, w.hops_cheap, w.span_pos, w.span_floor, tail_flags, wst_);
+        atomicAdd(&hdr->hops_cheap, w.hops_cheap);
     }
 }
 
@@ -1435,27 +1524,21 @@ void fx_seekverify_kernel(const FxVerifyRun *runs, uint32_t run_cap, const FxWal
     for (uint32_t ri = run0 + blockIdx.x; ri < nruns; ri += gridDim.x) {
         int tid = tid_in; asm volatile("" : "+v"(tid));        // (indices are computed where they are used, not kept: see walk_run)
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const bool lo = tid < HALF;
         const FxVerifyRun run = runs[ri];
         const FxWalkJob &jb = jobs[run.job];
         const XSrc xs = make_xsrc(jb.x, jb.xa_end, jb.n);
         const float threshold = jb.threshold;
         int64_t pos = run.pos;
         __syncthreads();
-        float2 w = lo ? xv(xs, pos - FX_HOP + tid, run.floor) : make_float2(0.0f, 0.0f);
-        if (lo) L.win[tid] = w;
-        float x2_0 = block_sum256(cm2(w), L, lane, wave);
+        float x2_0 = win_rearm(L, half_load(xs, pos - FX_HOP, run.floor, tid), tid);
         bool fired = false;
         for (uint32_t h = 0; h < run.nhops; h++) {
-            const float2 nw = lo ? xv(xs, pos + tid, run.floor) : make_float2(0.0f, 0.0f);
-            if (lo) L.win[FX_HOP + tid] = nw;
+            const float2 nw = half_load(xs, pos, run.floor, tid);
+            if (tid < HALF) L.win[FX_HOP + tid] = nw;
             const float x2_1 = block_sum256(cm2(nw), L, lane, wave);
             uint32_t bidx; int boff; float peak;
             if (seek_sweep(L, x2_0, x2_1, threshold, s2sum, twA, twB, lane, wave, bidx, boff, peak)) { fired = true; break; }
-            __syncthreads();
-            if (lo) L.win[tid] = nw;
-            x2_0 = x2_1; pos += FX_HOP;
-            __syncthreads();
+            win_slide(L, nw, x2_0, x2_1, pos, tid);
         }
         if (fired && tid == 0) {
             if (run.owner & 0x80000000u) atomicOr(&results[run.owner & 0x7fffffffu].tail_flags, (uint32_t)FX_FLAG_SPAN_BAD);
@@ -2539,17 +2622,17 @@ extern "C" unsigned fx_plan_ws_words(void) { return PW_WORDS; }
 #define PMF_SYMS    1024          // symbols per workgroup
 #define PMF_SPAN    (2 * PMF_SYMS + FX_MF_TAPS)
 
-// Work items (frame, first symbol) come from fx_plan_kernel; their number is only known on the device, so the grid is
-// sized from the host's estimate and strides over the list.  EQ: the equaliser stage is on -- the matched filter is
-// evaluated at every sample of the item's span and the frame's 13 trained taps combine 13 of its outputs per symbol.
-template <bool EQ>
+// The equalised payload filter (equaliser stage on; without it fx_paymf4_kernel below).  Work items (frame, first symbol) come from
+// fx_plan_kernel; their number is only known on the device, so the grid is sized from the host's estimate and strides over the
+// list.  The matched filter is evaluated at every sample of the item's span and the frame's 13 trained taps combine 13 of its
+// outputs per symbol.
 __global__ __launch_bounds__(PMF_THREADS)
 void fx_paymf_kernel(const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr, const FxFrame *chain, float2 *sym_raw,
                      const FxTables *T)
 {
-    constexpr int LEAD = EQ ? FX_EQ_TAPS - 1 : 0;
+    constexpr int LEAD = FX_EQ_TAPS - 1;
     __shared__ float2 v[PMF_SPAN + LEAD + 4];
-    __shared__ float2 u[EQ ? 2 * PMF_SYMS + FX_EQ_TAPS : 1];
+    __shared__ float2 u[2 * PMF_SYMS + FX_EQ_TAPS];
     __shared__ float2 eqw[16];
     __shared__ float taps[FX_MF_TAPS];
     const uint32_t nitems = hdr->n_mfblk;
@@ -2559,46 +2642,28 @@ void fx_paymf_kernel(const FxPayJob *jobs, const uint32_t *blk_job, const uint32
         const FxPayJob job = jobs[blk_job[bi]];
         const uint32_t c0 = blk_c0[bi];                            // first payload symbol of this item
         const uint32_t ns = min((uint32_t)PMF_SYMS, job.nsym - c0);
-        const int64_t sym0 = (int64_t)FX_SYM0_PAY + (EQ ? FX_EQ_DELAY : 0);
+        const int64_t sym0 = (int64_t)FX_SYM0_PAY + FX_EQ_DELAY;
         const int64_t nlo = sym_sample(sym0 + c0, job.mfc0) - LEAD - (FX_MF_TAPS - 1);
         const int64_t nhi = sym_sample(sym0 + c0 + ns - 1, job.mfc0);
         const int span = (int)(nhi - nlo + 1);
         const XSrc xs = make_xsrc(job.x, job.xa_end, 0);
         __syncthreads();
         if (tid < FX_MF_TAPS) taps[tid] = T->proto[job.pfb + FX_NPFB * tid];
-        if (EQ && tid < 16) eqw[tid] = tid < FX_EQ_TAPS ? chain[job.chain_idx].eq[tid] : make_float2(0.0f, 0.0f);
+        if (tid < 16) eqw[tid] = tid < FX_EQ_TAPS ? chain[job.chain_idx].eq[tid] : make_float2(0.0f, 0.0f);
         for (int m = tid; m < span; m += PMF_THREADS) {
             const int64_t nn = nlo + m;                            // (nn >= 0: a payload symbol is hundreds of samples into the frame)
             v[m] = derot(xld(xs, job.start + nn), job.mix_th + job.mix_dl * (uint32_t)nn, sc);
         }
         __syncthreads();
-        if (EQ) {
-            const int nu = span - (FX_MF_TAPS - 1);                // matched-filter outputs at samples nlo + 27 ... nhi
-            for (int m = tid; m < nu; m += PMF_THREADS) {
-                float ar = 0.0f, ai = 0.0f;
-#pragma unroll 7
-                for (int t = 0; t < FX_MF_TAPS; t++) {
-                    const float2 w = v[m + (FX_MF_TAPS - 1) - t]; const float h = taps[t];
-                    ar = fmaf(h, w.x, ar); ai = fmaf(h, w.y, ai);
-                }
-                u[m] = make_float2(ar * job.mf_scale, ai * job.mf_scale);
-            }
-            __syncthreads();
-            for (uint32_t i = tid; i < ns; i += PMF_THREADS) {
-                const int nc = (int)(sym_sample(sym0 + c0 + i, job.mfc0) - nlo) - (FX_MF_TAPS - 1);   // index of the symbol's sample in u[]
-                sym_raw[(size_t)job.sym_off + c0 + i] = eq_sum16(u + nc - (FX_EQ_TAPS - 1), eqw);
-            }
-        } else {
-            for (uint32_t i = tid; i < ns; i += PMF_THREADS) {
-                const int nc = (int)(sym_sample(sym0 + c0 + i, job.mfc0) - nlo);
-                float ar = 0.0f, ai = 0.0f;
-#pragma unroll 7
-                for (int t = 0; t < FX_MF_TAPS; t++) {
-                    const float2 w = v[nc - t]; const float h = taps[t];
-                    ar = fmaf(h, w.x, ar); ai = fmaf(h, w.y, ai);
-                }
-                sym_raw[(size_t)job.sym_off + c0 + i] = make_float2(ar * job.mf_scale, ai * job.mf_scale);
-            }
+        const int nu = span - (FX_MF_TAPS - 1);                    // matched-filter outputs at samples nlo + 27 ... nhi
+        for (int m = tid; m < nu; m += PMF_THREADS) {
+            const float2 y = mf_sum<7>(v, taps, m + (FX_MF_TAPS - 1));
+            u[m] = make_float2(y.x * job.mf_scale, y.y * job.mf_scale);
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < ns; i += PMF_THREADS) {
+            const int nc = (int)(sym_sample(sym0 + c0 + i, job.mfc0) - nlo) - (FX_MF_TAPS - 1);   // index of the symbol's sample in u[]
+            sym_raw[(size_t)job.sym_off + c0 + i] = eq_sum16(u + nc - (FX_EQ_TAPS - 1), eqw);
         }
     }
 }
@@ -2684,7 +2749,7 @@ extern "C" hipError_t fx_launch_paymf(unsigned grid, int eq, hipStream_t st, con
                                       const FxFrame *chain, float2 *sym_raw, const FxTables *T)
 {
     if (grid == 0) return hipSuccess;
-    if (eq) hipLaunchKernelGGL(fx_paymf_kernel<true>, dim3(grid), dim3(PMF_THREADS), 0, st, jobs, blk_job, blk_c0, hdr, chain, sym_raw, T);
+    if (eq) hipLaunchKernelGGL(fx_paymf_kernel, dim3(grid), dim3(PMF_THREADS), 0, st, jobs, blk_job, blk_c0, hdr, chain, sym_raw, T);
     else hipLaunchKernelGGL(fx_paymf4_kernel, dim3(grid), dim3(PMF_THREADS), 0, st, jobs, blk_job, blk_c0, hdr, sym_raw, T);
     return hipGetLastError();
 }
