@@ -50,8 +50,12 @@ class ConfigChain(Config):                  # fxrx_config up to soft_chain: Conf
     _fields_ = [("soft_chain", C.c_int)]
 
 
-class ConfigRs(ConfigChain):                # the whole fxrx_config: fxrx_create takes this one
+class ConfigRs(ConfigChain):                # fxrx_config up to soft_rs
     _fields_ = [("soft_rs", C.c_int)]
+
+
+class ConfigRsChain(ConfigRs):              # the whole fxrx_config: fxrx_create takes this one
+    _fields_ = [("soft_rs_fmax", C.c_int), ("soft_rs_chain", C.c_int)]
 
 
 class Frame(C.Structure):                   # fxrx_frame
@@ -98,6 +102,7 @@ EXPORTS = [
     "fxrx_debug_header_decode", "fxrx_debug_block_decode", "fxrx_sync_set_soft_block",
     "fxrx_debug_block_siso", "fxrx_sync_set_soft_chain",
     "fxrx_debug_rs_soft", "fxrx_sync_set_soft_rs",
+    "fxrx_debug_rs_chain", "fxrx_sync_set_soft_rs_fmax", "fxrx_sync_set_soft_rs_chain",
     "fxrx_sync_set_streaming", "fxrx_qdet_flush", "fxrx_qdet_pending", "fxrx_qdet_set_block", "fxrx_qdet_context",
     "fxrx_iq_sample_bytes", "fxrx_set_iq_scale", "fxrx_submit_fmt", "fxrx_process_fmt", "fxrx_iq_convert_host", "fxtx_quantize",
 ]
@@ -250,6 +255,10 @@ def lib():
     L.fxrx_debug_rs_soft.restype = C.c_int
     L.fxrx_debug_rs_soft.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fxrx_debug_block_siso.argtypes = [C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
+    L.fxrx_sync_set_soft_rs_fmax.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_rs_fmax.restype = C.c_int
+    L.fxrx_sync_set_soft_rs_chain.argtypes = [C.c_void_p, C.c_int]; L.fxrx_sync_set_soft_rs_chain.restype = C.c_int
+    L.fxrx_debug_rs_chain.restype = C.c_int
+    L.fxrx_debug_rs_chain.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.flexframesync_decode_header_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_header_soft.restype = C.c_int
     L.flexframesync_decode_payload_soft.argtypes = [C.c_void_p, C.c_int]; L.flexframesync_decode_payload_soft.restype = C.c_int
     L.fxrx_sync_pending.argtypes = [C.c_void_p]; L.fxrx_sync_pending.restype = C.c_uint

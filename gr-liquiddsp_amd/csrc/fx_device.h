@@ -33,6 +33,8 @@ struct FxTables {
     uint8_t  h84enc[16];                   // Hamming(8,4) codewords (soft header decoding)
     uint32_t h74enc[16], h128enc[256];     // Hamming(7,4) / (12,8) codewords (soft block decoding)
     uint8_t  sdinv[3][256];                // SECDED (22,16) / (39,32) / (72,64): syndrome -> data column index + 1, 0 = none
+    uint32_t rs_fmax;                      // not a table: the context's bound on f for soft Reed-Solomon decoding (fxrx_config.soft_rs_fmax), 0 .. 32;
+                                           // last, so that no other field moves; read by fx_paydec_kernel's SR instances only
 };
 
 #define FX_DEV __device__ __forceinline__

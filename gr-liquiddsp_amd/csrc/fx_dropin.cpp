@@ -78,7 +78,7 @@ bool alloc_ring(std::vector<fx_complex *> &ring, unsigned count, size_t samples)
 // (every few thousand samples) finds the oldest one done; their frames wait in `pending` and leave one per call.
 struct fxrx_sync_s {
     framesync_callback cb = nullptr; void *ud = nullptr;
-    fxrx_ctx *ctx = nullptr; float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0, soft_block = 0, soft_chain = 0, soft_rs = 0;
+    fxrx_ctx *ctx = nullptr; float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0, soft_block = 0, soft_chain = 0, soft_rs = 0, soft_rs_fmax = 0, soft_rs_chain = 0;
     unsigned block = kSyncBlockDefault, depth = kSyncDepthDefault;
     std::vector<fx_complex *> bufs; unsigned cur = 0; size_t fill = 0;     // ring of depth + 1 pinned input buffers of `block` samples
     std::deque<HeldFrame> pending; HeldFrame current;
@@ -152,7 +152,8 @@ static fxrx_ctx *sync_make_ctx(const fxrx_sync_s *q)
 {
     fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_FLEX_RX; cfg.n_streams = 1; cfg.want_framesyms = 1;
     if (q) { cfg.threshold = q->threshold; cfg.equalizer = q->equalizer; cfg.soft_decision = q->soft; cfg.soft_header = q->soft_header;
-            cfg.soft_block = q->soft && q->soft_block; cfg.soft_chain = q->soft && q->soft_block && q->soft_chain; cfg.soft_rs = q->soft && q->soft_rs; }
+            cfg.soft_block = q->soft && q->soft_block; cfg.soft_chain = q->soft && q->soft_block && q->soft_chain; cfg.soft_rs = q->soft && q->soft_rs;
+            cfg.soft_rs_fmax = cfg.soft_rs ? q->soft_rs_fmax : 0; cfg.soft_rs_chain = cfg.soft_rs && q->soft_rs_chain; }
     if (const char *d = std::getenv("FXRX_DEVICE")) cfg.device = std::atoi(d);
     fxrx_ctx *ctx = fxrx_create(&cfg);
     if (ctx && fxrx_set_depth(ctx, q ? q->depth : kSyncDepthDefault) != 0) { fxrx_destroy(ctx); return nullptr; }
@@ -231,14 +232,15 @@ static bool sync_recreate(flexframesync q, const char *what)
     return true;
 }
 // a decoder option of the liquid API: the new value is tried on a new context and kept only if that context could be made
-static int sync_set_option(flexframesync q, int fxrx_sync_s::*field, int on, const char *what)
+static int sync_set_value(flexframesync q, int fxrx_sync_s::*field, int value, const char *what)
 {
     if (!q) return -1;
     const int old = q->*field;
-    q->*field = on ? 1 : 0;
+    q->*field = value;
     if (!sync_recreate(q, what)) { q->*field = old; return -1; }
     return 0;
 }
+static int sync_set_option(flexframesync q, int fxrx_sync_s::*field, int on, const char *what) { return sync_set_value(q, field, on ? 1 : 0, what); }
 void fxrx_sync_set_threshold(flexframesync q, float t) { if (!q) return; q->threshold = t; sync_recreate(q, "fxrx_sync_set_threshold"); }
 void fxrx_sync_set_equalizer(flexframesync q, int on) { if (!q) return; q->equalizer = on ? 1 : 0; sync_recreate(q, "fxrx_sync_set_equalizer"); }
 void fxrx_sync_set_soft(flexframesync q, int on) { if (!q) return; q->soft = on ? 1 : 0; sync_recreate(q, "fxrx_sync_set_soft"); }
@@ -260,6 +262,27 @@ int fxrx_sync_set_soft_rs(flexframesync q, int on)
         return -1;
     }
     return sync_set_option(q, &fxrx_sync_s::soft_rs, on, "fxrx_sync_set_soft_rs");
+}
+// (in force while soft payload decoding and soft_rs are on; a value other than "no bound" without them, or one fxrx_create would not take, is refused)
+int fxrx_sync_set_soft_rs_fmax(flexframesync q, int fmax_plus_1)
+{
+    if (q && fmax_plus_1 && !(q->soft && q->soft_rs)) {
+        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs_fmax: needs soft payload decoding and soft_rs (setting unchanged)\n");
+        return -1;
+    }
+    if (q && fmax_plus_1 && (fmax_plus_1 < 0 || fmax_plus_1 > 33 || (fmax_plus_1 & 1) == 0)) {
+        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs_fmax: 0, or an even bound 0 .. 32 plus one (setting unchanged)\n");
+        return -1;
+    }
+    return sync_set_value(q, &fxrx_sync_s::soft_rs_fmax, fmax_plus_1, "fxrx_sync_set_soft_rs_fmax");
+}
+int fxrx_sync_set_soft_rs_chain(flexframesync q, int on)
+{
+    if (q && on && !(q->soft && q->soft_rs)) {
+        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs_chain: needs soft payload decoding and soft_rs (setting unchanged)\n");
+        return -1;
+    }
+    return sync_set_option(q, &fxrx_sync_s::soft_rs_chain, on, "fxrx_sync_set_soft_rs_chain");
 }
 // [RECALLED liquid 1.3.x] flexframesync_decode_header_soft / flexframesync_decode_payload_soft (include/liquid/liquid.h)
 int flexframesync_decode_header_soft(flexframesync q, int soft) { return sync_set_option(q, &fxrx_sync_s::soft_header, soft, "flexframesync_decode_header_soft"); }

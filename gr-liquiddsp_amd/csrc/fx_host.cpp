@@ -326,6 +326,7 @@ std::unique_ptr<FxTables> make_tables()
 int upload_tables(fxrx_ctx_s *c)
 {
     std::unique_ptr<FxTables> t = make_tables();
+    t->rs_fmax = c->cfg.soft_rs_fmax ? (uint32_t)c->cfg.soft_rs_fmax - 1u : 32u;      // (fxrx_create has checked the value)
     HIP_OK(hipMalloc((void **)&c->d_tables, sizeof(FxTables)));
     HIP_OK(hipMemcpy(c->d_tables, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
     return 0;
@@ -467,6 +468,11 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (cfg->soft_rs && (cfg->mode == FXRX_MODE_DETECTOR || !cfg->soft_decision)) {
         set_err("fxrx_create: soft_rs needs soft_decision and flex_rx mode (FXRX_ERR_ARG)"); return nullptr;
     }
+    if (cfg->soft_rs_fmax && (cfg->soft_rs_fmax < 0 || cfg->soft_rs_fmax > 33 || (cfg->soft_rs_fmax & 1) == 0)) {
+        set_err("fxrx_create: soft_rs_fmax is 0 or an even bound 0 .. 32 plus one (FXRX_ERR_ARG)"); return nullptr;
+    }
+    if (cfg->soft_rs_fmax && !cfg->soft_rs) { set_err("fxrx_create: soft_rs_fmax needs soft_rs (FXRX_ERR_ARG)"); return nullptr; }
+    if (cfg->soft_rs_chain && !cfg->soft_rs) { set_err("fxrx_create: soft_rs_chain needs soft_rs (FXRX_ERR_ARG)"); return nullptr; }
     int nd = 0;
     if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0 || cfg->device >= nd) {
         set_err("fxrx_create: no usable HIP device (this library has no CPU path)"); return nullptr;
@@ -597,7 +603,7 @@ static inline hipError_t launch_chainfast(const fxrx_ctx_s *c, const Slot &sl, h
 static inline int soft_level(const fxrx_config &cfg) { return cfg.soft_decision ? (cfg.soft_block ? (cfg.soft_chain ? 3 : 2) : 1) : 0; }
 static inline hipError_t launch_paydec(const fxrx_ctx_s *c, const Slot &sl, hipStream_t st, DecList which, unsigned first_wave, unsigned n_waves, unsigned waves_per_wg)
 {
-    return fx_launch_paydec(which == kDecRs ? 1 : 0, which == kDecFallback ? 0 : soft_level(c->cfg), c->cfg.soft_rs ? 1 : 0, first_wave, n_waves, waves_per_wg, st, sl.d_pjobs.p, sl.dec_list(which), sl.hdr_pay(), sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
+    return fx_launch_paydec(which == kDecRs ? 1 : 0, which == kDecFallback ? 0 : soft_level(c->cfg), c->cfg.soft_rs ? 1 : 0, c->cfg.soft_rs_chain ? 1 : 0, first_wave, n_waves, waves_per_wg, st, sl.d_pjobs.p, sl.dec_list(which), sl.hdr_pay(), sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p,
                             sl.d_soft.p, sl.d_dw.p, sl.h_out.p, sl.h_recs.p, sl.pres(), c->d_tables, which == kDecFallback ? sl.h_hdr.p : nullptr);
 }
 // decode, one wave per frame: the lean instance, then the Reed-Solomon instance (which strides)
@@ -1469,6 +1475,15 @@ int fxrx_debug_rs_soft(unsigned int n, unsigned int count, const uint8_t *in_sof
     unsigned nb, dl; fx::rs_dims(n, nb, dl);
     return debug_decode("fxrx_debug_rs_soft", in_soft, (size_t)count * fx::fec_enc_len(FX_FEC_RS_M8, n) * 8, 0, out, (size_t)count * n, chosen_f, (size_t)count * nb,
                         [&](const uint8_t *d_in, uint8_t *d_out, uint8_t *d_f, const FxTables *d_t) { return fx_launch_rssoft(n, count, nullptr, d_in, d_out, d_f, d_t); });
+}
+
+int fxrx_debug_rs_chain(unsigned int n, unsigned int count, int fmax, int chain, const uint8_t *in_soft, uint8_t *out, uint8_t *chosen_f)
+{
+    if (!in_soft || !out || !chosen_f || n == 0 || n > kDebugMaxN || fmax < 0 || fmax > 32 || (fmax & 1)) { set_err("fxrx_debug_rs_chain: bad argument"); return FXRX_ERR_ARG; }
+    if (count == 0) return 0;
+    unsigned nb, dl; fx::rs_dims(n, nb, dl);
+    return debug_decode("fxrx_debug_rs_chain", in_soft, (size_t)count * fx::fec_enc_len(FX_FEC_RS_M8, n) * 8, 0, out, (size_t)count * n * (chain ? 8 : 1), chosen_f, (size_t)count * nb,
+                        [&](const uint8_t *d_in, uint8_t *d_out, uint8_t *d_f, const FxTables *d_t) { return fx_launch_rschain(n, count, (unsigned)fmax, chain ? 1 : 0, nullptr, d_in, d_out, d_f, d_t); });
 }
 
 static int collect_block(fxrx_ctx_s *c)

@@ -3138,9 +3138,22 @@ __device__ __forceinline__ void rsg_load_tables(RsgLds *R, const FxTables *T, in
     for (uint32_t i = lane; i < 256; i += DEC_THREADS) R->lg[i] = T->rslog[i];
 }
 
-// soft: 8 fec_enc_len(RS, n) soft values in codeword order (8-byte aligned, not written); dec: n bytes (another buffer);
-// chosen_f (tests, may be null): the winning f per block (255 would say "no candidate"; c_32 always exists, so it is never written)
-__device__ __noinline__ void rs_decode_soft_wave(uint32_t n, const uint8_t *soft, uint8_t *dec, uint8_t *chosen_f, const FxTables *T, RsgLds *R, int lane)
+// soft: 8 fec_enc_len(RS, n) soft values in codeword order (8-byte aligned); chosen_f (tests, may be null): the winning f per block,
+// 255 for "no candidate".  fmax (fxrx_config.soft_rs_fmax, even, 0 .. 32): only the trials f = 0, 2, ..., fmax run; at fmax = 32 c_32
+// always exists, below that a block may have no candidate and is then passed on as received.
+// Output, one of two forms:
+//   sout null: n hard bytes at dec (another buffer): the winner's data bytes, or h's where there is none;
+//   sout set (fxrx_config.soft_rs_chain; dec unused): 8 n soft values at sout, MSB first in byte order: a block with a winner emits
+//     0 / 255 for its data bits, a block without one its own soft values unchanged; parity and pad positions are not emitted.
+// sout may be `soft` itself (dec_frame works in place in the soft arena, as block_fec_decode_siso does).  Block blk reads its 8 N
+// values at soft + 8 blk N and writes 8 len <= 8 dl at sout + 8 blk dl.  With sout = soft the writes start no later than the block's
+// reads and end at 8 (blk + 1) dl < 8 (blk + 1) N, before the next block's reads begin, so a block never touches what a later block
+// reads.  But they overlap the block's own input (block 0's exactly).  Therefore every read of s -- the hard bytes and keys, and the
+// cost sums of the trials (rsg_trial) -- comes before the block's first write, with a wave barrier between; and the copy of a block
+// without a winner runs in rounds of 64 positions, every lane's load of a round before any lane's store of it (a barrier between):
+// a round's stores lie at or below its own loads and below every later round's.
+__device__ __noinline__ void rs_decode_soft_wave(uint32_t n, const uint8_t *soft, uint8_t *dec, uint8_t *sout, uint8_t *chosen_f, uint32_t fmax, const FxTables *T,
+                                                 RsgLds *R, int lane)
 {
     unsigned nb, dl; rs_dims(n, nb, dl);
     const uint32_t N = dl + 32;
@@ -3172,20 +3185,33 @@ __device__ __noinline__ void rs_decode_soft_wave(uint32_t n, const uint8_t *soft
         unsigned chosen = 0;
         if (dirty) {                                                            // (a codeword is its own f = 0 candidate at cost 0)
             RsgTrial tr; tr.cost = RSG_NO_COST; tr.np = 0;
-            if (lane < (int)RSG_TRIALS) rsg_trial(2u * (unsigned)lane, N, R->S, R->era, s, R->ex, R->lg, tr);
-            const uint32_t mykey = tr.cost == RSG_NO_COST ? RSG_NO_COST : (tr.cost << 8) | (uint32_t)lane;      // (cost < 2^16)
+            if (lane < (int)RSG_TRIALS && rsg_trial_runs(2u * (unsigned)lane, fmax)) rsg_trial(2u * (unsigned)lane, N, R->S, R->era, s, R->ex, R->lg, tr);
+            const uint32_t mykey = rsg_key(tr.cost, (unsigned)lane);
             uint32_t best = mykey;
 #pragma unroll
             for (int m = 1; m < 64; m <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, m, 64));
-            __builtin_amdgcn_wave_barrier();                                    // (every trial has read h's syndromes and era)
-            // (defensive only: c_32 always exists, so best is never RSG_NO_COST and chosen never 255; a trial changes at most 32 bytes)
+            __builtin_amdgcn_wave_barrier();                                    // (every trial has read h's syndromes and era, and s for its cost)
+            // (no candidate among the trials that ran: h stays as received; a trial changes at most 32 bytes)
             if (best != RSG_NO_COST && mykey == best)
                 for (uint32_t i = 0; i < tr.np && i < 32u; i++) R->h[tr.pos[i]] ^= tr.val[i];
-            chosen = best == RSG_NO_COST ? 255u : 2u * (best & 255u);
+            chosen = rsg_chosen(best);
             __threadfence_block(); __builtin_amdgcn_wave_barrier();
         }
         const uint32_t off = blk * dl, len = off < n ? min(n - off, dl) : 0u;
-        for (uint32_t j = lane; j < len; j += DEC_THREADS) dec[off + j] = R->h[j];
+        if (sout) {
+            // (wave-uniform rounds: all of a round's loads of s, then a barrier, then its stores)
+            unsigned long long *o = reinterpret_cast<unsigned long long *>(sout + 8 * (size_t)off);
+            for (uint32_t j0 = 0; j0 < len; j0 += DEC_THREADS) {
+                const uint32_t j = j0 + (uint32_t)lane;
+                unsigned long long w = 0;
+                if (j < len) w = rsg_soft_out(chosen != 255u, R->h[j], *reinterpret_cast<const unsigned long long *>(s + 8 * (size_t)j));
+                __threadfence_block(); __builtin_amdgcn_wave_barrier();
+                if (j < len) o[j] = w;
+                __threadfence_block(); __builtin_amdgcn_wave_barrier();
+            }
+        } else {
+            for (uint32_t j = lane; j < len; j += DEC_THREADS) dec[off + j] = R->h[j];
+        }
         if (chosen_f && lane == 0) chosen_f[blk] = (uint8_t)chosen;
     }
 }
@@ -3999,14 +4025,15 @@ __device__ __forceinline__ void stage_hard(unsigned fs, uint32_t n, uint8_t *enc
 }
 // The same stage from soft values: 8 n_enc of them at S (de-interleaved) -> n hard bytes at dec.  A code without a soft-input decoder
 // in this instance takes hard decisions (value > 127) into hb, the stage's hard input buffer (Viterbi's scratch otherwise).
+// (rs_fmax: fxrx_config.soft_rs_fmax's bound, read by SR instances only)
 template <bool WITH_RS, bool SB, bool SR>
 __device__ __forceinline__ void stage_soft(unsigned fs, uint32_t n, uint32_t n_enc, const uint8_t *S, uint8_t *dec, uint8_t *hb, unsigned long long *dw, uint32_t *stamp_fwd,
-                                           const FxTables *T, RsgLds *R, int lane)
+                                           const FxTables *T, RsgLds *R, uint32_t rs_fmax, int lane)
 {
     const int pc = conv_p(fs);
     if (pc) viterbi27<2>(pc, n, S, dec, dw, hb, lane, stamp_fwd);
     else if (SB && sb_code(fs)) block_fec_decode_soft(fs, n, S, dec, T, lane);
-    else if (SR && fs == FX_FEC_RS_M8) rs_decode_soft_wave(n, S, dec, nullptr, T, R, lane);
+    else if (SR && fs == FX_FEC_RS_M8) rs_decode_soft_wave(n, S, dec, nullptr, nullptr, rs_fmax, T, R, lane);
     else {
         soft_to_hard_wave(S, hb, n_enc, lane);
         __threadfence_block(); __builtin_amdgcn_wave_barrier();
@@ -4023,11 +4050,13 @@ __device__ __forceinline__ void stage_soft(unsigned fs, uint32_t n, uint32_t n_e
 // SC (fxrx_config.soft_chain, with SB): a soft-block fec1 in front of a convolutional fec0 hands it soft values (block_fec_decode_siso,
 // in place in the soft arena), and fec0 decodes them as it does behind FEC_NONE: soft de-interleaver, soft-input Viterbi
 // SR (fxrx_config.soft_rs, with WITH_RS and SOFT): a Reed-Solomon code in a stage that decodes from soft values uses rs_decode_soft_wave
-// (R: its LDS); its output is hard bytes
-template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false, bool SR = false>
+// (R: its LDS) with the trials f <= rs_fmax (fxrx_config.soft_rs_fmax); its output is hard bytes
+// SRC (fxrx_config.soft_rs_chain, with SR): a Reed-Solomon fec1 in front of a convolutional fec0 hands it soft values (rs_decode_soft_wave's
+// soft form, in place in the soft arena), and fec0 decodes them as it does behind FEC_NONE or under SC
+template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false, bool SR = false, bool SRC = false>
 __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob *jobs, const uint32_t *job_idx, const uint8_t *hard, uint8_t *bufA,
                                           uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res,
-                                          const FxTables *T, uint8_t *X, RsgLds *R = nullptr)
+                                          const FxTables *T, uint8_t *X, RsgLds *R = nullptr, uint32_t rs_fmax = 32u)
 {
     const uint32_t jf = job_idx[ji];
     FxPayJob job = jobs[jf];
@@ -4048,14 +4077,16 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
         deinterleave_soft_wave(S, job.l1, lane);
         FX_STAMP(1);
         const bool siso = SC && conv_p(job.fec0) && sb_code(job.fec1);
-        still_soft = siso || job.fec1 == FX_FEC_NONE;
+        const bool rs_siso = SRC && conv_p(job.fec0) && job.fec1 == FX_FEC_RS_M8;
+        still_soft = siso || rs_siso || job.fec1 == FX_FEC_NONE;
         if (siso) { block_fec_decode_siso(job.fec1, job.l0, S, S, T, lane); __threadfence_block(); __builtin_amdgcn_wave_barrier(); }
-        else if (!still_soft) stage_soft<WITH_RS, SB, SR>(job.fec1, job.l0, job.l1, S, B, A, dw, nullptr, T, R, lane);
+        else if (rs_siso) { rs_decode_soft_wave(job.l0, S, nullptr, S, nullptr, rs_fmax, T, R, lane); __threadfence_block(); __builtin_amdgcn_wave_barrier(); }
+        else if (!still_soft) stage_soft<WITH_RS, SB, SR>(job.fec1, job.l0, job.l1, S, B, A, dw, nullptr, T, R, rs_fmax, lane);
         FX_STAMP(2);
         if (still_soft) {
             deinterleave_soft_wave(S, job.l0, lane);
             FX_STAMP(3);
-            stage_soft<WITH_RS, SB, SR>(job.fec0, job.k, job.l0, S, A, B, dw, stamp_fwd, T, R, lane);
+            stage_soft<WITH_RS, SB, SR>(job.fec0, job.k, job.l0, S, A, B, dw, stamp_fwd, T, R, rs_fmax, lane);
         }
     } else {
         // hard symbols -> packet bytes; outer code (fec1): de-interleave l1 bytes in place, decode -> l0 bytes
@@ -4080,13 +4111,16 @@ __device__ __forceinline__ void dec_frame(uint32_t ji, int lane, const FxPayJob 
 
 // SB: the soft-block variant (fxrx_config.soft_block), soft-input block decoders; SC: the soft-chain variant (fxrx_config.soft_chain),
 // SB with soft-output block decoders in front of a convolutional fec0.  Template arguments of dec_frame: the default instances
-// carry none of their code.  SR: the soft Reed-Solomon variant (fxrx_config.soft_rs) of the Reed-Solomon instance, likewise.
-template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false, bool SR = false>
+// carry none of their code.  SR: the soft Reed-Solomon variant (fxrx_config.soft_rs) of the Reed-Solomon instance, likewise; SRC: SR with
+// the soft hand-over to a convolutional fec0 (fxrx_config.soft_rs_chain).  The bound on f (fxrx_config.soft_rs_fmax) is a field of the
+// context's tables, FxTables.rs_fmax, which the SR instances alone read: no argument is added, so every other instance is the code it was.
+template <bool WITH_RS, bool SOFT, bool SB = false, bool SC = false, bool SR = false, bool SRC = false>
 __global__ __launch_bounds__(WITH_RS ? DEC_THREADS : DEC_THREADS * DEC_MAX_WAVES)
 void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlockHdr *hdr, uint32_t first_wave, const uint8_t *hard, uint8_t *bufA,
                       uint8_t *bufB, uint8_t *soft_arena, unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T,
                       FxBlockHdr *fallback_host)
 {
+    static_assert(!SRC || SR, "the soft hand-over of Reed-Solomon blocks is a variant of soft Reed-Solomon decoding");
     static_assert(!SB || SOFT, "soft-input block decoders need soft decisions");
     static_assert(!SC || SB, "soft-output block decoders are a variant of the soft-input ones");
     static_assert(!SR || (WITH_RS && SOFT), "soft Reed-Solomon decoding is a variant of the Reed-Solomon instance with soft decisions");
@@ -4105,7 +4139,8 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
     if constexpr (SR) {
         __shared__ RsgLds Rs;                                                    // (one wave per workgroup)
         rsg_load_tables(&Rs, T, lane);
-        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, SOFT, SB, SC, true>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X, &Rs);
+        const uint32_t rs_fmax = min(T->rs_fmax, 32u);
+        for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, SOFT, SB, SC, true, SRC>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X, &Rs, rs_fmax);
     } else if constexpr (WITH_RS) {
         for (uint32_t ji = ji0; ji < njobs; ji += gridDim.x * wpg) dec_frame<true, SOFT, SB, SC>(ji, lane, jobs, job_idx, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, X);
     } else {
@@ -4115,24 +4150,25 @@ void fx_paydec_kernel(const FxPayJob *jobs, const uint32_t *job_idx, const FxBlo
 
 // The instance of a set of options, the rule written once.  soft: 0 hard decisions, 1 soft decisions, 2 soft decisions with soft-input
 // block decoders (SB), 3 those with soft-output block decoders in front of a convolutional fec0 (SB and SC); sr (with_rs, soft and
-// fxrx_config.soft_rs): the Reed-Solomon instance decodes Reed-Solomon stages from soft values (SR).  Eleven instances: 2 x 4, and 3 with SR.
+// fxrx_config.soft_rs): the Reed-Solomon instance decodes Reed-Solomon stages from soft values (SR); src (sr and fxrx_config.soft_rs_chain):
+// and hands soft values on to a convolutional fec0 (SRC).  Fourteen instances: 2 x 4, 3 with SR, 3 with SR and SRC.
 using PaydecKernel = decltype(&fx_paydec_kernel<false, false>);
 template <int SOFT>
-static PaydecKernel paydec_instance(bool with_rs, bool sr)
+static PaydecKernel paydec_instance(bool with_rs, bool sr, bool src)
 {
     constexpr bool SF = SOFT >= 1, SB = SOFT >= 2, SC = SOFT == 3;
-    if constexpr (SF) if (sr) return fx_paydec_kernel<true, SF, SB, SC, true>;
+    if constexpr (SF) if (sr) return src ? fx_paydec_kernel<true, SF, SB, SC, true, true> : fx_paydec_kernel<true, SF, SB, SC, true>;
     return with_rs ? fx_paydec_kernel<true, SF, SB, SC> : fx_paydec_kernel<false, SF, SB, SC>;
 }
-extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, int soft_rs, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
+extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, int soft_rs, int rs_chain, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host)
 {
     if (grid_waves == 0) return hipSuccess;
     const unsigned w = with_rs ? 1u : (waves_per_wg < 1u ? 1u : (waves_per_wg > DEC_MAX_WAVES ? DEC_MAX_WAVES : waves_per_wg));
     const dim3 grid((grid_waves + w - 1) / w), block(DEC_THREADS * w);
-    const bool rs = with_rs != 0, sr = rs && soft && soft_rs;
-    const PaydecKernel kernel = soft == 3 ? paydec_instance<3>(rs, sr) : (soft == 2 ? paydec_instance<2>(rs, sr) : (soft ? paydec_instance<1>(rs, sr) : paydec_instance<0>(rs, sr)));
+    const bool rs = with_rs != 0, sr = rs && soft && soft_rs, src = sr && rs_chain;
+    const PaydecKernel kernel = soft == 3 ? paydec_instance<3>(rs, sr, src) : (soft == 2 ? paydec_instance<2>(rs, sr, src) : (soft ? paydec_instance<1>(rs, sr, src) : paydec_instance<0>(rs, sr, src)));
     hipLaunchKernelGGL(kernel, grid, block, 0, st, jobs, job_idx, hdr, first_wave, hard, bufA, bufB, soft_arena, dw_arena, out, recs, res, T, fallback_host);
     return hipGetLastError();
 }
@@ -4185,13 +4221,35 @@ void fx_rssoft_kernel(uint32_t n, uint32_t count, const uint8_t *in, uint8_t *ou
     if (p >= count) return;
     unsigned nb, dl; rs_dims(n, nb, dl);
     rsg_load_tables(&Rs, T, threadIdx.x);
-    rs_decode_soft_wave(n, in + 8 * (size_t)fec_enc_len(FX_FEC_RS_M8, n) * p, out + (size_t)n * p, chosen_f + (size_t)nb * p, T, &Rs, threadIdx.x);
+    rs_decode_soft_wave(n, in + 8 * (size_t)fec_enc_len(FX_FEC_RS_M8, n) * p, out + (size_t)n * p, nullptr, chosen_f + (size_t)nb * p, 32u, T, &Rs, threadIdx.x);
 }
 
 extern "C" hipError_t fx_launch_rssoft(unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, uint8_t *chosen_f, const FxTables *T)
 {
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(fx_rssoft_kernel, dim3(count), dim3(DEC_THREADS), 0, st, n, count, in, out, chosen_f, T);
+    return hipGetLastError();
+}
+
+// tests (fxrx_debug_rs_chain): the same decoder under a bound on f (fmax, even, 0 .. 32) and in either output form: chain = 0, n bytes
+// per packet; chain = 1, 8 n soft values per packet (into `out`, not in place); one chosen f per Reed-Solomon block, 255 for a block given up on
+__global__ __launch_bounds__(DEC_THREADS)
+void fx_rschain_kernel(uint32_t n, uint32_t count, uint32_t fmax, uint32_t chain, const uint8_t *in, uint8_t *out, uint8_t *chosen_f, const FxTables *T)
+{
+    __shared__ RsgLds Rs;
+    const uint32_t p = blockIdx.x;
+    if (p >= count) return;
+    unsigned nb, dl; rs_dims(n, nb, dl);
+    rsg_load_tables(&Rs, T, threadIdx.x);
+    const uint8_t *s = in + 8 * (size_t)fec_enc_len(FX_FEC_RS_M8, n) * p;
+    if (chain) rs_decode_soft_wave(n, s, nullptr, out + 8 * (size_t)n * p, chosen_f + (size_t)nb * p, fmax, T, &Rs, threadIdx.x);
+    else rs_decode_soft_wave(n, s, out + (size_t)n * p, nullptr, chosen_f + (size_t)nb * p, fmax, T, &Rs, threadIdx.x);
+}
+
+extern "C" hipError_t fx_launch_rschain(unsigned n, unsigned count, unsigned fmax, int chain, hipStream_t st, const uint8_t *in, uint8_t *out, uint8_t *chosen_f, const FxTables *T)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(fx_rschain_kernel, dim3(count), dim3(DEC_THREADS), 0, st, n, count, fmax > 32u ? 32u : fmax, chain ? 1u : 0u, in, out, chosen_f, T);
     return hipGetLastError();
 }
 

@@ -22,6 +22,7 @@ extern "C" hipError_t fx_launch_hdrdec(int soft, unsigned n, hipStream_t st, con
 extern "C" hipError_t fx_launch_blkdec(int soft, unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T);
 extern "C" hipError_t fx_launch_blksiso(unsigned fs, unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, const FxTables *T);
 extern "C" hipError_t fx_launch_rssoft(unsigned n, unsigned count, hipStream_t st, const uint8_t *in, uint8_t *out, uint8_t *chosen_f, const FxTables *T);
+extern "C" hipError_t fx_launch_rschain(unsigned n, unsigned count, unsigned fmax, int chain, hipStream_t st, const uint8_t *in, uint8_t *out, uint8_t *chosen_f, const FxTables *T);
 extern "C" hipError_t fx_launch_chainfast(unsigned nstreams, hipStream_t st, const FxStreamDesc *streams, const FxWalkJob *jobs, const FxWalkResult *results,
                                           const FxFrame *frames, FxFrame *chain, uint32_t *chain_count, FxBlockHdr *hdr, uint32_t force_repair,
                                           FxWalkJob *jobs_rw, uint32_t *req_list, uint32_t *stat, uint32_t pass);
@@ -39,7 +40,8 @@ extern "C" hipError_t fx_launch_vbfinish(unsigned first_wave, unsigned n_waves, 
 extern "C" hipError_t fx_launch_paymf(unsigned grid, int eq, hipStream_t st, const FxPayJob *jobs, const uint32_t *blk_job, const uint32_t *blk_c0, const FxBlockHdr *hdr,
                                       const FxFrame *chain, float2 *sym_raw, const FxTables *T);
 extern "C" hipError_t fx_launch_paypll(const FxPllGang *gang, const unsigned *grid_waves, unsigned waves_per_wg, hipStream_t st, const FxTables *T);
-extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, int soft_rs, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
+// (rs_chain: the soft hand-over of soft Reed-Solomon decoding, fxrx_config.soft_rs_chain; its bound on f, soft_rs_fmax, travels in T->rs_fmax)
+extern "C" hipError_t fx_launch_paydec(int with_rs, int soft, int soft_rs, int rs_chain, unsigned first_wave, unsigned grid_waves, unsigned waves_per_wg, hipStream_t st, const FxPayJob *jobs,
                                        const uint32_t *job_idx, const FxBlockHdr *hdr, const uint8_t *hard, uint8_t *bufA, uint8_t *bufB, uint8_t *soft_arena,
                                        unsigned long long *dw_arena, uint8_t *out, FxOutRec *recs, FxPayResult *res, const FxTables *T, FxBlockHdr *fallback_host);
 extern "C" hipError_t fx_launch_symcopy(unsigned grid, hipStream_t st, const FxBlockHdr *hdr, const float2 *sym, float2 *host);

@@ -98,6 +98,25 @@ FX_RSG_HD inline void rsg_trial(unsigned f, unsigned N, const uint8_t *S, const 
     out.cost = cost; out.np = np;
 }
 
+// The winner, give-up and output rule around the trials (fxrx_config.soft_rs_fmax, soft_rs_chain), written once for the kernel and
+// the host-side test driver (tests/cpp/rschain_check.cpp):
+//   trial f runs iff f <= fmax (fmax even, 0 .. 32; 32: every trial, the unbounded rule);
+//   trial t = f / 2 with cost D enters the minimum as (D << 8) | t (D < 2^16), so the least D wins, ties to the smallest f; a trial
+//   without a candidate, or one that did not run, as RSG_NO_COST; a minimum of RSG_NO_COST: no candidate, the block is given up on --
+//   passed on as received, chosen f 255.
+FX_RSG_HD inline bool rsg_trial_runs(unsigned f, unsigned fmax) { return f <= fmax; }
+FX_RSG_HD inline uint32_t rsg_key(uint32_t cost, unsigned t) { return cost == RSG_NO_COST ? RSG_NO_COST : (cost << 8) | t; }
+FX_RSG_HD inline unsigned rsg_chosen(uint32_t best) { return best == RSG_NO_COST ? 255u : 2u * (best & 255u); }
+// soft hand-over of one data byte, its eight values as they lie in memory (value b, the byte's bit 7 - b, in bits 8 b .. 8 b + 7 of
+// the word): a block with a winner emits 0 / 255 for the winner's byte c, a block given up on its own soft values w unchanged
+FX_RSG_HD inline unsigned long long rsg_soft_out(bool accepted, uint8_t c, unsigned long long w)
+{
+    if (!accepted) return w;
+    unsigned long long o = 0;
+    for (unsigned b = 0; b < 8; b++) if (c & (0x80u >> b)) o |= 0xFFull << (8 * b);
+    return o;
+}
+
 // hard byte and reliability rho = min over the bits of |2 s - 255| from a byte's eight soft values (MSB first)
 FX_RSG_HD inline void rsg_byte(const uint8_t *s, uint8_t &h, uint8_t &rho)
 {

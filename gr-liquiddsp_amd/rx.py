@@ -80,10 +80,12 @@ class RxContext:
     """fxrx_ctx wrapper.  Raises RxError when the library or a HIP device is missing (no fallback)."""
 
     def __init__(self, n_streams=1, mode=MODE_FLEX_RX, device=0, threshold=0.0, segment_len=0, want_framesyms=False, equalizer=False, soft_decision=False,
-                 soft_header=False, soft_block=False, soft_chain=False, soft_rs=False):
+                 soft_header=False, soft_block=False, soft_chain=False, soft_rs=False, soft_rs_fmax=None, soft_rs_chain=False):
+        """soft_rs_fmax: None for no bound, else the even bound 0 .. 32 itself (fxrx_config.soft_rs_fmax holds it plus one)"""
         self.L = _ffi.lib()
-        cfg = _ffi.ConfigRs(device, mode, n_streams, threshold, segment_len, 1 if want_framesyms else 0, 1 if equalizer else 0, 1 if soft_decision else 0,
-                          1 if soft_header else 0, 1 if soft_block else 0, 1 if soft_chain else 0, 1 if soft_rs else 0)
+        cfg = _ffi.ConfigRsChain(device, mode, n_streams, threshold, segment_len, 1 if want_framesyms else 0, 1 if equalizer else 0, 1 if soft_decision else 0,
+                                 1 if soft_header else 0, 1 if soft_block else 0, 1 if soft_chain else 0, 1 if soft_rs else 0,
+                                 0 if soft_rs_fmax is None else int(soft_rs_fmax) + 1, 1 if soft_rs_chain else 0)
         self.h = self.L.fxrx_create(C.byref(cfg))
         if not self.h:
             raise RxError("fxrx_create failed: %s" % self.L.fxrx_last_error().decode())

@@ -97,6 +97,12 @@ int  fxrx_sync_set_soft_chain(flexframesync q, int on);
 /* soft-decision Reed-Solomon decoding (fxrx_config.soft_rs), in force while soft payload decoding is on.  Re-creates the context; returns
  * 0, or -1 if that failed or if, with on != 0, soft payload decoding is off, in which case the previous setting stays */
 int  fxrx_sync_set_soft_rs(flexframesync q, int on);
+/* the bound on f of soft-decision Reed-Solomon decoding (fxrx_config.soft_rs_fmax, the same value: 0 for no bound, else the even bound
+ * 0 .. 32 plus one) and its soft hand-over to a convolutional fec0 (fxrx_config.soft_rs_chain), in force while soft payload decoding and
+ * soft_rs are on.  Each re-creates the context; returns 0, or -1 if that failed, if the value is none fxrx_create takes or if, with a
+ * value other than 0, soft payload decoding or soft_rs is off, in which case the previous setting stays */
+int  fxrx_sync_set_soft_rs_fmax(flexframesync q, int fmax_plus_1);
+int  fxrx_sync_set_soft_rs_chain(flexframesync q, int on);
 unsigned int fxrx_sync_pending(flexframesync q);     /* completed frames not yet delivered */
 /* the liquid signatures return void: when a block fails on the GPU its samples (and those of the blocks in flight with it) are
  * dropped -- never fed twice --, the synchroniser restarts freshly reset behind the gap, the text stays in fxrx_last_error(),
@@ -229,6 +235,27 @@ typedef struct {
                                     frames without a Reed-Solomon stage decode as with soft_rs = 0.  Needs soft_decision = 1 and flex_rx
                                     mode (fxrx_create fails with FXRX_ERR_ARG otherwise).  0 (default): the bounded-distance decoder on the
                                     hard decisions, radius 16 bytes */
+    int          soft_rs_fmax;   /* a bound on f for soft_rs.  Encoding: 0 (default): no bound, fmax = 32, soft_rs's rule as above; otherwise
+                                    fmax + 1 for an even fmax 0 .. 32 (1: f = 0 only; 17: fmax = 16; 33: the same as 0).  The rule is
+                                    soft_rs's with the trials f = 0, 2, ..., fmax only: the winner is the least D among their candidates,
+                                    ties to the smallest f.  With fmax < 32 a block may have no candidate; it is then passed on as
+                                    received (the hard bytes h).  fmax = 0 is the bounded-distance hard decoder, radius 16.  Choosing
+                                    fmax: trial f accepts any word within e = (32 - f) / 2 errors outside f erasures, so a word far from
+                                    every codeword is accepted by it with probability about q(N, f) = C(N - f, e) 255^e / 256^(2 e), the
+                                    share of the punctured code's space that its radius-e balls cover (N = 99: q(32) = 1, q(30) = 0.26,
+                                    q(24) = 2.7e-4, q(16) = 2e-9; table in DESIGN.md section 8): pick fmax from the miscorrection rate
+                                    you accept.  Needs soft_rs = 1; any other value: fxrx_create fails with FXRX_ERR_ARG */
+    int          soft_rs_chain;  /* 1: when fec1 is RS(255,223) and fec0 is convolutional, the Reed-Solomon stage emits one soft value per
+                                    data bit instead of hard bytes.  Per block, with len the data bytes the block really carries (the
+                                    padded last block: fewer than dl), 8 len values, MSB first, in byte order: a block with a winning
+                                    candidate c (a codeword as received is its own f = 0 candidate) emits o = c_bit ? 255 : 0 for its data
+                                    bits; a block with no candidate (soft_rs_fmax) emits o = s, the channel's soft values of its data
+                                    positions, unchanged; parity and pad positions are not emitted.  The 8 l0 values pass the soft
+                                    de-interleaver and fec0 decodes with the soft-input Viterbi, as behind FEC_NONE or under soft_chain.
+                                    With every block accepted the result is that of the hard hand-over.  Every other pair (Reed-Solomon
+                                    as fec0 behind fec1 none, Reed-Solomon with fec0 none or a block code, no Reed-Solomon) decodes as
+                                    with soft_rs_chain = 0.  The rule is this project's.  Needs soft_rs = 1 (fxrx_create fails with
+                                    FXRX_ERR_ARG otherwise).  0 (default): hard bytes are handed on */
 } fxrx_config;
 
 typedef struct {
@@ -360,6 +387,10 @@ int fxrx_debug_block_siso(unsigned int fec, unsigned int n, unsigned int count, 
  * candidate always exists).  Synchronous, on the current HIP device; returns 0 or
  * FXRX_ERR_* */
 int fxrx_debug_rs_soft(unsigned int n, unsigned int count, const uint8_t *in_soft, uint8_t *out, uint8_t *chosen_f);
+/* tests: the same decoder under a bound on f (fmax itself: even, 0 .. 32; fxrx_config.soft_rs_fmax) and in either output form
+ * (fxrx_config.soft_rs_chain).  chain = 0: out gets n bytes per packet, the hard output under the bound; chain = 1: out gets 8 n soft
+ * values per packet.  in_soft and chosen_f as for fxrx_debug_rs_soft; a block given up on has chosen_f 255.  The same cap on n. */
+int fxrx_debug_rs_chain(unsigned int n, unsigned int count, int fmax, int chain, const uint8_t *in_soft, uint8_t *out, uint8_t *chosen_f);
 /* diagnostic builds (-DFX_STAMPS) only: shader-clock deltas of the decode phases of payload job i */
 int fxrx_debug_stamps(const fxrx_ctx *c, unsigned int i, uint32_t out[8]);
 int fxrx_debug_chain_stamps(const fxrx_ctx *c, uint32_t out[8]);  /* chain kernel phase clocks (stream 0) of the last collected block */
