@@ -14,6 +14,7 @@
 #include <map>
 #include <tuple>
 #include "fx_common.h"
+#include "fx_fecdims.h"
 
 namespace fx {
 
@@ -126,10 +127,6 @@ inline void fft512(const cf *in, cf *out, const cf *tw)
 }  // namespace hfft
 
 // ------------------------------------------------------------------ CRC / whitening / interleaver
-inline unsigned crc_len(unsigned check)
-{
-    switch (check) { case FX_CRC_CHECKSUM: case FX_CRC_8: return 1; case FX_CRC_16: return 2; case FX_CRC_24: return 3; case FX_CRC_32: return 4; default: return 0; }
-}
 inline uint32_t crc_key(unsigned check, const uint8_t *msg, unsigned n)
 {
     uint32_t prev, mask;
@@ -284,57 +281,14 @@ struct BlockCodes {
 };
 inline const BlockCodes &block_codes() { static BlockCodes bc; return bc; }
 
-inline int conv_period(unsigned fs)
-{
-    switch (fs) {
-    case FX_FEC_CONV_V27: return 1; case FX_FEC_CONV_V27P23: return 2; case FX_FEC_CONV_V27P34: return 3;
-    case FX_FEC_CONV_V27P45: return 4; case FX_FEC_CONV_V27P56: return 5; case FX_FEC_CONV_V27P67: return 6;
-    case FX_FEC_CONV_V27P78: return 7; default: return 0;
-    }
-}
-inline void conv_masks(int p, unsigned &pa, unsigned &pb)
-{
-    switch (p) {
-    case 2: pa = 0x3; pb = 0x1; break;   case 3: pa = 0x3; pb = 0x5; break;   case 4: pa = 0xf; pb = 0x1; break;
-    case 5: pa = 0xb; pb = 0x15; break;  case 6: pa = 0x17; pb = 0x29; break; case 7: pa = 0x2f; pb = 0x51; break;
-    default: pa = 1; pb = 1; break;
-    }
-}
-inline bool blk_spec(unsigned fs, unsigned &k, unsigned &n)
-{
-    switch (fs) {
-    case FX_FEC_HAMMING74: k = 4; n = 7; return true;
-    case FX_FEC_HAMMING128: k = 8; n = 12; return true;
-    case FX_FEC_GOLAY2412: k = 12; n = 24; return true;
-    default: return false;
-    }
-}
-inline bool fec_supported(unsigned fs)
-{
-    unsigned k, n;
-    return fs == FX_FEC_NONE || fs == FX_FEC_HAMMING84 || fs == FX_FEC_SECDED7264 || fs == FX_FEC_SECDED2216 ||
-           fs == FX_FEC_SECDED3932 || fs == FX_FEC_RS_M8 || blk_spec(fs, k, n) || conv_period(fs) != 0;
-}
-inline void rs_dims(unsigned n, unsigned &nb, unsigned &dl) { nb = (n + 222) / 223; if (nb == 0) nb = 1; dl = (n + nb - 1) / nb; }
-inline unsigned fec_enc_len(unsigned fs, unsigned n)
-{
-    int p = conv_period(fs);
-    if (p) { unsigned T = 8 * n + 6; unsigned bits = p == 1 ? 2 * T : T + (T + (unsigned)p - 1) / (unsigned)p; return (bits + 7) / 8; }
-    unsigned bk, bn;
-    if (blk_spec(fs, bk, bn)) { unsigned nb = (8 * n + bk - 1) / bk; return (nb * bn + 7) / 8; }
-    if (fs == FX_FEC_RS_M8) { unsigned nb, dl; rs_dims(n, nb, dl); return nb * (dl + 32); }
-    if (fs == FX_FEC_SECDED2216) return 3 * (n / 2) + ((n % 2) ? (n % 2) + 1 : 0);
-    if (fs == FX_FEC_SECDED3932) return 5 * (n / 4) + ((n % 4) ? (n % 4) + 1 : 0);
-    if (fs == FX_FEC_HAMMING84) return 2 * n;
-    if (fs == FX_FEC_SECDED7264) return 9 * (n / 8) + ((n % 8) ? (n % 8) + 1 : 0);
-    return n;
-}
+// lengths, supported schemes, puncturing: fx_fecdims.h, shared with the kernels
+using ::crc_len; using ::blk_spec; using ::fec_supported; using ::rs_dims; using ::fec_enc_len;
 inline void fec_encode(unsigned fs, unsigned n, const uint8_t *dec, uint8_t *enc)
 {
     const BlockCodes &bc = block_codes();
-    int p = conv_period(fs);
+    int p = conv_p(fs);
     if (p) {
-        unsigned pa, pb; conv_masks(p, pa, pb);
+        unsigned pa, pb; conv_punct(p, pa, pb);
         unsigned T = 8 * n + 6, sr = 0, nb = 0, el = fec_enc_len(fs, n);
         std::memset(enc, 0, el);
         for (unsigned t = 0; t < T; t++) {

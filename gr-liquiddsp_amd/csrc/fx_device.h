@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fx_common.h"
+#include "fx_fecdims.h"
 
 struct FxTables {
     float2   tw[512];        // exp(-j 2 pi m / 512)
@@ -408,61 +409,4 @@ FX_DEV float2 eq_sum16(const float2 *x, const float2 *w)
 // sample index (relative to the aligned start) at which MF output symbol c appears
 FX_DEV int64_t sym_sample(int64_t c, int mfc0) { return mfc0 == 0 ? 2 * c : (c == 0 ? 0 : 2 * c - 1); }
 
-// ---------------------------------------------------------------- coded lengths (device copy of the host rule)
-FX_DEV unsigned crc_len(unsigned check)
-{
-    switch (check) {
-    case FX_CRC_CHECKSUM: case FX_CRC_8: return 1;
-    case FX_CRC_16: return 2;
-    case FX_CRC_24: return 3;
-    case FX_CRC_32: return 4;
-    default: return 0;
-    }
-}
-FX_DEV int conv_p(unsigned fs)   // puncturing period; 0 = not a K=7 convolutional scheme
-{
-    switch (fs) {
-    case FX_FEC_CONV_V27: return 1;
-    case FX_FEC_CONV_V27P23: return 2;
-    case FX_FEC_CONV_V27P34: return 3;
-    case FX_FEC_CONV_V27P45: return 4;
-    case FX_FEC_CONV_V27P56: return 5;
-    case FX_FEC_CONV_V27P67: return 6;
-    case FX_FEC_CONV_V27P78: return 7;
-    default: return 0;
-    }
-}
-FX_DEV bool blk_spec(unsigned fs, unsigned &k, unsigned &n)    // bit-packed block codes
-{
-    switch (fs) {
-    case FX_FEC_HAMMING74: k = 4; n = 7; return true;
-    case FX_FEC_HAMMING128: k = 8; n = 12; return true;
-    case FX_FEC_GOLAY2412: k = 12; n = 24; return true;
-    default: k = n = 0; return false;
-    }
-}
-FX_DEV bool fec_supported(unsigned fs)
-{
-    unsigned k, n;
-    return fs == FX_FEC_NONE || fs == FX_FEC_HAMMING84 || fs == FX_FEC_SECDED7264 || fs == FX_FEC_SECDED2216 ||
-           fs == FX_FEC_SECDED3932 || fs == FX_FEC_RS_M8 || blk_spec(fs, k, n) || conv_p(fs) != 0;
-}
-// Reed-Solomon: n message bytes in nb blocks of at most 223, dl message bytes each (the last may hold fewer), 32 parity bytes behind each
-FX_DEV void rs_dims(unsigned n, unsigned &nb, unsigned &dl) { nb = (n + 222) / 223; if (nb == 0) nb = 1; dl = (n + nb - 1) / nb; }
-FX_DEV unsigned fec_enc_len(unsigned fs, unsigned n)
-{
-    int p = conv_p(fs);
-    if (p) {
-        unsigned T = 8 * n + 6;
-        unsigned bits = p == 1 ? 2 * T : T + (T + (unsigned)p - 1) / (unsigned)p;
-        return (bits + 7) / 8;
-    }
-    unsigned bk, bn;
-    if (blk_spec(fs, bk, bn)) { unsigned nb = (8 * n + bk - 1) / bk; return (nb * bn + 7) / 8; }
-    if (fs == FX_FEC_RS_M8) { unsigned nb, dl; rs_dims(n, nb, dl); return nb * (dl + 32); }
-    if (fs == FX_FEC_SECDED2216) return 3 * (n / 2) + ((n % 2) ? (n % 2) + 1 : 0);
-    if (fs == FX_FEC_SECDED3932) return 5 * (n / 4) + ((n % 4) ? (n % 4) + 1 : 0);
-    if (fs == FX_FEC_HAMMING84) return 2 * n;
-    if (fs == FX_FEC_SECDED7264) return 9 * (n / 8) + ((n % 8) ? (n % 8) + 1 : 0);
-    return n;
-}
+// coded lengths, supported schemes, puncturing: fx_fecdims.h (one text for kernels and host)

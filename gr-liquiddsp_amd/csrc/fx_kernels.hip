@@ -3713,17 +3713,12 @@ __device__ __forceinline__ void acs_step(uint32_t &P, unsigned cu, const unsigne
     P = m & ~1u;
 }
 
-// enc: VM 0 / 1: the coded bits, packed; VM 2: one soft byte per coded bit
+// ---- viterbi27, step by step.  Each step: what it needs visible to the wave -> what it leaves visible. ----
+// v27_tables: nothing -> per rotation phase, in the lane's registers: this lane's state, its MSB (hi), the bit-doubled expected
+// code bits of its own branch (A in bits 0-1, B in bits 2-3), role-adjusted for the swap phases -- see acs_step
 template <int VM>
-__device__ __forceinline__ void viterbi27(int p, uint32_t n, const uint8_t *enc, uint8_t *dec, unsigned long long *dw, uint8_t *scratch, int lane, uint32_t *stamp_fwd)
+__device__ __forceinline__ void v27_tables(int lane, unsigned (&ta)[6], unsigned (&tb)[6])
 {
-#ifdef FX_STAMPS
-    unsigned long long tv0_ = __builtin_readcyclecounter();
-#endif
-    const uint32_t Tn = 8 * n + 6;
-    // per rotation phase: this lane's state, its MSB (hi), the bit-doubled expected code bits of its own branch
-    // (A in bits 0-1, B in bits 2-3), role-adjusted for the swap phases -- see acs_step
-    unsigned ta[6], tb[6];
 #pragma unroll
     for (int ph = 0; ph < 6; ph++) {
         const unsigned st = (((unsigned)lane << ph) | ((unsigned)lane >> (6 - ph))) & 63u;   // state held at phase ph
@@ -3744,38 +3739,41 @@ __device__ __forceinline__ void viterbi27(int p, uint32_t n, const uint8_t *enc,
             ta[ph] = wa; tb[ph] = wb;
         }
     }
-    unsigned pa, pb;                                       // puncturing rows (A, B) as bit masks over the column
-    switch (p) {
-    case 2: pa = 0x3; pb = 0x1; break;                 // 11 / 10
-    case 3: pa = 0x3; pb = 0x5; break;                 // 110 / 101
-    case 4: pa = 0xf; pb = 0x1; break;                 // 1111 / 1000
-    case 5: pa = 0xb; pb = 0x15; break;                // 11010 / 10101
-    case 6: pa = 0x17; pb = 0x29; break;               // 111010 / 100101
-    case 7: pa = 0x2f; pb = 0x51; break;               // 1111010 / 1000101
-    default: pa = 0x1; pb = 0x1; break;
+}
+// v27_codeword: enc (the stage before wrote it; visible) -> the received code word of step t, in the form acs_step<.., VM> takes,
+// in the lane's register; 0 at and behind step Tn.  pa / pb: conv_punct(p)
+template <int VM>
+__device__ __forceinline__ unsigned v27_codeword(const uint8_t *enc, uint32_t t, uint32_t Tn, unsigned p, unsigned pa, unsigned pb)
+{
+    if (t >= Tn) return 0u;
+    const unsigned col = t % p;
+    const unsigned hasA = (pa >> col) & 1, hasB = (pb >> col) & 1;
+    uint32_t nb = conv_bits_before(t, p);
+    unsigned ra = 0, rb = 0;
+    if (VM == 2) {
+        if (hasA) { ra = enc[nb]; nb++; }
+        if (hasB) { rb = enc[nb]; }
+        return ra | (rb << 8) | (hasA * 0xff0000u) | (hasB * 0xff000000u);
     }
-    // received code word of step t: R4 | H4 << 4 | (2 * bits present) << 8
-    auto prep = [&](uint32_t t) -> unsigned {
-        if (t >= Tn) return 0u;
-        const unsigned col = t % (unsigned)p;
-        const unsigned hasA = (pa >> col) & 1, hasB = (pb >> col) & 1;
-        uint32_t nb = (p == 1) ? 2 * t : t + (t + (unsigned)p - 1) / (unsigned)p;       // coded bits before step t
-        unsigned ra = 0, rb = 0;
-        if (VM == 2) {
-            if (hasA) { ra = enc[nb]; nb++; }
-            if (hasB) { rb = enc[nb]; }
-            return ra | (rb << 8) | (hasA * 0xff0000u) | (hasB * 0xff000000u);
-        }
-        if (hasA) { ra = getbit(enc, nb); nb++; }
-        if (hasB) { rb = getbit(enc, nb); }
-        if (VM == 0) return 8u * (ra | (rb << 1));
-        return (ra * 3u) | (rb * 12u) | ((hasA * 3u | hasB * 12u) << 4) | ((2u * (hasA + hasB)) << 8);
-    };
+    if (hasA) { ra = getbit(enc, nb); nb++; }
+    if (hasB) { rb = getbit(enc, nb); }
+    if (VM == 0) return 8u * (ra | (rb << 1));
+    return (ra * 3u) | (rb * 12u) | ((hasA * 3u | hasB * 12u) << 4) | ((2u * (hasA + hasB)) << 8);
+}
+// v27_forward: enc -> dw, lane-major: word [chunk][lane] holds this lane's decisions of the chunk's 64 steps, newest step in bit 0
+// of each half.  The lanes' own stores only: the caller fences before any lane reads another's.
+// A chunk is 64 steps, lane l holding the code word of step t0 + l; the next chunk's loads fly while this chunk computes.
+template <int VM>
+__device__ __forceinline__ void v27_forward(int p, uint32_t Tn, const uint8_t *enc, unsigned long long *dw, int lane)
+{
+    unsigned ta[6], tb[6], pa, pb;
+    v27_tables<VM>(lane, ta, tb);
+    conv_punct(p, pa, pb);
     uint32_t P = (lane == 0) ? 0u : (1u << 25);            // state 0 sits in lane 0 at every phase
-    unsigned code_next = prep(lane);
+    unsigned code_next = v27_codeword<VM>(enc, (uint32_t)lane, Tn, (unsigned)p, pa, pb);
     for (uint32_t t0 = 0; t0 < Tn; t0 += 64) {
         const unsigned code = code_next;
-        code_next = prep(t0 + 64 + lane);                  // next chunk's loads fly while this chunk computes
+        code_next = v27_codeword<VM>(enc, t0 + 64 + lane, Tn, (unsigned)p, pa, pb);
         const uint32_t nstep = min(64u, Tn - t0);
         unsigned hist[2] = { 0u, 0u };
 #pragma unroll
@@ -3804,112 +3802,147 @@ __device__ __forceinline__ void viterbi27(int p, uint32_t n, const uint8_t *enc,
                 }
             }
         }
-        // lane-major history: word [chunk][lane] holds this lane's decisions, newest step in bit 0 of each half
         dw[t0 + lane] = ((unsigned long long)hist[1] << 32) | hist[0];
     }
+}
+
+// ---- traceback, parallel over 64-step chunks with exact verification: the wave-per-frame decoder's, and the batch path's
+// when a block's end-state guess was wrong (vb_retrace_block) ----
+// A serial traceback is one dependent step per trellis step.  Instead every lane traces whole chunks: chunk c is first entered
+// from a *guess* S_c of its end state, obtained by tracing chunk c+1 back from state 0 (survivor paths merge within a few
+// constraint lengths, so the guess is almost always right), and yields the state B_c at its start.  The chain is then
+// verified: the true end state of chunk c is B_{c+1} (end_state for the last chunk); any chunk whose guess differs is
+// re-traced from the true state, until nothing changes.  At that fixed point every chunk was entered from the state the
+// serial traceback would have had -- same bits, bit for bit.
+// steps 64c .. 64c+63 are output bytes 8c .. 8c+7, MSB first (the buffer has 8 bytes of slack)
+__device__ __forceinline__ void vb_emit(uint8_t *dec, uint32_t c, uint32_t b0, uint32_t b1)
+{
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        lo |= (__brev((b0 >> (8 * k)) & 0xffu) >> 24) << (8 * k);
+        hi |= (__brev((b1 >> (8 * k)) & 0xffu) >> 24) << (8 * k);
+    }
+    *reinterpret_cast<uint2 *>(dec + 8 * (size_t)c) = make_uint2(lo, hi);
+}
+// The driver.  A lane interleaves NCH chains (chunks base + 64 j + lane), to overlap their loads.  trace(cidx, act, st, bits)
+// is the layout's chunk tracer: for every chain j with act[j], chunk cidx[j] entered in state st[j] -> st[j] the state at the
+// chunk's start, bits[j] its 64 message bits (step 64 c + i at bit i of the pair); chains that are off keep their st.
+// Tracer::max_chunks bounds nchunk: a layout that never has more than one pass of chunks gets no loop over base.
+// Needs the decision words visible to the wave; leaves dec visible to it, and returns the state at step 0.
+// scratch: 2 nchunk bytes, per chunk the end state it was entered from and the state at its start.
+template <int NCH, typename Tracer>
+__device__ __forceinline__ unsigned vb_traceback(const Tracer &trace, uint32_t nchunk, unsigned end_state, uint8_t *dec, uint8_t *scratch, int lane)
+{
+    constexpr bool one_pass = Tracer::max_chunks <= 64u * NCH;
+    const uint32_t Lc = nchunk - 1;
+    uint8_t *Sarr = scratch, *Barr = scratch + nchunk;
+    // the chunks of the chains that are on: entered from S, arrived at st, their bytes
+    const auto commit = [&](const uint32_t (&cidx)[NCH], const bool (&on)[NCH], const unsigned (&S)[NCH], const unsigned (&st)[NCH], const uint32_t (&bits)[NCH][2]) {
+#pragma unroll
+        for (int j = 0; j < NCH; j++) if (on[j]) { Sarr[cidx[j]] = (uint8_t)S[j]; Barr[cidx[j]] = (uint8_t)st[j]; vb_emit(dec, cidx[j], bits[j][0], bits[j][1]); }
+    };
+    // pass 1: guess + trace
+    for (uint32_t base = 0; base < nchunk; base += 64 * NCH) {
+        uint32_t cidx[NCH], cnext[NCH], bits[NCH][2]; bool act[NCH], warm[NCH]; unsigned st[NCH], S[NCH];
+#pragma unroll
+        for (int j = 0; j < NCH; j++) {
+            cidx[j] = base + 64 * j + lane; act[j] = cidx[j] < nchunk;
+            cnext[j] = cidx[j] + 1; warm[j] = act[j] && cidx[j] < Lc; st[j] = cidx[j] == Lc ? end_state : 0u;
+        }
+        trace(cnext, warm, st, bits);                               // warm-up through chunk c+1 from state 0
+#pragma unroll
+        for (int j = 0; j < NCH; j++) S[j] = st[j];
+        trace(cidx, act, st, bits);
+        commit(cidx, act, S, st, bits);
+        if (one_pass) break;
+    }
+    // pass 2: verify the chain, re-trace what was entered from a wrong state, repeat to the fixed point
+    for (;;) {
+        __threadfence_block(); __builtin_amdgcn_wave_barrier();
+        bool changed = false;
+        for (uint32_t base = 0; base < nchunk; base += 64 * NCH) {
+            uint32_t cidx[NCH], bits[NCH][2]; bool redo[NCH]; unsigned st[NCH], S[NCH]; bool any = false;
+#pragma unroll
+            for (int j = 0; j < NCH; j++) {
+                cidx[j] = base + 64 * j + lane;
+                redo[j] = false; st[j] = 0;
+                if (cidx[j] < nchunk) {
+                    const unsigned need = cidx[j] == Lc ? end_state : Barr[cidx[j] + 1];
+                    if (Sarr[cidx[j]] != need) { redo[j] = true; st[j] = need; any = true; }
+                }
+                S[j] = st[j];
+            }
+            if (__any(any)) {
+                trace(cidx, redo, st, bits);
+                commit(cidx, redo, S, st, bits);
+                changed = true;
+            }
+            if (one_pass) break;
+        }
+        if (!__any(changed)) break;
+    }
+    return Barr[0];
+}
+// the tracer of viterbi27's layout: lane-major and rotated -- state s of step t sits in lane rotr(s, t mod 6), the lane's word of
+// chunk c and half h at dw32[(c * 64 + lane) * 2 + h]; r, the rotation phase, runs down with the steps
+struct V27Tracer {
+    static constexpr uint32_t max_chunks = 0xFFFFFFFFu;             // (a 65535-byte frame has about 8200)
+    const uint32_t *dw32; uint32_t Tn;
+    template <int NCH>
+    __device__ __forceinline__ void operator()(const uint32_t (&cidx)[NCH], const bool (&act)[NCH], unsigned (&st)[NCH], uint32_t (&bits)[NCH][2]) const
+    {
+        unsigned r[NCH]; uint32_t ns[NCH];
+#pragma unroll
+        for (int j = 0; j < NCH; j++) {
+            const uint32_t t0 = 64u * cidx[j];
+            ns[j] = act[j] ? min(64u, Tn - t0) : 0u;
+            r[j] = (t0 + ns[j]) % 6u;
+            bits[j][0] = bits[j][1] = 0u;
+        }
+#pragma unroll
+        for (int h = 1; h >= 0; h--) {
+            for (int uh = 31; uh >= 0; uh--) {
+                uint32_t word[NCH]; bool on[NCH];
+#pragma unroll
+                for (int j = 0; j < NCH; j++) {
+                    on[j] = (uint32_t)(32 * h + uh) < ns[j];
+                    const unsigned ln = ((st[j] >> r[j]) | (st[j] << (6 - r[j]))) & 63u;
+                    word[j] = on[j] ? dw32[((size_t)cidx[j] * 64 + ln) * 2 + h] : 0u;
+                }
+#pragma unroll
+                for (int j = 0; j < NCH; j++) {
+                    if (on[j]) {
+                        const uint32_t nh = min(ns[j] - 32u * h, 32u);
+                        bits[j][h] |= (st[j] & 1u) << uh;
+                        st[j] = (st[j] >> 1) | (((word[j] >> (nh - 1 - uh)) & 1u) << 5);
+                        r[j] = r[j] ? r[j] - 1 : 5;
+                    }
+                }
+            }
+        }
+    }
+};
+
+// The decoder: n message bytes of a frame's code stage, by one wave.  p: conv_p of the scheme; enc: VM 0 / 1: the coded bits,
+// packed; VM 2: one soft byte per coded bit; dw: 8 n + 6 words of scratch, rounded up to whole chunks of 64; scratch: two
+// bytes per chunk.  Forward pass (the FX_STAMPS clock is around it), the fence that shows every lane the others' decision
+// words, traceback.
+template <int VM>
+__device__ __forceinline__ void viterbi27(int p, uint32_t n, const uint8_t *enc, uint8_t *dec, unsigned long long *dw, uint8_t *scratch, int lane, uint32_t *stamp_fwd)
+{
+#ifdef FX_STAMPS
+    unsigned long long tv0_ = __builtin_readcyclecounter();
+#endif
+    const uint32_t Tn = 8 * n + 6;
+    v27_forward<VM>(p, Tn, enc, dw, lane);
     __threadfence_block();
     __builtin_amdgcn_wave_barrier();
 #ifdef FX_STAMPS
     if (lane == 0 && stamp_fwd) *stamp_fwd = (uint32_t)(__builtin_readcyclecounter() - tv0_);
 #endif
-    // ---- traceback, parallel over 64-step chunks with exact verification ----
-    // A serial traceback is Tn dependent steps.  Instead every lane traces whole chunks: chunk c is first entered
-    // from a *guess* S_c of its end state, obtained by tracing chunk c+1 back from state 0 (survivor paths merge
-    // within a few constraint lengths, so the guess is almost always right), and yields the state B_c at its
-    // start.  The chain is then verified: the true end state of chunk c is B_{c+1} (0 for the last chunk); any
-    // chunk whose guess differs is re-traced from the true state, until nothing changes.  At that fixed point
-    // every chunk was entered from the state the serial traceback would have had -- same bits, bit for bit.
-    {
-        const uint32_t nchunk = (Tn + 63) / 64, Lc = nchunk - 1;
-        const uint32_t *dw32 = reinterpret_cast<const uint32_t *>(dw);
-        uint8_t *Sarr = scratch, *Barr = scratch + nchunk;          // per-chunk end-state guess / start state
-        constexpr int NCH = 4;                                      // chains per lane, interleaved to overlap load latency
-        // one pass of up to NCH chunks per lane: st[] in/out, bits out
-        auto trace = [&](const uint32_t (&cidx)[NCH], const bool (&act)[NCH], unsigned (&st)[NCH], uint32_t (&bits)[NCH][2]) {
-            unsigned r[NCH]; uint32_t ns[NCH];
-#pragma unroll
-            for (int j = 0; j < NCH; j++) {
-                const uint32_t t0 = 64u * cidx[j];
-                ns[j] = act[j] ? min(64u, Tn - t0) : 0u;
-                r[j] = (t0 + ns[j]) % 6u;
-                bits[j][0] = bits[j][1] = 0u;
-            }
-#pragma unroll
-            for (int h = 1; h >= 0; h--) {
-                for (int uh = 31; uh >= 0; uh--) {
-                    uint32_t word[NCH]; bool on[NCH];
-#pragma unroll
-                    for (int j = 0; j < NCH; j++) {
-                        on[j] = (uint32_t)(32 * h + uh) < ns[j];
-                        const unsigned ln = ((st[j] >> r[j]) | (st[j] << (6 - r[j]))) & 63u;
-                        word[j] = on[j] ? dw32[((size_t)cidx[j] * 64 + ln) * 2 + h] : 0u;
-                    }
-#pragma unroll
-                    for (int j = 0; j < NCH; j++) {
-                        if (on[j]) {
-                            const uint32_t nh = min(ns[j] - 32u * h, 32u);
-                            bits[j][h] |= (st[j] & 1u) << uh;
-                            st[j] = (st[j] >> 1) | (((word[j] >> (nh - 1 - uh)) & 1u) << 5);
-                            r[j] = r[j] ? r[j] - 1 : 5;
-                        }
-                    }
-                }
-            }
-        };
-        auto emit = [&](uint32_t c, const uint32_t (&b)[2]) {
-            // steps 64c .. 64c+63 are output bytes 8c .. 8c+7, MSB first (the buffer has 8 bytes of slack)
-            uint32_t lo = 0, hi = 0;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                lo |= (__brev((b[0] >> (8 * k)) & 0xffu) >> 24) << (8 * k);
-                hi |= (__brev((b[1] >> (8 * k)) & 0xffu) >> 24) << (8 * k);
-            }
-            *reinterpret_cast<uint2 *>(dec + 8 * (size_t)c) = make_uint2(lo, hi);
-        };
-        // pass 1: guess + trace
-        for (uint32_t base = 0; base < nchunk; base += 64 * NCH) {
-            uint32_t cidx[NCH], cnext[NCH], bits[NCH][2]; bool act[NCH], warm[NCH]; unsigned st[NCH];
-#pragma unroll
-            for (int j = 0; j < NCH; j++) {
-                cidx[j] = base + 64 * j + lane; act[j] = cidx[j] < nchunk;
-                cnext[j] = cidx[j] + 1; warm[j] = act[j] && cidx[j] < Lc; st[j] = 0;
-            }
-            trace(cnext, warm, st, bits);                               // warm-up through chunk c+1 from state 0
-            unsigned S[NCH];
-#pragma unroll
-            for (int j = 0; j < NCH; j++) S[j] = st[j];
-            trace(cidx, act, st, bits);
-#pragma unroll
-            for (int j = 0; j < NCH; j++) if (act[j]) { Sarr[cidx[j]] = (uint8_t)S[j]; Barr[cidx[j]] = (uint8_t)st[j]; emit(cidx[j], bits[j]); }
-        }
-        // pass 2: verify the chain, re-trace what was entered from a wrong state, repeat to the fixed point
-        for (;;) {
-            __threadfence_block(); __builtin_amdgcn_wave_barrier();
-            bool changed = false;
-            for (uint32_t base = 0; base < nchunk; base += 64 * NCH) {
-                uint32_t cidx[NCH], bits[NCH][2]; bool redo[NCH]; unsigned st[NCH]; bool any = false;
-#pragma unroll
-                for (int j = 0; j < NCH; j++) {
-                    cidx[j] = base + 64 * j + lane;
-                    redo[j] = false; st[j] = 0;
-                    if (cidx[j] < nchunk) {
-                        const unsigned need = cidx[j] == Lc ? 0u : Barr[cidx[j] + 1];
-                        if (Sarr[cidx[j]] != need) { redo[j] = true; st[j] = need; any = true; }
-                    }
-                }
-                if (__any(any)) {
-                    unsigned S[NCH];
-#pragma unroll
-                    for (int j = 0; j < NCH; j++) S[j] = st[j];
-                    trace(cidx, redo, st, bits);
-#pragma unroll
-                    for (int j = 0; j < NCH; j++) if (redo[j]) { Sarr[cidx[j]] = (uint8_t)S[j]; Barr[cidx[j]] = (uint8_t)st[j]; emit(cidx[j], bits[j]); }
-                    changed = true;
-                }
-            }
-            if (!__any(changed)) break;
-        }
-    }
+    const V27Tracer trace = { reinterpret_cast<const uint32_t *>(dw), Tn };
+    vb_traceback<4>(trace, (Tn + 63) / 64, 0u, dec, scratch, lane);
 }
 
 // CRC over n bytes by one wavefront.  The register update is linear over GF(2): every lane runs the bitwise
@@ -4317,23 +4350,13 @@ __device__ __forceinline__ void vb_half(const uint32_t (&P)[64], uint32_t (&N)[6
     vb_butterfly<J0 + 12>(P, N, c2, c2p, hist); vb_butterfly<J0 + 13>(P, N, c2, c2p, hist); vb_butterfly<J0 + 14>(P, N, c2, c2p, hist); vb_butterfly<J0 + 15>(P, N, c2, c2p, hist);
 }
 
-// puncturing rows (A, B) of the K = 7 codes as bit masks over the column
-__device__ __forceinline__ void vb_punct(int p, unsigned &pa, unsigned &pb)
-{
-    switch (p) {
-    case 2: pa = 0x3; pb = 0x1; break;   case 3: pa = 0x3; pb = 0x5; break;   case 4: pa = 0xf; pb = 0x1; break;
-    case 5: pa = 0xb; pb = 0x15; break;  case 6: pa = 0x17; pb = 0x29; break; case 7: pa = 0x2f; pb = 0x51; break;
-    default: pa = 0x1; pb = 0x1; break;
-    }
-}
-
 // the coded-bit stream of one trellis block: position, puncturing column, a 64-bit window
 struct VbStream { uint32_t col, nb, w0, w1, wbase; };
 // the stream in front of trellis step ts of a code punctured with period p: its column, the coded bits before it; the window empty
 __device__ __forceinline__ VbStream vb_stream_at(uint32_t ts, unsigned p)
 {
     VbStream s;
-    s.col = ts % p; s.nb = (p == 1u) ? 2u * ts : ts + (ts + p - 1u) / p; s.w0 = s.w1 = s.wbase = 0;
+    s.col = ts % p; s.nb = conv_bits_before(ts, p); s.w0 = s.w1 = s.wbase = 0;
     return s;
 }
 // 2 x cost of the four expected pairs e = A | B << 1 against what was received at this step (punctured positions cost nothing)
@@ -4378,7 +4401,7 @@ __device__ __forceinline__ void vb_forward(const uint8_t *enc, int p, uint32_t t
     uint32_t P[64], N[64];
 #pragma unroll
     for (int i = 0; i < 64; i++) P[i] = 0u;
-    unsigned pa, pb; vb_punct(p, pa, pb);
+    unsigned pa, pb; conv_punct(p, pa, pb);
     const unsigned up = (unsigned)p;
     VbStream s = vb_stream_at(init == 0 ? t_reg - reg_at : t_reg, up);    // (the first step this lane really runs)
     const uint32_t *enc32 = reinterpret_cast<const uint32_t *>(enc);      // (byte_off is a multiple of 16)
@@ -4410,8 +4433,23 @@ __device__ __forceinline__ void vb_forward(const uint8_t *enc, int p, uint32_t t
     if (lane_on && end_vec) vb_save_vec(metric, end_vec);
 }
 
-// per work item, after the forward pass: [7:0] the end state its traceback started from, [15:8] the state it arrived at
-#define VB_ST_REP 0x20000u        // ... were not: the block has been run again from the true ones
+// The status word of a work item, vb_st[slot].  Its forward pass writes it whole (guess, the rest zero; fx_vbfix_kernel again,
+// with REP), its traceback fills in the two states and keeps the rest, fx_vbfinish_kernel reads it.
+//   [7:0]   end      the end state the item's traceback started from: 0 behind the tail, else the NEXT item's guess
+//   [15:8]  arrived  the state that traceback arrived at, at the item's first step
+//   [17]    REP      the hand-over check found the block started from wrong metric differences: it has been run again from the
+//                    true ones (fx_vbfinish_kernel counts these into the frame's record)
+//   [29:24] guess    the item's first FX_VB_TWARM steps traced back from state 0: the end state of the item BEFORE it, probably
+#define VB_ST_REP 0x20000u
+#define VB_ST_GUESS_SHIFT 24
+#define VB_ST_GUESS (63u << VB_ST_GUESS_SHIFT)
+__device__ __forceinline__ unsigned vb_st_end(uint32_t v) { return v & 0xffu; }
+__device__ __forceinline__ unsigned vb_st_arrived(uint32_t v) { return (v >> 8) & 0xffu; }
+__device__ __forceinline__ unsigned vb_st_guess(uint32_t v) { return (v >> VB_ST_GUESS_SHIFT) & 63u; }
+__device__ __forceinline__ bool vb_st_repeated(uint32_t v) { return (v & VB_ST_REP) != 0u; }
+// the word a forward pass leaves / the word a traceback makes of it (the guess bits stay: the item before may still be reading them)
+__device__ __forceinline__ uint32_t vb_st_fresh(unsigned guess, bool repeated) { return ((guess & 63u) << VB_ST_GUESS_SHIFT) | (repeated ? VB_ST_REP : 0u); }
+__device__ __forceinline__ uint32_t vb_st_traced(uint32_t old, unsigned end, unsigned arrived) { return end | (arrived << 8) | (old & (VB_ST_REP | VB_ST_GUESS)); }
 static_assert(FX_VB_WARM <= 128, "trellis blocks are at least 128 steps: a block's warm-up must fit into the block before it");
 // warm-up steps by puncturing period: the rate-1/2 code merges fastest; the high-rate punctured codes (5/6, 6/7, 7/8) carry
 // little redundancy per step and take longest (at marginal SNR a 96-step warm-up left every sixth of their blocks to be run again)
@@ -4477,10 +4515,10 @@ __device__ __forceinline__ void vb2_step(const uint32_t (&Q)[64], uint32_t (&N)[
 // The traceback of the block BEFORE this one does not know its end state.  Survivors merge within a few constraint lengths, so
 // tracing this block's first FX_VB_TWARM steps back from state 0 arrives, almost always, at the state the true path passes
 // through at this block's first step: the guess.  It is made here, by the lane that has just written those decision words
-// (they come back from the L2, not from HBM -- fx_vbtrace_kernel used to read them a second time for this), and left in bits
-// 24..29 of the item's status word; fx_vbfinish_kernel verifies every guess against the state the traceback really arrives at.
+// (they come back from the L2, not from HBM -- fx_vbtrace_kernel used to read them a second time for this), and left in
+// the guess field of the item's status word; fx_vbfinish_kernel verifies every guess against the state the traceback really arrives at.
 __device__ __forceinline__ void vb_trace16(const unsigned long long *dwl, uint32_t u0, uint32_t lim, unsigned &st, uint32_t &bits16);
-__device__ __forceinline__ uint32_t vb_make_guess(const unsigned long long *dwl, uint32_t len)
+__device__ __forceinline__ unsigned vb_make_guess(const unsigned long long *dwl, uint32_t len)
 {
     const uint32_t wl = min((uint32_t)FX_VB_TWARM, len);
     unsigned S = 0;
@@ -4489,7 +4527,7 @@ __device__ __forceinline__ uint32_t vb_make_guess(const unsigned long long *dwl,
         uint32_t unused = 0;
         vb_trace16(dwl, 16u * (uint32_t)grp, wl, S, unused);
     }
-    return (S & 63u) << 24;
+    return S;
 }
 
 struct VbHalf {                       // one of a lane's two work items
@@ -4520,7 +4558,7 @@ __device__ __forceinline__ void vb2_forward(int p, uint32_t blk, const VbHalf &A
     uint32_t Q[64], N[64];
 #pragma unroll
     for (int i = 0; i < 64; i++) Q[i] = 0u;
-    unsigned pa, pb; vb_punct(p, pa, pb);
+    unsigned pa, pb; conv_punct(p, pa, pb);
     const unsigned up = (unsigned)p;
     const uint32_t warm = vb_warm(p);
     VbStream sa = vb_stream_at(A.first ? A.t_reg : A.t_reg - warm, up), sb = vb_stream_at(B.first ? B.t_reg : B.t_reg - warm, up);
@@ -4588,6 +4626,23 @@ __device__ __forceinline__ VbItem vb_item(const FxPayJob *jobs, const uint32_t *
     it.t_reg = it.b * blk; it.t1 = min(it.Tn, it.t_reg + blk);
     return it;
 }
+// a lane's work item in the item kernels: the item of its slot, the slot's slab of decision words and its vector slot (start
+// record, end record 64 bytes behind it; vec_arena null in a kernel that uses none)
+struct VbWaveItem { VbItem it; uint32_t slot; unsigned long long *dwl; uint8_t *vec; };
+__device__ __forceinline__ VbWaveItem vb_wave_item(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, uint32_t slot, uint32_t blk,
+                                                   unsigned long long *dwv, uint8_t *vec_arena)
+{
+    VbWaveItem w;
+    w.slot = slot; w.it = vb_item(jobs, vb_items, item_cap, slot, blk);
+    w.dwl = vb_slab(dwv, slot, blk); w.vec = vec_arena ? vec_arena + (size_t)slot * 128u : nullptr;
+    return w;
+}
+// the wave's puncturing period: its items share their code (classes are padded to whole waves), but a padding slot has no frame
+// of its own, so the code is read from a lane of `live` (not zero)
+__device__ __forceinline__ int vb_wave_period(unsigned long long live, unsigned fec0)
+{
+    return conv_p((unsigned)__shfl((int)fec0, __ffsll((long long)live) - 1, 64));
+}
 
 extern "C" __global__ __launch_bounds__(64, 3)
 void fx_vbfwd_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, const FxBlockHdr *hdr, uint32_t first_item, const uint8_t *bufB,
@@ -4598,6 +4653,8 @@ void fx_vbfwd_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t it
     const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
     const uint32_t it0 = first_item + blockIdx.x * 128u;
     if (it0 >= nitems) return;
+    // (this kernel's register allocation is on the edge -- 168 VGPRs, 3 waves / SIMD --: its two halves name their slots, slabs and vector
+    // slots themselves, not through vb_wave_item, which cost it 16 bytes more scratch)
     const uint32_t slot_a = it0 + threadIdx.x, slot_b = slot_a + 64u;
     const VbItem ia = vb_item(jobs, vb_items, item_cap, slot_a, blk);
     VbItem ib = ia; ib.on = false;
@@ -4605,9 +4662,7 @@ void fx_vbfwd_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t it
     const unsigned long long live_a = __ballot(ia.on), live_b = __ballot(ib.on);
     if (!live_a && !live_b) return;
     const FxPayJob &ja = jobs[ia.g], &jb = jobs[ib.g];
-    // (a padding slot has no frame of its own: the wave's code class is read from a live lane)
-    const int p = live_a ? conv_p((unsigned)__shfl((int)ja.fec0, __ffsll((long long)live_a) - 1, 64))
-                         : conv_p((unsigned)__shfl((int)jb.fec0, __ffsll((long long)live_b) - 1, 64));
+    const int p = live_a ? vb_wave_period(live_a, ja.fec0) : vb_wave_period(live_b, jb.fec0);
     VbHalf A, B;
     A.enc = bufB + ja.byte_off; A.on = ia.on; A.first = !ia.on || ia.b == 0; A.t_reg = A.first && !ia.on ? 0u : ia.t_reg; A.t1 = ia.t1;
     A.dwl = vb_slab(dwv, slot_a, blk); A.vec = vec_arena + (size_t)slot_a * 128u;
@@ -4615,8 +4670,8 @@ void fx_vbfwd_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t it
     B.dwl = vb_slab(dwv, ib.on ? slot_b : slot_a, blk); B.vec = vec_arena + (size_t)(ib.on ? slot_b : slot_a) * 128u;
     __shared__ uint32_t rows[128 * VB_ROW];
     vb2_forward(p, blk, A, B, rows);
-    if (ia.on) vb_st[slot_a] = vb_make_guess(A.dwl, ia.t1 - ia.t_reg);
-    if (ib.on) vb_st[slot_b] = vb_make_guess(B.dwl, ib.t1 - ib.t_reg);
+    if (ia.on) vb_st[slot_a] = vb_st_fresh(vb_make_guess(A.dwl, ia.t1 - ia.t_reg), false);
+    if (ib.on) vb_st[slot_b] = vb_st_fresh(vb_make_guess(B.dwl, ib.t1 - ib.t_reg), false);
 }
 
 // The same pass, one work item per lane (32-bit metrics): twice the waves of the packed kernel at about 1.6 x its instructions
@@ -4629,17 +4684,16 @@ void fx_vbfwd1_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t i
     const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
     const uint32_t it0 = first_item + blockIdx.x * 64u;
     if (it0 >= nitems) return;
-    const uint32_t slot = it0 + threadIdx.x;
-    const VbItem it = vb_item(jobs, vb_items, item_cap, slot, blk);
+    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, dwv, vec_arena);
+    const VbItem &it = w.it;
     const unsigned long long live = __ballot(it.on);
     if (!live) return;
     const FxPayJob &job = jobs[it.g];
-    const int p = conv_p((unsigned)__shfl((int)job.fec0, __ffsll((long long)live) - 1, 64));
-    uint8_t *vec = vec_arena + (size_t)slot * 128u;
+    const int p = vb_wave_period(live, job.fec0);
     const bool first = !it.on || it.b == 0;
-    vb_forward(bufB + job.byte_off, p, it.t_reg, it.t1, first ? 1 : 0, nullptr, vb_slab(dwv, slot, blk), first ? nullptr : vec, vec + 64,
+    vb_forward(bufB + job.byte_off, p, it.t_reg, it.t1, first ? 1 : 0, nullptr, w.dwl, first ? nullptr : w.vec, w.vec + 64,
                vb_warm(p) + blk, vb_warm(p), it.on);
-    if (it.on) vb_st[slot] = vb_make_guess(vb_slab(dwv, slot, blk), it.t1 - it.t_reg);
+    if (it.on) vb_st[w.slot] = vb_st_fresh(vb_make_guess(w.dwl, it.t1 - it.t_reg), false);
 }
 
 __device__ __forceinline__ bool vb_same64(const uint8_t *a, const uint8_t *b)
@@ -4663,18 +4717,17 @@ void fx_vbfix_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t it
     const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
     const uint32_t it0 = first_item + blockIdx.x * 64u;
     if (it0 >= nitems) return;
-    const uint32_t slot = it0 + threadIdx.x;
-    const VbItem it = vb_item(jobs, vb_items, item_cap, slot, blk);
-    uint8_t *vec = vec_arena + (size_t)slot * 128u;
+    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, dwv, vec_arena);
+    const VbItem &it = w.it;
+    uint8_t *vec = w.vec;
     // (dbg bit 1, tests only: every other failing block is left as it is, for the fallback path to be exercised)
-    const bool bad = it.on && it.b > 0 && !vb_same64(vec, vec - 64) && !((dbg & 2u) && (slot & 1u));
+    const bool bad = it.on && it.b > 0 && !vb_same64(vec, vec - 64) && !((dbg & 2u) && (w.slot & 1u));
     const unsigned long long fails = __ballot(bad);
     if (!fails) return;
     const FxPayJob &job = jobs[it.g];
-    const int p = conv_p((unsigned)__shfl((int)job.fec0, __ffsll((long long)fails) - 1, 64));
-    unsigned long long *dwl = vb_slab(dwv, slot, blk);
-    vb_forward(bufB + job.byte_off, p, it.t_reg, it.t1, 2, bad ? vec - 64 : vec, dwl, vec, vec + 64, blk, 0u, bad);
-    if (bad) vb_st[slot] = VB_ST_REP | vb_make_guess(dwl, it.t1 - it.t_reg);       // (fx_vbfinish_kernel counts these; the guess: from the new decisions)
+    const int p = vb_wave_period(fails, job.fec0);
+    vb_forward(bufB + job.byte_off, p, it.t_reg, it.t1, 2, bad ? vec - 64 : vec, w.dwl, vec, vec + 64, blk, 0u, bad);
+    if (bad) vb_st[w.slot] = vb_st_fresh(vb_make_guess(w.dwl, it.t1 - it.t_reg), true);     // (the guess: from the new decisions)
 }
 
 // sixteen traceback steps u0 + 15 .. u0 of one lane (those below lim only): the words first, then the chain through them
@@ -4690,17 +4743,6 @@ __device__ __forceinline__ void vb_trace16(const unsigned long long *dwl, uint32
             st = (st >> 1) | ((unsigned)((q[i] >> st) & 1ull) << 5);
         }
     }
-}
-// steps 64c .. 64c+63 of a frame are output bytes 8c .. 8c+7, MSB first
-__device__ __forceinline__ void vb_emit(uint8_t *dec, uint32_t c, uint32_t b0, uint32_t b1)
-{
-    uint32_t lo = 0, hi = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        lo |= (__brev((b0 >> (8 * k)) & 0xffu) >> 24) << (8 * k);
-        hi |= (__brev((b1 >> (8 * k)) & 0xffu) >> 24) << (8 * k);
-    }
-    *reinterpret_cast<uint2 *>(dec + 8 * (size_t)c) = make_uint2(lo, hi);
 }
 // the 64-step chunk c of a region of len steps, entered in state st: bits out, state at the chunk's start back
 __device__ __forceinline__ unsigned vb_trace_chunk(const unsigned long long *dwl, uint32_t c, uint32_t len, unsigned st, uint32_t &b0, uint32_t &b1)
@@ -4727,19 +4769,19 @@ void fx_vbtrace_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t 
     const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
     const uint32_t it0 = first_item + blockIdx.x * 64u;
     if (it0 >= nitems) return;
-    const uint32_t slot = it0 + threadIdx.x;
-    const VbItem it = vb_item(jobs, vb_items, item_cap, slot, blk);
+    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, dwv, nullptr);
+    const VbItem &it = w.it;
+    const uint32_t slot = w.slot;
     if (!__ballot(it.on)) return;
     const FxPayJob &job = jobs[it.g];
     const uint32_t len = it.on ? it.t1 - it.t_reg : 0u;
-    uint32_t old = it.on ? vb_st[slot] : 0u;
-    const uint32_t flags = old & VB_ST_REP;
-    const unsigned long long *dwl = vb_slab(dwv, slot, blk);
+    const uint32_t old = it.on ? vb_st[slot] : 0u;
+    const unsigned long long *dwl = w.dwl;
     // the end state: 0 behind the flushed tail; elsewhere the guess the next block's forward pass left (its first FX_VB_TWARM
     // steps traced back from state 0)
     const bool has_next = it.on && it.b + 1u < it.nblk;
     // (dbg bit 0, tests only: the guess is state 0 -- wrong 63 times in 64, for the re-trace path to be exercised)
-    const unsigned S = (has_next && !(dbg & 1u)) ? ((vb_st[slot + 1u] >> 24) & 63u) : 0u;
+    const unsigned S = (has_next && !(dbg & 1u)) ? vb_st_guess(vb_st[slot + 1u]) : 0u;
     uint8_t *A = bufA + job.byte_off + it.t_reg / 8u;
     unsigned st = S;
     for (int c = (int)(blk / 64u) - 1; c >= 0; c--) {
@@ -4748,38 +4790,29 @@ void fx_vbtrace_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t 
         st = vb_trace_chunk(dwl, (uint32_t)c, len, st, b0, b1);
         if (64u * (uint32_t)c < len) vb_emit(A, (uint32_t)c, b0, b1);
     }
-    if (it.on) vb_st[slot] = S | (st << 8) | flags | (old & 0x3F000000u);       // (the guess bits stay: the item before this one may still be reading them)
+    if (it.on) vb_st[slot] = vb_st_traced(old, S, st);
 }
 
-// One block's traceback again, by a whole wave (its end-state guess was wrong): parallel over 64-step chunks with exact
-// verification -- chunk c is first entered from a guess of its end state (chunk c+1 traced back from state 0), then the
-// chain of chunk start states is checked and chunks entered from a wrong state are traced again, to the fixed point.
-// Returns the state at the block's first step.
+// the tracer of the batch path's layout: step-major, one chunk at a time (vb_trace_chunk)
+struct VbSlabTracer {
+    static constexpr uint32_t max_chunks = 64u;                           // (blk <= 4096)
+    const unsigned long long *dwl; uint32_t len;
+    template <int NCH>
+    __device__ __forceinline__ void operator()(const uint32_t (&cidx)[NCH], const bool (&act)[NCH], unsigned (&st)[NCH], uint32_t (&bits)[NCH][2]) const
+    {
+#pragma unroll
+        for (int j = 0; j < NCH; j++) if (act[j]) st[j] = vb_trace_chunk(dwl, cidx[j], len, st[j], bits[j][0], bits[j][1]);
+    }
+};
+// One block's traceback again, by a whole wave (its end-state guess was wrong): vb_traceback, a chunk per lane, from the true
+// end state.  scratch: 2 len / 64 bytes (the frame's byte buffer holds more than len / 8).  Returns the state at the block's
+// first step.
 __device__ __forceinline__ unsigned vb_retrace_block(const unsigned long long *dwl, uint32_t len, unsigned end_state, uint8_t *dec, uint8_t *scratch, int lane)
 {
-    const uint32_t nchunk = (len + 63) / 64, Lc = nchunk - 1;             // (at most 64 chunks: blk <= 4096)
-    uint8_t *Sarr = scratch, *Barr = scratch + nchunk;                     // (2 len / 64 bytes: the frame's byte buffer holds more than len / 8)
-    const uint32_t c = (uint32_t)lane;
-    if (c < nchunk) {
-        uint32_t b0, b1; unsigned S = end_state;
-        if (c < Lc) S = vb_trace_chunk(dwl, c + 1, len, 0u, b0, b1);
-        const unsigned Bst = vb_trace_chunk(dwl, c, len, S, b0, b1);
-        Sarr[c] = (uint8_t)S; Barr[c] = (uint8_t)Bst; vb_emit(dec, c, b0, b1);
-    }
-    for (;;) {
-        __threadfence_block(); __builtin_amdgcn_wave_barrier();
-        bool redo = false; unsigned need = 0;
-        if (c < nchunk) { need = c == Lc ? end_state : Barr[c + 1]; redo = Sarr[c] != need; }
-        if (!__any(redo)) break;
-        __builtin_amdgcn_wave_barrier();
-        if (redo) {
-            uint32_t b0, b1;
-            const unsigned Bst = vb_trace_chunk(dwl, c, len, need, b0, b1);
-            Sarr[c] = (uint8_t)need; Barr[c] = (uint8_t)Bst; vb_emit(dec, c, b0, b1);
-        }
-    }
+    const VbSlabTracer trace = { dwl, len };
+    const unsigned arrived = vb_traceback<1>(trace, (len + 63) / 64, end_state, dec, scratch, lane);
     __threadfence_block(); __builtin_amdgcn_wave_barrier();
-    return Barr[0];
+    return arrived;
 }
 
 // ---- front part, one wave per frame: symbols -> packet bytes, de-interleave, fec1 (not convolutional), de-interleave ----
@@ -4911,8 +4944,8 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
         const uint32_t v = b < nblk ? vb_st[at + b] : 0u, vn = b + 1u < nblk ? vb_st[at + b + 1u] : 0u;
         // every hand-over, on the records as they stand now: block b started from what block b - 1 ended with
         if (b > 0 && b < nblk) { const uint8_t *vec = vec_arena + (size_t)(at + b) * 128u; const bool same = vb_same64(vec, vec - 64); bad = bad || !same; }
-        rep += (uint32_t)__popcll(__ballot((v & VB_ST_REP) != 0u));
-        mism = mism || (b + 1u < nblk && (v & 0xffu) != ((vn >> 8) & 0xffu));
+        rep += (uint32_t)__popcll(__ballot(vb_st_repeated(v)));
+        mism = mism || (b + 1u < nblk && vb_st_end(v) != vb_st_arrived(vn));
     }
     if (__any(bad)) {                                                       // an unverified hand-over: the frame is decoded the other way
         // (the host's copy only learns THAT frames were handed back -- a plain store, whoever gets there --; fxrx_collect then fetches the
@@ -4921,11 +4954,11 @@ void fx_vbfinish_kernel(const FxPayJob *jobs, const uint32_t *job_idx, FxBlockHd
         return;
     }
     if (__any(mism)) {                                                      // a wrong end-state guess: from the last block downwards
-        unsigned need = (vb_st[at + nblk - 1u] >> 8) & 0xffu;
+        unsigned need = vb_st_arrived(vb_st[at + nblk - 1u]);
         for (int b = (int)nblk - 2; b >= 0; b--) {
             const uint32_t v = vb_st[at + (uint32_t)b];
-            if ((v & 0xffu) != need) need = vb_retrace_block(vb_slab(dwv, at + (uint32_t)b, blk), blk, need, A + (size_t)b * (blk / 8u), B, lane);
-            else need = (v >> 8) & 0xffu;
+            if (vb_st_end(v) != need) need = vb_retrace_block(vb_slab(dwv, at + (uint32_t)b, blk), blk, need, A + (size_t)b * (blk / 8u), B, lane);
+            else need = vb_st_arrived(v);
         }
     }
     __threadfence_block(); __builtin_amdgcn_wave_barrier();
@@ -5223,19 +5256,13 @@ __device__ __forceinline__ void tx_fec_encode(unsigned fs, uint32_t n, const uin
     const int p = conv_p(fs);
     unsigned bk, bn;
     if (p) {                                     // K=7 (0x6d, 0x4f): every coded bit is a parity of a 7-bit window; a byte per lane
-        unsigned pa, pb;
-        switch (p) {
-        case 2: pa = 0x3; pb = 0x1; break;   case 3: pa = 0x3; pb = 0x5; break;   case 4: pa = 0xf; pb = 0x1; break;
-        case 5: pa = 0xb; pb = 0x15; break;  case 6: pa = 0x17; pb = 0x29; break; case 7: pa = 0x2f; pb = 0x51; break;
-        default: pa = 1; pb = 1; break;
-        }
+        unsigned pa, pb; conv_punct(p, pa, pb);
         unsigned ncol = 0, slot_col[8], slot_gen[8];        // kept bits of one puncturing period: slot -> (column, generator)
         for (int c = 0; c < p; c++) {
             if ((pa >> c) & 1) { slot_col[ncol] = (unsigned)c; slot_gen[ncol] = 0x6d; ncol++; }
             if ((pb >> c) & 1) { slot_col[ncol] = (unsigned)c; slot_gen[ncol] = 0x4f; ncol++; }
         }
-        const uint32_t Tn = 8 * n + 6;
-        const uint32_t nbits = p == 1 ? 2 * Tn : Tn + (Tn + (uint32_t)p - 1) / (uint32_t)p;
+        const uint32_t nbits = conv_bits_before(8 * n + 6, (unsigned)p);
         for (uint32_t j = lane; j < el; j += DEC_THREADS) {
             unsigned v = 0;
             for (int b = 0; b < 8; b++) {
