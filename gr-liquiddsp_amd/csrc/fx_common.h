@@ -340,6 +340,7 @@ struct FxPllMember {
 struct FxPllGang { uint32_t n; FxPllMember m[FX_GANG_MAX]; };
 struct FxVbpreMember {
     FxPayJob *jobs; const uint32_t *job_idx; const FxBlockHdr *hdr; const uint8_t *hard; uint8_t *bufA, *bufB, *out; FxOutRec *recs; FxBlockHdr *hdr_host;
+    uint32_t *vb_items; uint32_t vb_cap; // the block's trellis items (FxPlanArgs.vb_items): a frame's wave writes the frame's run
     uint32_t first_wave, n_waves;        // the waves this member would have launched alone: blockIdx.x = 0 .. n_waves - 1 stands for job first_wave + blockIdx.x
 };
 struct FxVbpreGang { uint32_t n; FxVbpreMember m[FX_GANG_MAX]; };
@@ -354,7 +355,8 @@ struct FxPlanArgs {
     FxPayJob *pjobs; FxOutRec *recs;     // out: one per chain frame (recs: pinned host memory)
     uint32_t *mf_job, *mf_c0, mf_cap;    // out: matched-filter items (frame, first symbol)
     uint32_t *pll_list, *dec_list, list_cap;   // out: the PLL lists (one per modulation class) and the three decode lists, list_cap slots each
-    uint32_t *vb_items, vb_cap;          // out: batch-Viterbi work items (frame at [i], trellis block at [vb_cap + i])
+    uint32_t *vb_items, vb_cap;          // batch-Viterbi work items (frame at [i], trellis block at [vb_cap + i]): out, the padding of the code classes only;
+                                         // a frame's run (FxPayJob.vb_off, vb_nblk) is written by fx_vbpre_kernel
     FxBlockHdr *hdr, *hdr_pay, *hdr_host;   // the walk-phase header (zeroed again) / what the payload kernels read / the host's copy
     uint32_t *ws;                        // fx_plan_ws_words() words, zero between blocks
 };

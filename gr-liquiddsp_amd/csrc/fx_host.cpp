@@ -889,7 +889,7 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
 
 static FxVbpreMember vbpre_member(Slot &sl, uint32_t first_wave, uint32_t n_waves)
 {
-    return FxVbpreMember{ sl.d_pjobs.p, sl.dec_list(kDecBatch), sl.hdr_pay(), sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, first_wave, n_waves };
+    return FxVbpreMember{ sl.d_pjobs.p, sl.dec_list(kDecBatch), sl.hdr_pay(), sl.d_hard.p, sl.d_bufA.p, sl.d_bufB.p, sl.h_out.p, sl.h_recs.p, sl.h_hdr.p, sl.d_vb_items.p, sl.vb_cap, first_wave, n_waves };
 }
 // ---- the tails of n blocks (n <= FX_GANG_MAX; n = 1: a block's own tail, on its own stream), on the last one's stream: one PLL
 // launch for all, each block's own decode launches where it has any, one fx_vbpre_kernel launch for all, each block's trellis

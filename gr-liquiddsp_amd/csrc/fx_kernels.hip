@@ -2388,11 +2388,9 @@ void fx_planlists_kernel(const FxPlanArgs a)
         if (val && pp < a.list_cap) a.pll_list[pp] = g;
         const uint32_t rs = key.dec(bt), dp = wave_agg_add(pw + PW_DEC_FILL, rs, 1u, val);
         if (val && dp < a.list_cap) a.dec_list[(size_t)rs * a.list_cap + dp] = g;
-        const uint32_t at = sh.vbc_base[key.vc] + wave_agg_add(pw + PW_VBC_FILL, key.vc, vnb, bt);   // its trellis blocks, among those of the same code
-        if (bt) {
-            for (uint32_t b = 0; b < vnb; b++) if (at + b < a.vb_cap) { a.vb_items[at + b] = g; a.vb_items[a.vb_cap + at + b] = b; }
-            a.pjobs[g].vb_off = at;
-        }
+        // its trellis blocks, among those of the same code: the run's place only -- fx_vbpre_kernel writes the items (vb_item below)
+        const uint32_t at = sh.vbc_base[key.vc] + wave_agg_add(pw + PW_VBC_FILL, key.vc, vnb, bt);
+        if (bt) a.pjobs[g].vb_off = at;
     }
     if (blockIdx.x == 0) plan_pad_lists<PLAN_THREADS>(cnt, sh.cls_base, sh.vbc_base, a);
     // the workgroup that finishes last: block header for the payload kernels and for the host; counters, workspace and the
@@ -2426,9 +2424,10 @@ void fx_planlists_kernel(const FxPlanArgs a)
 //   jobs     in batches of up to PLAN_BATCH frames of the thread: the rest of every frame record of the batch is loaded (its lines are the
 //            ones the size words came from) BEFORE the first job or host record goes out -- memory operations complete in order, so a load
 //            issued behind a record's stores would wait until they have reached host memory.  List slots come from LDS cursors (any order
-//            within a class, as with the pair's atomics), and the frame's trellis / matched-filter runs are noted in LDS: keep[] = (first
-//            trellis item, trellis blocks, first filter item, filter blocks)
-//   items    16 lanes per frame write those runs, consecutive lanes consecutive slots
+//            within a class, as with the pair's atomics), and the frame's matched-filter run is noted in LDS: keep[] = (first filter item,
+//            filter blocks).  Its trellis run gets its place here (vb_off, from the code class's cursor) and nothing else: the items
+//            of a run are written by the frame's wave of fx_vbpre_kernel, and only for a frame that needs them
+//   items    16 lanes per frame write the matched-filter runs, consecutive lanes consecutive slots
 //   header   read a word per thread at the start, filled from LDS, mirrored and zeroed a word per thread
 // The arena offsets, the matched-filter item order and the frames demoted at the end of the trellis arena are the pair's: all three depend
 // only on prefix sums in frame order.
@@ -2458,11 +2457,11 @@ void fx_planfused_kernel(const FxPlanArgs a)
     constexpr int KEEP = PLAN_TILE / NT, JB = PLAN_BATCH;
     static_assert(NT % 64 == 0 && KEEP * NT == PLAN_TILE && KEEP % JB == 0, "whole waves; the tile is KEEP frames a thread, in whole batches");
     __shared__ PlanOneShared<NT> sh;
-    __shared__ uint4 keep[PLAN_TILE];
+    __shared__ uint2 keep[PLAN_TILE];
     const PlanCounts<false> cnt{ sh.cnt + PO_CLS, sh.cnt + PO_DEC, sh.cnt + PO_VBC };
     const uint32_t tid = threadIdx.x, nstreams = a.nstreams;
     // diagnostic builds: thread 0's shader clocks per step, summed over tiles, in the header's free stamp words -- [1] header read, stream
-    // bases, sizes, scan, counts, class bases | [2] jobs and records | [6] item runs, padding | [7] the fence in front of the header
+    // bases, sizes, scan, counts, class bases | [2] jobs and records | [6] matched-filter item runs, padding | [7] the fence in front of the header
 #ifdef FX_STAMPS
     unsigned long long tk_ = __builtin_readcyclecounter(); uint32_t st1_ = 0, st2_ = 0, st6_ = 0, st7_ = 0;
 #define PLAN_TICK(acc) do { const unsigned long long t_ = __builtin_readcyclecounter(); acc += (uint32_t)(t_ - tk_); tk_ = t_; } while (0)
@@ -2568,7 +2567,7 @@ void fx_planfused_kernel(const FxPlanArgs a)
                         if (dp < a.list_cap) a.dec_list[(size_t)rs * a.list_cap + dp] = g;
                         if (f.batch) at = sh.vbc_base[key.vc] + atomicAdd(&sh.fill[PO_VBC + key.vc], f.vnb);   // its trellis blocks, among those of the same code
                     }
-                    keep[g - t0] = make_uint4(at, f.vnb, st[PV_MF], f.nblk);
+                    keep[g - t0] = make_uint2(st[PV_MF], f.nblk);
                     plan_emit(a.pjobs + g, a.recs + g, r[i], wi, f, st, a.eq, slot[b0 + i], at);
 #pragma unroll
                     for (int q = 0; q < PLAN_NV; q++) st[q] += v[q];
@@ -2576,12 +2575,11 @@ void fx_planfused_kernel(const FxPlanArgs a)
             }
             __syncthreads();
             PLAN_TICK(st2_);
-            // 5. the trellis and matched-filter runs of the tile's frames: 16 lanes per frame, consecutive lanes consecutive slots
+            // 5. the matched-filter runs of the tile's frames: 16 lanes per frame, consecutive lanes consecutive slots
             for (uint32_t k = tid >> 4; k < nt; k += NT / 16) {
-                const uint4 kp = keep[k];
+                const uint2 kp = keep[k];
                 const uint32_t g = t0 + k, sub = tid & 15u;
-                for (uint32_t b = sub; b < kp.y; b += 16u) if (kp.x + b < a.vb_cap) { a.vb_items[kp.x + b] = g; a.vb_items[a.vb_cap + kp.x + b] = b; }
-                for (uint32_t c = sub; c < kp.w; c += 16u) if (kp.z + c < a.mf_cap) { a.mf_job[kp.z + c] = g; a.mf_c0[kp.z + c] = c * 1024u; }
+                for (uint32_t c = sub; c < kp.y; c += 16u) if (kp.x + c < a.mf_cap) { a.mf_job[kp.x + c] = g; a.mf_c0[kp.x + c] = c * 1024u; }
             }
             __syncthreads();                                                 // (keep[] belongs to the next tile from here)
         }
@@ -4609,19 +4607,29 @@ __device__ __forceinline__ void vb2_forward(int p, uint32_t blk, const VbHalf &A
 }
 
 // ---- forward pass: one lane per (frame, trellis block) work item; the items of a wave share their puncturing code ----
-// vb_items: [0, cap) the frame of every item slot (0xFFFFFFFF: padding of a code class's last wave), [cap, 2 cap) its block.
-// The items of a frame fx_vbpre_kernel has decoded itself (FxPayJob.vb_clean) are off like padding: the trellis kernels
-// neither read nor write their status words, vector records or decision words (all stale), and a wave without a live item
-// leaves at once.
+// vb_items: [0, cap) the frame of every item slot (0xFFFFFFFF: off), [cap, 2 cap) its block.
+// Who writes a slot.  The plan stage gives every batch frame its run of slots (FxPayJob.vb_off, vb_nblk) and writes 0xFFFFFFFF into
+// the padding of each code class's last wave -- nothing else.  The run itself is written by the frame's wave of fx_vbpre_kernel
+// (vb_write_run): frame and block for a frame that needs the trellis, 0xFFFFFFFF for one the wave has decoded itself
+// (FxPayJob.vb_clean).  A slot below the block's n_vb_items whose frame no wave of fx_vbpre_kernel has reached yet (the grid
+// follows the last block's traffic; fx_host.cpp:finish_decode then runs it over all frames, the trellis kernels behind it) holds
+// what an earlier block left.  So an item is ON only if its frame word names a frame of THIS block whose job owns the slot and
+// whose block word is the slot's place in that run; the frame word is not used as an index before it is known to be below the
+// block's frame count (nframes: the block header's n_frames).  A stale item that passes is this block's layout, and decodes what
+// an item written by the plan stage would decode for a frame fx_vbpre_kernel has not reached: work that finish_decode does again.
+// Items that are off -- padding, clean frames, stale words -- are alike: the trellis kernels neither read nor write their status
+// words, vector records or decision words (all stale), and a wave without a live item leaves at once.
 struct VbItem { uint32_t g, b, t_reg, t1, Tn, nblk; bool on; };
-__device__ __forceinline__ VbItem vb_item(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, uint32_t slot, uint32_t blk)
+__device__ __forceinline__ VbItem vb_item(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, uint32_t slot, uint32_t blk, uint32_t nframes)
 {
     VbItem it;
     const uint32_t item = vb_items[slot];
-    it.on = item != 0xFFFFFFFFu;
-    it.g = it.on ? item : 0u; it.b = it.on ? vb_items[item_cap + slot] : 0u;
+    it.on = item < nframes;                                                // (0xFFFFFFFF is no frame of any block)
+    it.g = it.on ? item : 0u;
     const FxPayJob &job = jobs[it.g];
-    it.on = it.on && job.vb_clean == 0u;
+    const uint32_t b = slot - job.vb_off;                                  // (unsigned: a slot in front of the run is far above any vb_nblk; a frame off the batch path has vb_nblk 0)
+    it.on = it.on && job.vb_clean == 0u && b < job.vb_nblk && vb_items[item_cap + slot] == b;
+    it.b = it.on ? b : 0u;
     it.Tn = 8u * job.k + 6u; it.nblk = job.vb_nblk;
     it.t_reg = it.b * blk; it.t1 = min(it.Tn, it.t_reg + blk);
     return it;
@@ -4629,11 +4637,11 @@ __device__ __forceinline__ VbItem vb_item(const FxPayJob *jobs, const uint32_t *
 // a lane's work item in the item kernels: the item of its slot, the slot's slab of decision words and its vector slot (start
 // record, end record 64 bytes behind it; vec_arena null in a kernel that uses none)
 struct VbWaveItem { VbItem it; uint32_t slot; unsigned long long *dwl; uint8_t *vec; };
-__device__ __forceinline__ VbWaveItem vb_wave_item(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, uint32_t slot, uint32_t blk,
+__device__ __forceinline__ VbWaveItem vb_wave_item(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, uint32_t slot, uint32_t blk, uint32_t nframes,
                                                    unsigned long long *dwv, uint8_t *vec_arena)
 {
     VbWaveItem w;
-    w.slot = slot; w.it = vb_item(jobs, vb_items, item_cap, slot, blk);
+    w.slot = slot; w.it = vb_item(jobs, vb_items, item_cap, slot, blk, nframes);
     w.dwl = vb_slab(dwv, slot, blk); w.vec = vec_arena ? vec_arena + (size_t)slot * 128u : nullptr;
     return w;
 }
@@ -4650,15 +4658,15 @@ void fx_vbfwd_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t it
 {
     // (128 item slots per wave: the low-half blocks are slots it0 .. it0 + 63, the high-half blocks the 64 behind them;
     // code classes are padded to 128 slots, so a wave's items share their puncturing code)
-    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
+    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk, nframes = hdr->n_frames;
     const uint32_t it0 = first_item + blockIdx.x * 128u;
     if (it0 >= nitems) return;
     // (this kernel's register allocation is on the edge -- 168 VGPRs, 3 waves / SIMD --: its two halves name their slots, slabs and vector
     // slots themselves, not through vb_wave_item, which cost it 16 bytes more scratch)
     const uint32_t slot_a = it0 + threadIdx.x, slot_b = slot_a + 64u;
-    const VbItem ia = vb_item(jobs, vb_items, item_cap, slot_a, blk);
+    const VbItem ia = vb_item(jobs, vb_items, item_cap, slot_a, blk, nframes);
     VbItem ib = ia; ib.on = false;
-    if (slot_b < nitems) ib = vb_item(jobs, vb_items, item_cap, slot_b, blk);
+    if (slot_b < nitems) ib = vb_item(jobs, vb_items, item_cap, slot_b, blk, nframes);
     const unsigned long long live_a = __ballot(ia.on), live_b = __ballot(ib.on);
     if (!live_a && !live_b) return;
     const FxPayJob &ja = jobs[ia.g], &jb = jobs[ib.g];
@@ -4681,10 +4689,10 @@ extern "C" __global__ __launch_bounds__(64)
 void fx_vbfwd1_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, const FxBlockHdr *hdr, uint32_t first_item, const uint8_t *bufB,
                       unsigned long long *dwv, uint8_t *vec_arena, uint32_t *vb_st)
 {
-    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
+    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk, nframes = hdr->n_frames;
     const uint32_t it0 = first_item + blockIdx.x * 64u;
     if (it0 >= nitems) return;
-    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, dwv, vec_arena);
+    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, nframes, dwv, vec_arena);
     const VbItem &it = w.it;
     const unsigned long long live = __ballot(it.on);
     if (!live) return;
@@ -4714,10 +4722,10 @@ extern "C" __global__ __launch_bounds__(64)
 void fx_vbfix_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, const FxBlockHdr *hdr, uint32_t first_item, const uint8_t *bufB,
                      unsigned long long *dwv, uint8_t *vec_arena, uint32_t *vb_st, uint32_t dbg)
 {
-    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
+    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk, nframes = hdr->n_frames;
     const uint32_t it0 = first_item + blockIdx.x * 64u;
     if (it0 >= nitems) return;
-    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, dwv, vec_arena);
+    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, nframes, dwv, vec_arena);
     const VbItem &it = w.it;
     uint8_t *vec = w.vec;
     // (dbg bit 1, tests only: every other failing block is left as it is, for the fallback path to be exercised)
@@ -4766,10 +4774,10 @@ extern "C" __global__ __launch_bounds__(64)
 void fx_vbtrace_kernel(const FxPayJob *jobs, const uint32_t *vb_items, uint32_t item_cap, const FxBlockHdr *hdr, uint32_t first_item, uint8_t *bufA,
                        unsigned long long *dwv, uint32_t *vb_st, uint32_t dbg)
 {
-    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk;
+    const uint32_t nitems = hdr->n_vb_items, blk = hdr->vb_blk, nframes = hdr->n_frames;
     const uint32_t it0 = first_item + blockIdx.x * 64u;
     if (it0 >= nitems) return;
-    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, dwv, nullptr);
+    const VbWaveItem w = vb_wave_item(jobs, vb_items, item_cap, it0 + threadIdx.x, blk, nframes, dwv, nullptr);
     const VbItem &it = w.it;
     const uint32_t slot = w.slot;
     if (!__ballot(it.on)) return;
@@ -4855,8 +4863,9 @@ __device__ __forceinline__ uint64_t vb_lds_word(const uint8_t *X, uint32_t w)
 // the Viterbi decoder outputs (every other path into any state of it costs d_free = 10 or more), so it is written to A here
 // -- bit 7 of byte j is step 8 j, as the traceback leaves it -- and the frame is marked clean: the trellis kernels skip it and
 // the frame's tail follows at once (fx_vbclean.h: the code's feed-forward inverse, the re-encoding, the comparison; DESIGN.md
-// section 2.3).  A lane per 32-step word, the words before it re-read from LDS for the carries.  Returns whether the frame is clean.
-__device__ __forceinline__ bool vb_clean_check(FxPayJob *jobs, uint32_t jf, uint32_t k, const uint8_t *X, uint8_t *A, int lane)
+// section 2.3).  A lane per 32-step word, the words before it re-read from LDS for the carries.  Returns whether the frame is clean
+// (its caller marks the job).
+__device__ __forceinline__ bool vb_clean_check(uint32_t k, const uint8_t *X, uint8_t *A, int lane)
 {
     const uint32_t Tn = 8u * k + 6u, nw = (Tn + 31u) / 32u;
     bool ok = true;
@@ -4872,8 +4881,19 @@ __device__ __forceinline__ bool vb_clean_check(FxPayJob *jobs, uint32_t jf, uint
             reinterpret_cast<uint32_t *>(A)[w] = __builtin_bswap32(u);   // (byte_off is a multiple of 16; bytes up to k + 3 are the frame's)
         }
     }
-    if (lane == 0) jobs[jf].vb_clean = clean ? 1u : 0u;
     return clean;
+}
+// The frame's run of trellis items (vb_item above: who writes a slot, and what an unwritten one means): frame and block for every slot
+// of a frame that needs the trellis, "off" in the frame words of one that does not.  Lanes take consecutive slots; slots are bounded
+// by the arena as the plan stage bounds the runs it hands out.
+__device__ __forceinline__ void vb_write_run(uint32_t *vb_items, uint32_t item_cap, uint32_t g, uint32_t at, uint32_t nblk, bool clean, int lane)
+{
+    for (uint32_t b = lane; b < nblk; b += DEC_THREADS) {
+        const uint32_t slot = at + b;
+        if (slot >= item_cap) break;
+        vb_items[slot] = clean ? 0xFFFFFFFFu : g;
+        if (!clean) vb_items[item_cap + slot] = b;
+    }
 }
 // early_tail: a clean frame is finished here -- de-whitening, CRC, payload and record to the host (dec_tail) --, the wave has its job
 // and has just written the message; for any other frame one lane raises hdr_host->vb_dirty (a plain store, whoever gets there): the
@@ -4906,7 +4926,11 @@ void fx_vbpre_kernel(const FxVbpreGang g, const FxTables *T, uint32_t clean_on, 
         for (uint32_t j = lane; j < n16; j += DEC_THREADS) reinterpret_cast<uint4 *>(B)[j] = reinterpret_cast<const uint4 *>(X)[j];
         // (the check reads up to 8 bytes past the coded bits: zeroed above; packets on the global-memory branch below keep the trellis)
         job.k = __builtin_amdgcn_readfirstlane(job.k);
-        const bool clean = clean_on && conv_p(job.fec0) == 1 && vb_clean_check(jobs, jf, job.k, X, A, lane);
+        // (a punctured code is never clean, and leaves the job's vb_clean as the plan stage wrote it: 0)
+        const bool checked = clean_on && conv_p(job.fec0) == 1;
+        const bool clean = checked && vb_clean_check(job.k, X, A, lane);
+        vb_write_run(m.vb_items, m.vb_cap, jf, job.vb_off, job.vb_nblk, clean, lane);
+        if (checked && lane == 0) jobs[jf].vb_clean = clean ? 1u : 0u;
         if (!early_tail) return;
         if (!clean) { if (lane == 0) hdr_host->vb_dirty = 1u; return; }
         job.pay_len = __builtin_amdgcn_readfirstlane(job.pay_len); job.check = __builtin_amdgcn_readfirstlane(job.check);
@@ -4915,6 +4939,7 @@ void fx_vbpre_kernel(const FxVbpreGang g, const FxTables *T, uint32_t clean_on, 
         return;
     }
     vbpre_front<false>(job, hs, nullptr, A, B, T, lane);
+    vb_write_run(m.vb_items, m.vb_cap, jf, job.vb_off, job.vb_nblk, false, lane);
     if (early_tail && lane == 0) hdr_host->vb_dirty = 1u;
 }
 
