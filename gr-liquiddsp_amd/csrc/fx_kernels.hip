@@ -19,7 +19,8 @@
 //                       polyphase matched filter + decimate-by-2 over the payload span
 //                       (fx_paymf_kernel: the same at every sample, then the frame's equaliser taps, when the equaliser stage is on).
 //   fx_paypll_kernel    one lane per frame: the decision-directed payload PLL (the only true
-//                       sample-to-sample recurrence of the path), hard demod, EVM.
+//                       sample-to-sample recurrence of the path), hard demod, EVM; raw symbols fetched
+//                       PLL_AHEAD blocks of eight ahead into a register ring.
 //   fx_vbpre / fx_vbfwd / fx_vbfix / fx_vbtrace / fx_vbfinish   packet decode with the K=7 Viterbi run a lane per trellis
 //                       block (two blocks per lane, packed 16-bit metrics), hand-overs speculated and verified.
 //   fx_paydec_kernel    one wavefront per frame (lane = trellis state): soft decisions, Reed-Solomon, frames without a
@@ -2755,11 +2756,16 @@ extern "C" hipError_t fx_launch_paymf(unsigned grid, int eq, hipStream_t st, con
 // ===================================================================== payload: PLL + hard demod (lane per frame)
 // The decision-directed loop is a strict symbol-to-symbol recurrence, so a frame is one lane.  What the
 // lane can do is keep the recurrence's critical path short: raw symbols are fetched eight at a time
-// (one block ahead, 64 contiguous bytes per lane), results leave as 16-byte stores, the sin/cos table sits
+// (PLL_AHEAD blocks ahead, 64 contiguous bytes per lane and block), results leave as 16-byte stores, the sin/cos table sits
 // in LDS and the four PSK2/PSK4 constellation points in registers.
 #define PLL_THREADS 64
 #define PLL_MAX_WAVES 4       // waves per workgroup is a launch-time placement knob (one wave per SIMD of a CU at 4)
 #define PLL_BLK     8
+// Blocks of eight fetched ahead of the one the recurrence is in.  A lane's four loads touch four cache lines of its own (lanes
+// are a frame apart), and one block of cover (about 2 200 cycles) did not hide them: of 1, 2, 3 and 4 blocks ahead, 3 gave the
+// shortest launch (shortest of 23 launches 0.79 / 0.79 / 0.75 / 0.76 ms; profiles/README.md, `pllahead`).
+#define PLL_AHEAD   3
+#define PLL_RING    (PLL_AHEAD + 1)
 
 __device__ __forceinline__ void pll_load8(const float4 *p, float4 b[4]) { b[0] = p[0]; b[1] = p[1]; b[2] = p[2]; b[3] = p[3]; }
 
@@ -2843,15 +2849,31 @@ __device__ __forceinline__ void pll_frame(uint32_t f, const FxPayJob *jobs, cons
     uint32_t th = job.pll_th; float fq = job.pll_f * 683565248.0f, evm = 0.0f; unsigned prev = 0;
     const unsigned nsym = job.nsym;
     const uint32_t nfull = nsym / PLL_BLK, rem = nsym % PLL_BLK;
-    float4 cur[4], nxt[4];
-    if (nsym) pll_load8(in, cur);
-    for (uint32_t b = 0; b < nfull; b++) {
-        if ((b + 1) * PLL_BLK < nsym) pll_load8(in + 4 * (b + 1), nxt);
-        pll_block8<MS, false>(cur, PLL_BLK, th, fq, evm, prev, sc, out + 4 * b, hd + b);
+    // raw symbols: a register ring of PLL_RING blocks; block b lives in slot b % PLL_RING.  The block loop is unrolled by the
+    // ring length, so every slot index is a compile-time constant (registers, no private memory).
+    float4 ring[PLL_RING][4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) cur[k] = nxt[k];
+    for (int a = 0; a < PLL_AHEAD; a++)
+        if ((uint32_t)a * PLL_BLK < nsym) pll_load8(in + 4 * a, ring[a]);
+    // whole turns of the ring: full blocks only
+    uint32_t b = 0;
+    for (; b + PLL_RING <= nfull; b += PLL_RING) {
+#pragma unroll
+        for (int s = 0; s < PLL_RING; s++) {
+            if ((b + s + PLL_AHEAD) * PLL_BLK < nsym) pll_load8(in + 4 * (b + s + PLL_AHEAD), ring[(s + PLL_AHEAD) % PLL_RING]);
+            pll_block8<MS, false>(ring[s], PLL_BLK, th, fq, evm, prev, sc, out + 4 * (b + s), hd + (b + s));
+        }
     }
-    if (rem) pll_block8<MS, true>(cur, rem, th, fq, evm, prev, sc, out + 4 * nfull, hd + nfull);
+    // the last, partial turn (b is a multiple of the ring length): fewer than PLL_RING full blocks, then the TAIL block in its slot
+#pragma unroll
+    for (int s = 0; s < PLL_RING; s++) {
+        if (b + s < nfull) {
+            if ((b + s + PLL_AHEAD) * PLL_BLK < nsym) pll_load8(in + 4 * (b + s + PLL_AHEAD), ring[(s + PLL_AHEAD) % PLL_RING]);
+            pll_block8<MS, false>(ring[s], PLL_BLK, th, fq, evm, prev, sc, out + 4 * (b + s), hd + (b + s));
+        } else if (b + s == nfull && rem) {
+            pll_block8<MS, true>(ring[s], rem, th, fq, evm, prev, sc, out + 4 * nfull, hd + nfull);
+        }
+    }
     recs[f].evm_sum = evm;                                                          // straight into the host's result record
 }
 
