@@ -48,6 +48,7 @@
 #include "fx_codec.hpp"
 #include "fx_launch.h"
 #include "fx_traffic.h"
+#include "fx_frontplan.h"
 
 namespace {
 
@@ -115,7 +116,6 @@ static bool pinned_device_ptr(const void *p, const void **dev, uintptr_t align_m
 inline unsigned iq_sample_bytes(int fmt) { return fmt == FXRX_IQ_FC32 ? 8u : fmt == FXRX_IQ_SC16 ? 4u : fmt == FXRX_IQ_SC8 ? 2u : 0u; }
 constexpr unsigned kMaxDepth = 32;
 constexpr unsigned kStateRing = kMaxDepth + 3;      // FxStreamState records per stream: one per block in flight and then some
-constexpr uint32_t kRepairCap = 256;                // frame-table slots per stream for walks done by the chain kernel
 
 struct StreamState {
     float2 *carry[3] = { nullptr, nullptr, nullptr };   // tails, right-aligned: block b reads carry[b % 3], writes carry[(b + 1) % 3]
@@ -331,12 +331,6 @@ int upload_tables(fxrx_ctx_s *c)
     HIP_OK(hipMemcpy(c->d_tables, t.get(), sizeof(FxTables), hipMemcpyHostToDevice));
     return 0;
 }
-
-// frame-table slots per walk job: the densest legal traffic is a header-only frame (618 samples) after the other.  (Should a
-// table fill up all the same -- FX_EXIT_TABLE_FULL -- the full-size chain kernel continues the segment.)
-// Densest possible traffic: a flexframe is at least ~630 samples long (preamble, header, tail), so flex_rx finds at most one frame
-// per 600 samples; the bare detector (frame_detector_cc) can fire again on the very next hop, 256 samples on.
-inline uint32_t seg_frames_cap(uint64_t seg, bool detect) { return (uint32_t)std::min<uint64_t>(seg / (detect ? 256 : 600) + 8, 4000); }
 
 int alloc_carry(StreamState &S, int64_t cap)
 {
@@ -636,199 +630,152 @@ static void mark_noskip(fxrx_ctx_s *c, const Slot &sl, const std::vector<uint32_
 enum { kChainFast = 0, kChainFull = 1, kChainDone = 2 };
 static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t chain_st = nullptr, bool may_defer = false);
 
-// ---- enqueue the whole kernel chain of the block in `sl` (descriptors are rebuilt: a replay calls this again) ----
-static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
+// ---- enqueue the whole kernel chain of the block in `sl` (descriptors are rebuilt: a replay calls this again), as five steps ----
+// what the steps hand on: the block's plan and the host copies of the descriptors it becomes
+struct FrontBuild {
+    FrontPlan plan;
+    std::vector<FxWalkJob> jobs; std::vector<FxStreamDesc> sds;
+    // job lists: speculative walkers in launch order | true walkers of continuing streams | speculative jobs the pre-lock scan takes
+    std::vector<uint32_t> early, late, spec;
+    size_t desc_bytes = 0;
+};
+
+// 1. the plan (fx_frontplan.h), from what the context and the block's snapshot say; its capacities go to the slot
+static int plan_front(const fxrx_ctx_s *c, Slot &sl, FrontPlan &plan)
+{
+    const unsigned NS = c->cfg.n_streams;
+    FrontKnobs k;
+    k.detect = c->cfg.mode == FXRX_MODE_DETECTOR; k.depth = c->depth; k.n_cus = c->n_cus; k.walk_per_cu = c->walk_per_cu;
+    k.segment_len = c->cfg.segment_len; k.taper = c->taper; k.prescan = c->prescan; k.prescan_hops = c->prescan_hops;
+    k.batch_viterbi = c->batch_viterbi; k.soft_decision = c->cfg.soft_decision != 0; k.vb_blk_force = c->vb_blk_force;
+    std::vector<StreamIn> in(NS);
+    for (unsigned s = 0; s < NS; s++) in[s] = StreamIn{ sl.n[s], !sl.snap[s].fresh_start, sl.snap[s].carry_bound };
+    plan = front_plan(in, c->traffic, k);
+    const FrontCaps &cap = plan.caps;
+    sl.NJ = plan.cuts.size();
+    sl.frame_slots = cap.frame_slots; sl.chain_cap = cap.chain_slots; sl.run_cap = cap.run_cap; sl.mf_cap = cap.mf_cap;
+    sl.sym_cap = cap.sym_cap; sl.byte_cap = cap.byte_cap; sl.dw_cap = cap.dw_cap; sl.out_cap = cap.out_cap;
+    sl.vb_blk = cap.vb_blk; sl.vb_cap = cap.vb.vb_cap; sl.vb_dw_words = cap.vb.vb_dw_words; sl.vb_slots_alloc = cap.vb.vb_slots_alloc;
+    sl.ps_hops = plan.ps_hops; sl.ps_words = prescan_words(plan.ps_hops); sl.ps_taken = sl.ps_fallback = 0;
+    if (cap.too_large) { set_err("fxrx_submit: batch too large for 32-bit arena offsets"); return FXRX_ERR_ARG; }
+    return 0;
+}
+
+// 2. the cuts as FxWalkJob and FxStreamDesc records -- everything that points into the context's or the block's memory --, the job lists,
+// and the layout of the descriptor arena
+static void build_descriptors(const fxrx_ctx_s *c, Slot &sl, FrontBuild &fb)
 {
     const unsigned NS = c->cfg.n_streams;
     const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR;
     const uint64_t b = sl.seq;
-    hipStream_t st = sl.st;
-    const double tp0 = g_prof_on ? prof_now() : 0.0;
-
-    // hops of every speculative job that fx_prescan_kernel scans ahead of the walkers (0: no such launch): a mean frame spacing
-    // of the last collected block plus two hops -- a segment start falls anywhere in a frame --, whole chunks
-    uint32_t ps_K = 0;
-    if (c->prescan && !detect) {
-        if (c->prescan_hops >= 0) ps_K = (uint32_t)c->prescan_hops;             // (as given: the last chunk may be a short one)
-        else {
-            ps_K = c->traffic.frames ? (uint32_t)std::min<uint64_t>(128, std::max<uint64_t>(16, c->traffic.samples / c->traffic.frames / FX_HOP + 2)) : 64u;
-            ps_K = (ps_K + FX_PRESCAN_CHUNK - 1) / FX_PRESCAN_CHUNK * FX_PRESCAN_CHUNK;
-        }
-    }
-
-    // ---- 1. segments ----
-    uint64_t seg = c->cfg.segment_len;
-    if (seg == 0) {
-        uint64_t tot = 0;
-        for (unsigned s = 0; s < NS; s++) tot += sl.n[s];
-        // Walker workgroups resident at once: two per CU for the flex_rx instance (4 waves x 256 VGPRs each), two for the
-        // leaner detector-only instance.  One block at a time (latency): little work -> a single round of workgroups with a
-        // small margin (the kernel then lasts as long as its slowest segment); lots of work -> ~4 rounds so that uneven
-        // segments even out.  Several blocks in flight (throughput): every segment start costs a speculative walker a
-        // pre-lock scan of half a frame on average -- about as much as two frames' worth of real work -- and the chip is
-        // kept busy by the other blocks anyway, so fewer, longer segments: down to one workgroup per two CUs.
-        const uint64_t slots = (uint64_t)c->n_cus * c->walk_per_cu;
-        // (about three blocks' walkers overlap at any time: keep that many workgroups' worth of segments between them)
-        // (Measured again with the tails ganged, DESIGN.md section 6, pre-scan log: twice as many segments, down to one workgroup per
-        // CU -- 6 x slots / depth, 256 at depth 12 -- give the higher rates on config 2.  Why they do is not established.)
-        if (c->depth > 1 && !detect) seg = tot / std::max<uint64_t>(std::max<uint64_t>(1, c->n_cus), std::min<uint64_t>(slots, 6 * slots / c->depth));
-        else if (tot / slots < 131072) seg = tot / (slots - slots / 16);
-        else seg = std::max<uint64_t>(tot / (4 * slots), 65536);
-        seg = std::max<uint64_t>(seg, 32768); seg = std::min<uint64_t>(seg, 1u << 20);
-    }
-    seg = std::max<uint64_t>(seg, 4096);
-    // (detector-only mode with more jobs than fit on the chip at once: config 3 alone 28.7 -> 24.7 ms; the flex_rx walker, whose launches
-    // overlap the rest of the chain, gains nothing from it: configs 4, 5 and 2 measured equal or worse)
-    float taper = c->taper;
-    if (taper < 0.0f) {
-        uint64_t tot = 0;
-        for (unsigned s = 0; s < NS; s++) tot += sl.n[s];
-        taper = (detect && tot / seg > 4ull * (uint64_t)c->n_cus) ? 0.75f : 0.0f;
-    }
-    std::vector<FxWalkJob> jobs; std::vector<uint32_t> early, late; std::vector<FxStreamDesc> sds(NS);
-    uint32_t frame_slots = 0, chain_slots = 0; uint64_t n_total = 0, carry_total = 0;
+    const FrontPlan &plan = fb.plan;
+    fb.jobs.reserve(plan.cuts.size()); fb.sds.resize(NS);
     for (unsigned s = 0; s < NS; s++) {
-        StreamState &S = c->st[s]; const StreamSnap &sn = sl.snap[s];
+        const StreamState &S = c->st[s]; const StreamSnap &sn = sl.snap[s]; const StreamCaps &sc = plan.caps.streams[s];
         const int64_t ns = (int64_t)sl.n[s];
         const bool cont = !sn.fresh_start;
-        FxStreamDesc &sd = sds[s];
+        FxStreamDesc &sd = fb.sds[s];
         sd.x = sl.x[s]; sd.xa_end = cont ? S.carry[b % 3] + S.carry_cap : nullptr; sd.n = ns;
-        sd.first_job = (uint32_t)jobs.size();
+        sd.first_job = plan.first_cut[s]; sd.n_jobs = plan.first_cut[s + 1] - plan.first_cut[s];
         sd.state_in = cont ? c->d_state + ((b + kStateRing - 1) % kStateRing) * NS + s : nullptr;
         sd.state_out = c->d_state + (b % kStateRing) * NS + s;
         sd.state_out_host = c->h_state + (b % kStateRing) * NS + s;
         sd.carry_out_end = S.carry[(b + 1) % 3] + S.carry_cap; sd.carry_cap = S.carry_cap;
         sd.abs_base = sn.tot0;
-        // a continuing stream's true walker only has to reach its first hand-off, so its own segment is short: it starts
-        // late (after the previous block's chain kernel) while the speculative walkers of the other segments are long under way
-        int64_t p = 0; bool first = true;
-        const int64_t seg0 = cont ? (int64_t)std::min<uint64_t>(seg, 8192) : (int64_t)seg;
-        // Tapered segments: what is launched last is short.  A walker workgroup alone on its CU runs at well under half the rate four
-        // of them reach together (tools/dev/dev_walk_timeline.py), so the last jobs of a launch set the length of its drain.
-        const int64_t p_t = cont ? std::min<int64_t>(ns, seg0) : 0;                       // the taper covers [p_t, ns)
-        const int64_t k_t = taper > 0.0f ? std::max<int64_t>(1, ((ns - p_t) + (int64_t)seg / 2) / (int64_t)seg) : 0;
-        int64_t i_t = 0;
-        while (first || p < ns) {
+        sd.chain_base = sc.chain_base; sd.chain_cap = sc.chain_cap; sd.repair_base = sc.repair_base; sd.repair_cap = kRepairCap;
+        for (uint32_t ji = plan.first_cut[s]; ji < plan.first_cut[s + 1]; ji++) {
+            const Cut &cut = plan.cuts[ji];
+            const bool true_walker = cut.first && cont;       // starts from the state the previous block leaves, behind that block's chain kernel
             FxWalkJob j{};
-            j.x = sd.x; j.xa_end = sd.xa_end; j.n = ns; j.start = p;
-            j.stop = std::min<int64_t>(ns, p + (first ? seg0 : (int64_t)seg));
-            if (ns - j.stop < (int64_t)seg / 2) j.stop = ns;          // fold a short last segment in
-            if (k_t > 1 && p >= p_t) {
-                // piece i of k: boundary at the integral of the falling line (1 + t) -> (1 - t)
-                const double u = (double)(i_t + 1) / (double)k_t;
-                const int64_t e = p_t + (int64_t)((double)(ns - p_t) * (u * (1.0 + taper) - taper * u * u));
-                j.stop = (i_t + 1 >= k_t) ? ns : std::min<int64_t>(ns, std::max<int64_t>(p + 4096, e & ~(int64_t)255));
-                i_t++;
-            }
-            j.fresh = 1u; j.floor = p;
+            j.x = sd.x; j.xa_end = sd.xa_end; j.n = ns; j.start = cut.start; j.stop = cut.stop;
+            j.fresh = 1u; j.floor = cut.start;
             j.mode = detect ? FX_MODE_DETECT : FX_MODE_FLEXRX;
             j.handoff = j.stop < ns ? 1u : 0u;
-            j.prelock = first ? 0u : 1u;
-            j.frame_base = frame_slots; j.max_frames = seg_frames_cap((uint64_t)(j.stop - j.start) + (first && cont ? (uint64_t)sn.carry_bound : 0u), detect);
-            frame_slots += j.max_frames;
+            j.prelock = cut.first ? 0u : 1u;
+            j.frame_base = plan.caps.frame_base[ji]; j.max_frames = cut.max_frames;
             j.threshold = c->cfg.threshold;
             j.no_skip = (detect || !c->skip_seek || sl.force_noskip || sn.noskip) ? 1u : 0u;
-            j.state_in = (first && cont) ? sd.state_in : nullptr;
+            j.state_in = true_walker ? sd.state_in : nullptr;
             j.stream = s; j.verify_per = c->traffic.verify_per; j.eq = (!detect && c->cfg.equalizer) ? 1u : 0u;
-            (first && cont ? late : early).push_back((uint32_t)jobs.size());
-            jobs.push_back(j);
-            p = j.stop; first = false;
-            if (p >= ns) break;
+            (true_walker ? fb.late : fb.early).push_back(ji);
+            fb.jobs.push_back(j);
         }
-        sd.n_jobs = (uint32_t)jobs.size() - sd.first_job;
-        sd.chain_base = chain_slots; sd.chain_cap = (uint32_t)((uint64_t)(ns + (cont ? sn.carry_bound : 0)) / (detect ? 256u : 600u) + 8u);
-        chain_slots += sd.chain_cap;
-        n_total += (uint64_t)ns; carry_total += cont ? (uint64_t)sn.carry_bound : 0u;
     }
-    for (unsigned s = 0; s < NS; s++) { sds[s].repair_base = frame_slots; sds[s].repair_cap = kRepairCap; frame_slots += kRepairCap; }
-    if (taper > 0.0f)
-        std::stable_sort(early.begin(), early.end(), [&](uint32_t a, uint32_t b2) { return jobs[a].stop - jobs[a].start > jobs[b2].stop - jobs[b2].start; });
-    const size_t NJ = jobs.size();
-    sl.NJ = NJ; sl.n_early = early.size(); sl.n_late = late.size(); sl.any_late = !late.empty();
-    sl.frame_slots = frame_slots; sl.chain_cap = chain_slots;
-    sl.run_cap = (uint32_t)std::min<uint64_t>((n_total + carry_total) / FX_HOP + 2 * NJ + 1024, 0x7fffffffu);
-    const uint64_t span = n_total + carry_total;                     // samples the block's frames can occupy
-    sl.sym_cap = span / 2 + 8ull * chain_slots + 64;
-    sl.byte_cap = (span / 2) * 3 / 4 + 48ull * chain_slots + 64;
-    sl.dw_cap = detect ? 0 : (span / 2) * 6 + 200ull * chain_slots + 64;
-    sl.out_cap = (span / 2) * 3 / 4 + 16ull * chain_slots + 64;
-    sl.mf_cap = (uint32_t)std::min<uint64_t>(span / 2 / 1024 + chain_slots + 16, 0x7fffffffu);
-    // batch Viterbi: trellis steps per block from the traffic of the last block.  The forward pass is arithmetic bound, three
-    // waves to a SIMD: some six waves per SIMD spread evenly over the chip, fewer and the slowest SIMD sets the time; blocks
-    // shorter than a couple of warm-ups waste their work.  (Longer blocks with several blocks in flight -- less warm-up, the
-    // chip is full anyway -- measured worse: 192 steps 30.0, 256: 29.8, 384: 28.8, 512: 27.6, 1024: 24.6 Gsamples/s on config 2.)
-    {
-        const uint64_t want_items = 64ull * 4ull * (uint64_t)c->n_cus * 6ull;
-        sl.vb_blk = (detect || c->cfg.soft_decision || !c->batch_viterbi) ? 0u
-                  : (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(192, ((c->traffic.vb_steps / want_items + 63) / 64) * 64));
+    if (plan.taper > 0.0f) longest_first(fb.early, plan.cuts);
+    if (plan.ps_hops) for (uint32_t ji : fb.early) if (fb.jobs[ji].prelock && fb.jobs[ji].mode == FX_MODE_FLEXRX) {
+        FxWalkJob &j = fb.jobs[ji];
+        j.prescan_words = sl.ps_words; j.prescan_hops = fx_prescan_valid_hops(j.start, j.stop, j.n, plan.ps_hops);     // (j.prescan: pack_descriptors, once its table is reserved)
+        fb.spec.push_back(ji);
     }
-    if (sl.vb_blk && c->vb_blk_force) sl.vb_blk = c->vb_blk_force;
-    // (arena: 1.5 trellis steps per sample of span -- QPSK r1/2 has 0.47, QAM16 r2/3 1.17 -- or what the last block's traffic
-    // asked for plus a quarter, in work items of the block length chosen above; frames whose work items do not fit are
-    // decoded by the wave-per-frame kernel, and the next block's arena is larger.  Sized in steps, not items, so that a
-    // change of block length does not reallocate gigabytes.)
-    {
-        const uint64_t steps_cap = std::min<uint64_t>(std::max<uint64_t>(span + span / 2, c->traffic.vb_steps + c->traffic.vb_steps / 4), 4 * span);
-        sl.vb_cap = sl.vb_blk ? (uint32_t)((steps_cap / sl.vb_blk + 2048 + 127) & ~127ull) : 128u;
-        // (the decision-word arena itself: the same number of words whatever the block length -- the 2048 extra work items
-        // priced at the longest block --, or a change of block length by one notch would reallocate it, 1.5 x larger)
-        sl.vb_dw_words = sl.vb_blk ? std::max<uint64_t>((uint64_t)sl.vb_cap * sl.vb_blk, steps_cap + 2176ull * 4096ull) : 0;
-        sl.vb_slots_alloc = sl.vb_blk ? std::max<uint64_t>(sl.vb_cap, steps_cap / 192 + 2176) : 128;     // likewise the per-item arenas: priced at the shortest block
-    }
-    if (sl.sym_cap >= (1ull << 32) || sl.dw_cap >= (1ull << 32)) { set_err("fxrx_submit: batch too large for 32-bit arena offsets"); return FXRX_ERR_ARG; }
-
-    const double tp1 = g_prof_on ? prof_now() : 0.0;
-    // ---- 2. memory ----
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    sl.n_early = fb.early.size(); sl.n_late = fb.late.size(); sl.any_late = !fb.late.empty(); sl.ps_jobs = (uint32_t)fb.spec.size();
     // (the job lists: early | late, NJ entries together, and behind them the speculative jobs the pre-lock scan takes)
-    const size_t o_list = up16(NJ * sizeof(FxWalkJob)), o_streams = o_list + up16(2 * NJ * sizeof(uint32_t)), desc_bytes = o_streams + up16(NS * sizeof(FxStreamDesc));
-    sl.o_list = o_list; sl.o_streams = o_streams;
-    std::vector<uint32_t> spec;
-    if (ps_K) for (uint32_t ji : early) if (jobs[ji].prelock && jobs[ji].mode == FX_MODE_FLEXRX) spec.push_back(ji);
-    sl.ps_jobs = (uint32_t)spec.size(); sl.ps_hops = ps_K; sl.ps_words = (ps_K + FX_PRESCAN_CHUNK - 1) / FX_PRESCAN_CHUNK; sl.ps_taken = sl.ps_fallback = 0;
-    if (!spec.empty()) {
-        if (sl.d_prescan.reserve(spec.size() * sl.ps_words)) return FXRX_ERR_HIP;
-        for (size_t i = 0; i < spec.size(); i++) {
-            FxWalkJob &j = jobs[spec[i]];
-            j.prescan = sl.d_prescan.p + i * sl.ps_words; j.prescan_words = sl.ps_words;
-            j.prescan_hops = fx_prescan_valid_hops(j.start, j.stop, j.n, ps_K);
-        }
-    }
-    if (sl.hp_desc.reserve(desc_bytes) || sl.d_desc.reserve(desc_bytes) || sl.d_wres.reserve(NJ + NS) || sl.d_frames.reserve(frame_slots) ||
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    sl.o_list = up16(sl.NJ * sizeof(FxWalkJob)); sl.o_streams = sl.o_list + up16(2 * sl.NJ * sizeof(uint32_t));
+    fb.desc_bytes = sl.o_streams + up16(NS * sizeof(FxStreamDesc));
+}
+
+// 3. every buffer of the block at the capacity the plan gives it (buffers only ever grow)
+static int reserve_block(fxrx_ctx_s *c, Slot &sl, const FrontBuild &fb)
+{
+    const unsigned NS = c->cfg.n_streams;
+    const size_t NJ = sl.NJ;
+    const uint32_t chain_slots = sl.chain_cap;
+    const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR, flex = !detect, syms = c->cfg.want_framesyms != 0, soft = flex && c->cfg.soft_decision;
+    // pre-lock scan table; descriptors, walk and chain tables, payload jobs and lists
+    if (!fb.spec.empty() && sl.d_prescan.reserve(fb.spec.size() * sl.ps_words)) return FXRX_ERR_HIP;
+    if (sl.hp_desc.reserve(fb.desc_bytes) || sl.d_desc.reserve(fb.desc_bytes) || sl.d_wres.reserve(NJ + NS) || sl.d_frames.reserve(sl.frame_slots) ||
         sl.d_runs.reserve(sl.run_cap) || sl.d_req.reserve(2 * NJ + 16) || sl.d_cstat.reserve(NS) || sl.d_chain.reserve(chain_slots) || sl.d_chain_count.reserve(NS) || sl.d_stream_base.reserve(NS + 1) ||
         sl.d_pjobs.reserve(chain_slots) || sl.h_recs.reserve(chain_slots) || sl.d_mf_job.reserve(sl.mf_cap) || sl.d_mf_c0.reserve(sl.mf_cap) ||
         sl.d_pll_list.reserve(sl.list_cap()) || sl.d_dec_list.reserve(kDecLists * (size_t)sl.list_cap())) return FXRX_ERR_HIP;
-    if (!detect && (sl.d_symraw.reserve(sl.sym_cap) || sl.d_hard.reserve(sl.sym_cap + 64) ||
-                    sl.d_bufA.reserve(sl.byte_cap + 256) || sl.d_bufB.reserve(sl.byte_cap + 256) || sl.d_dw.reserve(sl.dw_cap) || sl.h_out.reserve(sl.out_cap))) return FXRX_ERR_HIP;
-    if (!detect && c->cfg.want_framesyms && sl.h_framesyms.reserve(sl.sym_cap)) return FXRX_ERR_HIP;
-    if (detect && c->cfg.want_framesyms) {
-        // aligned windows: one 4 KB slot per detection the block is expected to hold -- the last collected block's count plus a margin, as
-        // for the other lists only the device can count (one slot per possible detection would be twice the input, in pinned memory); a
-        // block that holds more is completed when it is collected (finish_windows)
-        sl.win_reserved = c->detwin_reserve ? std::min(chain_slots, c->detwin_reserve) : with_margin(c->traffic.frames, chain_slots);
+    // flex_rx only: the payload arenas
+    if (flex && (sl.d_symraw.reserve(sl.sym_cap) || sl.d_hard.reserve(sl.sym_cap + 64) ||
+                 sl.d_bufA.reserve(sl.byte_cap + 256) || sl.d_bufB.reserve(sl.byte_cap + 256) || sl.d_dw.reserve(sl.dw_cap) || sl.h_out.reserve(sl.out_cap))) return FXRX_ERR_HIP;
+    // frame symbols for the host
+    if (flex && syms && sl.h_framesyms.reserve(sl.sym_cap)) return FXRX_ERR_HIP;
+    // detector windows (a block that holds more than were reserved is completed when it is collected: finish_windows)
+    if (detect && syms) {
+        sl.win_reserved = window_slots(c->traffic, chain_slots, c->detwin_reserve);
         if (sl.h_win.reserve((size_t)sl.win_reserved * FX_NFFT) || sl.h_wintail.reserve(2 * (size_t)NS * FX_NFFT) || sl.h_winflag.reserve(1)) return FXRX_ERR_HIP;
         *sl.h_winflag.p = 0u;
     }
+    // the plan kernels' workspace: zeroed once, they leave it zero
     if (!sl.d_plan_ws.p) {
         if (sl.d_plan_ws.reserve(fx_plan_ws_words())) return FXRX_ERR_HIP;
-        HIP_OK(hipMemsetAsync(sl.d_plan_ws.p, 0, fx_plan_ws_words() * sizeof(uint32_t), st));
+        HIP_OK(hipMemsetAsync(sl.d_plan_ws.p, 0, fx_plan_ws_words() * sizeof(uint32_t), sl.st));
     }
+    // batch Viterbi (the item list also without the path)
     if (sl.d_vb_items.reserve(2 * (size_t)sl.vb_slots_alloc) ||
         (sl.vb_blk && (sl.d_vb_vec.reserve(128 * (size_t)sl.vb_slots_alloc) || sl.d_vb_dw.reserve((size_t)sl.vb_dw_words) || sl.d_vb_st.reserve(sl.vb_slots_alloc)))) return FXRX_ERR_HIP;
-    if (!detect && c->cfg.soft_decision && (sl.d_soft.reserve(8 * sl.byte_cap) || (c->cfg.want_framesyms && sl.h_soft.reserve(8 * sl.byte_cap)))) return FXRX_ERR_HIP;
+    // soft values
+    if (soft && (sl.d_soft.reserve(8 * sl.byte_cap) || (syms && sl.h_soft.reserve(8 * sl.byte_cap)))) return FXRX_ERR_HIP;
 #ifdef FX_STAMPS
-    if (!detect && sl.d_pres.reserve(chain_slots)) return FXRX_ERR_HIP;
+    if (flex && sl.d_pres.reserve(chain_slots)) return FXRX_ERR_HIP;
 #endif
-    std::memcpy(sl.hp_desc.p, jobs.data(), NJ * sizeof(FxWalkJob));
-    uint32_t *hl = reinterpret_cast<uint32_t *>(sl.hp_desc.p + o_list);
-    if (!early.empty()) std::memcpy(hl, early.data(), early.size() * sizeof(uint32_t));
-    if (!late.empty()) std::memcpy(hl + early.size(), late.data(), late.size() * sizeof(uint32_t));
-    if (!spec.empty()) std::memcpy(hl + NJ, spec.data(), spec.size() * sizeof(uint32_t));
-    std::memcpy(sl.hp_desc.p + o_streams, sds.data(), NS * sizeof(FxStreamDesc));
-    const uint32_t *d_list = sl.job_list();
+    return 0;
+}
 
-    const double tp2 = g_prof_on ? prof_now() : 0.0;
-    // ---- 3. the chain, front part: walkers and seek verification ----
+// 4. the descriptor arena in page-locked memory: [FxWalkJob x NJ | job lists | FxStreamDesc x NS]
+static void pack_descriptors(Slot &sl, FrontBuild &fb)
+{
+    const size_t NJ = sl.NJ;
+    for (size_t i = 0; i < fb.spec.size(); i++) fb.jobs[fb.spec[i]].prescan = sl.d_prescan.p + i * sl.ps_words;
+    std::memcpy(sl.hp_desc.p, fb.jobs.data(), NJ * sizeof(FxWalkJob));
+    uint32_t *hl = reinterpret_cast<uint32_t *>(sl.hp_desc.p + sl.o_list);
+    if (!fb.early.empty()) std::memcpy(hl, fb.early.data(), fb.early.size() * sizeof(uint32_t));
+    if (!fb.late.empty()) std::memcpy(hl + fb.early.size(), fb.late.data(), fb.late.size() * sizeof(uint32_t));
+    if (!fb.spec.empty()) std::memcpy(hl + NJ, fb.spec.data(), fb.spec.size() * sizeof(uint32_t));
+    std::memcpy(sl.hp_desc.p + sl.o_streams, fb.sds.data(), fb.sds.size() * sizeof(FxStreamDesc));
+}
+
+// 5. the chain, front part: walkers and seek verification.  *chain_st: the stream the chain kernel goes to
+static int enqueue_front(fxrx_ctx_s *c, Slot &sl, const FrontBuild &fb, hipStream_t *chain_st)
+{
+    const bool detect = c->cfg.mode == FXRX_MODE_DETECTOR;
+    const uint64_t b = sl.seq;
+    const size_t NJ = sl.NJ;
+    const unsigned n_early = (unsigned)fb.early.size(), n_late = (unsigned)fb.late.size(), n_spec = (unsigned)fb.spec.size();
+    hipStream_t st = sl.st;
+    const uint32_t *d_list = sl.job_list();
     // (integer IQ first: raw copy where the source is not readable from the device, then fx_ingest_kernel into the staging buffer
     // the descriptors point at.  Launched here, behind every check and reservation of the block; a replay finds the list empty.)
     if (!sl.ingest.empty()) {
@@ -840,21 +787,21 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
             HIP_OK(fx_launch_ingest(st, sl.ingest_fmt, src, sl.d_in[j.stream].p, (size_t)j.n, sl.ingest_scale, (unsigned)c->n_cus));
         }
     }
-    HIP_OK(fx_launch_upload(st, sl.hp_desc.p, sl.d_desc.p, desc_bytes, (unsigned)c->n_cus));     // (descriptors: our own page-locked buffer)
+    HIP_OK(fx_launch_upload(st, sl.hp_desc.p, sl.d_desc.p, fb.desc_bytes, (unsigned)c->n_cus));     // (descriptors: our own page-locked buffer)
     const int tl = c->timing_level >= 0 ? c->timing_level : (c->depth > 1 ? 0 : 2);      // stage events: see fxrx_set_timing
     sl.timing_level = tl;
     // (the speculative jobs' pre-lock scan: part of the walk stage, in front of every walker launch that reads its table)
-    if (c->debug_walk_twice > 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, sl.jobs(), d_list + NJ, c->d_tables));
-    for (int rep = 0; rep < c->debug_walk_twice; rep++) HIP_OK(launch_walk(c, sl, st, d_list, (unsigned)early.size()));
+    if (c->debug_walk_twice > 0) HIP_OK(fx_launch_prescan(st, n_spec, sl.ps_words, sl.jobs(), d_list + NJ, c->d_tables));
+    for (int rep = 0; rep < c->debug_walk_twice; rep++) HIP_OK(launch_walk(c, sl, st, d_list, n_early));
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvStart], st));
-    if (c->debug_walk_twice <= 0) HIP_OK(fx_launch_prescan(st, (unsigned)spec.size(), sl.ps_words, sl.jobs(), d_list + NJ, c->d_tables));
-    HIP_OK(launch_walk(c, sl, st, d_list, (unsigned)early.size()));
+    if (c->debug_walk_twice <= 0) HIP_OK(fx_launch_prescan(st, n_spec, sl.ps_words, sl.jobs(), d_list + NJ, c->d_tables));
+    HIP_OK(launch_walk(c, sl, st, d_list, n_early));
     // the true walkers of continuing streams read the state the previous block's chain kernel leaves.  What the speculative
     // walkers skipped is verified before that wait -- it does not depend on the state --, so that the chain of dependencies
     // from one block's chain kernel to the next one's is just: true walkers, their few verification runs, chain kernel
     const bool verify = !detect && c->skip_seek && !sl.force_noskip;
     hipStream_t cst = st;                                     // the stream the rest of the front part and the chain kernel go to
-    if (!late.empty()) {
+    if (n_late) {
         if (verify) {
             HIP_OK(fx_launch_copy_u32(st, &sl.hdr_walk()->n_runs, &sl.hdr_walk()->runs_done));
             HIP_OK(launch_seekverify(c, sl, st, c->verify_per_cu * (unsigned)c->n_cus, 0u));
@@ -871,16 +818,32 @@ static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
         cst = c->st_chain;
         HIP_OK(hipStreamWaitEvent(cst, sl.ev[kEvHandover], 0));
         if (c->prev_chain) HIP_OK(hipStreamWaitEvent(cst, c->prev_chain, 0));
-        HIP_OK(launch_walk(c, sl, cst, d_list + early.size(), (unsigned)late.size()));
+        HIP_OK(launch_walk(c, sl, cst, d_list + n_early, n_late));
     }
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvWalk], cst));
     if (verify)
-        HIP_OK(launch_seekverify(c, sl, cst, late.empty() ? c->verify_per_cu * (unsigned)c->n_cus : (unsigned)std::min<size_t>((size_t)c->verify_per_cu * (size_t)c->n_cus, std::max<size_t>(64, 16 * late.size())), 1u));
+        HIP_OK(launch_seekverify(c, sl, cst, !n_late ? c->verify_per_cu * (unsigned)c->n_cus : (unsigned)std::min<size_t>((size_t)c->verify_per_cu * (size_t)c->n_cus, std::max<size_t>(64, 16 * (size_t)n_late)), 1u));
     if (tl >= 2) HIP_OK(hipEventRecord(sl.ev[kEvVerify], cst));
     // chain kernels run in block order in any case (they write the carry buffers in rotation); this one writes
     // carry[(b + 1) % 3], which the payload MF of block b - 2 may still be reading
-    if (late.empty() && c->prev_chain) HIP_OK(hipStreamWaitEvent(cst, c->prev_chain, 0));
+    if (!n_late && c->prev_chain) HIP_OK(hipStreamWaitEvent(cst, c->prev_chain, 0));
     if (c->carry_reader[(b + 1) % 3]) HIP_OK(hipStreamWaitEvent(cst, c->carry_reader[(b + 1) % 3], 0));
+    *chain_st = cst;
+    return 0;
+}
+
+static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
+{
+    const double tp0 = g_prof_on ? prof_now() : 0.0;
+    FrontBuild fb;
+    { const int r = plan_front(c, sl, fb.plan); if (r) return r; }
+    build_descriptors(c, sl, fb);
+    const double tp1 = g_prof_on ? prof_now() : 0.0;
+    { const int r = reserve_block(c, sl, fb); if (r) return r; }
+    pack_descriptors(sl, fb);
+    const double tp2 = g_prof_on ? prof_now() : 0.0;
+    hipStream_t cst = nullptr;
+    { const int r = enqueue_front(c, sl, fb, &cst); if (r) return r; }
     const double tp3 = g_prof_on ? prof_now() : 0.0;
     const int rb = enqueue_back(c, sl, kChainFast, cst, may_defer);
     if (g_prof_on) { const double tp4 = prof_now(); g_prof[1] += tp1 - tp0; g_prof[2] += tp2 - tp1; g_prof[3] += tp3 - tp2; g_prof[4] += tp4 - tp3; g_prof_n++; }
