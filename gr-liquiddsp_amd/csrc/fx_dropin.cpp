@@ -231,19 +231,19 @@ static bool sync_recreate(flexframesync q, const char *what)
     q->ctx = nc;
     return true;
 }
-// a decoder option of the liquid API: the new value is tried on a new context and kept only if that context could be made
-static int sync_set_value(flexframesync q, int fxrx_sync_s::*field, int value, const char *what)
+// a setting that lives in the context configuration: the new value is tried on a new context and kept only if that context could be made
+extern "C++" template <class T> static int sync_set_value(flexframesync q, T fxrx_sync_s::*field, T value, const char *what)
 {
     if (!q) return -1;
-    const int old = q->*field;
+    const T old = q->*field;
     q->*field = value;
     if (!sync_recreate(q, what)) { q->*field = old; return -1; }
     return 0;
 }
 static int sync_set_option(flexframesync q, int fxrx_sync_s::*field, int on, const char *what) { return sync_set_value(q, field, on ? 1 : 0, what); }
-void fxrx_sync_set_threshold(flexframesync q, float t) { if (!q) return; q->threshold = t; sync_recreate(q, "fxrx_sync_set_threshold"); }
-void fxrx_sync_set_equalizer(flexframesync q, int on) { if (!q) return; q->equalizer = on ? 1 : 0; sync_recreate(q, "fxrx_sync_set_equalizer"); }
-void fxrx_sync_set_soft(flexframesync q, int on) { if (!q) return; q->soft = on ? 1 : 0; sync_recreate(q, "fxrx_sync_set_soft"); }
+void fxrx_sync_set_threshold(flexframesync q, float t) { (void)sync_set_value(q, &fxrx_sync_s::threshold, t, "fxrx_sync_set_threshold"); }
+void fxrx_sync_set_equalizer(flexframesync q, int on) { (void)sync_set_option(q, &fxrx_sync_s::equalizer, on, "fxrx_sync_set_equalizer"); }
+void fxrx_sync_set_soft(flexframesync q, int on) { (void)sync_set_option(q, &fxrx_sync_s::soft, on, "fxrx_sync_set_soft"); }
 int fxrx_sync_set_soft_block(flexframesync q, int on) { return sync_set_option(q, &fxrx_sync_s::soft_block, on, "fxrx_sync_set_soft_block"); }
 // (in force while soft payload decoding and soft_block are on; turning it on without them is refused, as fxrx_create would)
 int fxrx_sync_set_soft_chain(flexframesync q, int on)

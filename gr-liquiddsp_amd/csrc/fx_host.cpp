@@ -1,9 +1,12 @@
 // fx_host.cpp -- host runtime of libfxrx.so: device tables, block descriptors, the stream-ordered kernel chain of a
 // block, result marshalling and the C ABI declared in include/fxrx.h.
 //
-// A block (one fxrx_submit: new samples of every stream) is ONE chain of kernels enqueued on the block's own HIP stream;
-// the host never waits between them:
+// A block (one fxrx_submit: new samples of every stream) is submitted in three steps (submit_block).  Stage: the block's snapshot of every
+// stream, its plan (fx_frontplan.h), a route for every stream's input (fx_ingestplan.h), its descriptors -- on the host, into the block's
+// slot.  Reserve: every buffer; a submit that fails fails up to here, the context untouched and nothing enqueued.  Enqueue: ONE chain of
+// kernels on the block's own HIP stream, and only then does the context move on; the host never waits between the kernels:
 //
+//   input (host IQ, integer IQ)         -- a copy and / or fx_upload_kernel / fx_ingest_kernel per stream, into the slot's staging buffers
 //   pre-lock scan (flex_rx)             -- fx_prescan_kernel: the first hops of every speculative segment, all at once
 //   walkers (speculative segments)      -- fx_walk_kernel, launched at once
 //   seek verification, phase 0          -- fx_seekverify_kernel over the runs those walkers emitted (continuing streams only)
@@ -49,6 +52,7 @@
 #include "fx_launch.h"
 #include "fx_traffic.h"
 #include "fx_frontplan.h"
+#include "fx_ingestplan.h"
 
 namespace {
 
@@ -101,19 +105,16 @@ template <class T> struct PinBuf {
     ~PinBuf() { if (p) (void)hipHostFree(p); }
 };
 
-constexpr size_t kUploadKernelMax = 64u << 20;      // host blocks up to this size are uploaded by fx_upload_kernel when their memory is page-locked
-// is p page-locked host memory the device can read, and at which address?  (align_mask: float IQ is fetched in 8-byte pieces;
-// integer IQ may sit at any multiple of its sample size: 0)
-static bool pinned_device_ptr(const void *p, const void **dev, uintptr_t align_mask = 7u)
+// is p page-locked host memory the device can read, and at which address?
+static bool pinned_device_ptr(const void *p, const void **dev)
 {
-    if (!p || (reinterpret_cast<uintptr_t>(p) & align_mask)) return false;
+    if (!p) return false;
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }     // (pageable memory: not an error here)
     if (a.type != hipMemoryTypeHost || !a.devicePointer) return false;
     *dev = a.devicePointer;
     return true;
 }
-inline unsigned iq_sample_bytes(int fmt) { return fmt == FXRX_IQ_FC32 ? 8u : fmt == FXRX_IQ_SC16 ? 4u : fmt == FXRX_IQ_SC8 ? 2u : 0u; }
 constexpr unsigned kMaxDepth = 32;
 constexpr unsigned kStateRing = kMaxDepth + 3;      // FxStreamState records per stream: one per block in flight and then some
 
@@ -126,8 +127,9 @@ struct StreamState {
     unsigned noskip_left = 0;               // blocks this stream is still walked with the exact detector on every hop (a skipped hop fired recently; survives a reset)
 };
 
-// integer IQ of one stream, to be converted into the slot's float staging buffer in front of the block's chain
-struct IngestJob { unsigned stream = 0; const void *dev_src = nullptr; const void *host_src = nullptr; uint64_t n = 0; };
+// new samples of one stream on their way into the slot's float staging buffer, in front of the block's chain (fx_ingestplan.h).
+// src: where the route's first step reads -- the caller's pointer, or its device-visible address where a kernel reads host memory
+struct IngestJob { unsigned stream = 0; IngestRoute route = kRouteNone; const void *src = nullptr; uint64_t n = 0; };
 
 // what a block needs to know about a stream at submit time (kept for a replay)
 struct StreamSnap { int64_t tot0 = 0; bool fresh_start = true; int64_t carry_bound = 0; bool noskip = false; };
@@ -155,7 +157,7 @@ struct Slot {
     std::vector<const float2 *> x; std::vector<uint64_t> n; std::vector<StreamSnap> snap;
     std::vector<DevBuf<float2>> d_in;        // staging of host inputs (and of integer inputs, host or device, after their conversion)
     std::vector<DevBuf<uint8_t>> d_raw;      // integer IQ that reaches the device through the copy engines (pageable memory, very large blocks)
-    std::vector<IngestJob> ingest; int ingest_fmt = FXRX_IQ_FC32; float ingest_scale = 0.0f;   // conversions enqueue_block still has to launch
+    std::vector<IngestJob> ingest; int ingest_fmt = FXRX_IQ_FC32; float ingest_scale = 0.0f;   // uploads and conversions enqueue_front still has to launch
     // descriptor arena, one upload: [FxWalkJob x NJ | job lists | FxStreamDesc x NS]
     PinBuf<uint8_t> hp_desc; DevBuf<uint8_t> d_desc;
     size_t NJ = 0, n_early = 0, n_late = 0, o_list = 0, o_streams = 0;
@@ -259,10 +261,7 @@ struct fxrx_ctx_s {
     unsigned noskip_left = 0;            // blocks still to be walked with the exact detector on every hop (after a verification failure)
     unsigned debug_fail_submit = 0, debug_fail_collect = 0;   // tests (fxrx_debug_fail): the next n submits / collects report a failure
     uint64_t discarded = 0;              // blocks dropped by a failing fxrx_collect (see discard_inflight)
-    // FXRX_INGEST_KERNEL_MAX: integer IQ in page-locked memory up to this many raw bytes per stream and block is read over the bus by
-    // fx_ingest_kernel itself (no copy call on the host thread); above it copy engine + device pass.  Measured:
-    // the two routes are equal within the spread up to 1 MB raw, and the kernel read is slower from 2 MB on.
-    size_t ingest_kernel_max = 1u << 20;
+    IngestLimits ingest_limits;          // sizes up to which a kernel reads page-locked host IQ itself (FXRX_INGEST_KERNEL_MAX: the integer formats')
     float iq_scale[3] = { 1.0f, 1.0f / 32768.0f, 1.0f / 128.0f };   // fxrx_set_iq_scale, indexed by FXRX_IQ_*
     // FXRX_TAIL_GANG: tails per gang launch (1: off; at most FX_GANG_MAX).  The PLL and fx_vbpre_kernel hold a hardware queue for as
     // long with one block's frames as with four blocks', and queue time is what bounds the pipeline.
@@ -412,9 +411,10 @@ static int make_slot(fxrx_ctx_s *c)
     HIP_OK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
     for (auto &e : s->ev) HIP_OK(hipEventCreate(&e));
     s->index = (unsigned)c->slots.size();
-    if (s->h_hdr.reserve(1) || s->d_hdr.reserve(2)) return FXRX_ERR_HIP;
+    if (s->h_hdr.reserve(1) || s->d_hdr.reserve(2) || s->d_plan_ws.reserve(fx_plan_ws_words())) return FXRX_ERR_HIP;
     std::memset(s->h_hdr.p, 0, sizeof(FxBlockHdr));
     HIP_OK(hipMemset(s->d_hdr.p, 0, 2 * sizeof(FxBlockHdr)));     // (fx_plan_kernel zeroes the counters again after every block)
+    HIP_OK(hipMemset(s->d_plan_ws.p, 0, fx_plan_ws_words() * sizeof(uint32_t)));     // (the plan kernels leave their workspace zero)
     c->slots.push_back(std::move(s));
     return 0;
 }
@@ -433,7 +433,7 @@ void fxrx_destroy(fxrx_ctx *c)
     (void)close_gang(c);
     sync_all(c);
     if (g_prof_on && g_prof_n) {
-        std::fprintf(stderr, "[fxrx] submit profile over %lu blocks (ms per block): upload + bookkeeping %.4f, segments %.4f, memory + descriptors %.4f, front launches %.4f, back launches %.4f\n",
+        std::fprintf(stderr, "[fxrx] submit profile over %lu blocks (ms per block): input routes + bookkeeping %.4f, segments %.4f, memory + descriptors %.4f, front launches %.4f, back launches %.4f\n",
                      g_prof_n, g_prof[0] / g_prof_n, g_prof[1] / g_prof_n, g_prof[2] / g_prof_n, g_prof[3] / g_prof_n, g_prof[4] / g_prof_n);
         for (auto &v : g_prof) v = 0.0; g_prof_n = 0;
     }
@@ -442,6 +442,7 @@ void fxrx_destroy(fxrx_ctx *c)
         if (s->st) (void)hipStreamDestroy(s->st);
     }
     if (c->st_chain) { (void)hipStreamSynchronize(c->st_chain); (void)hipStreamDestroy(c->st_chain); }
+    if (c->ref_event) (void)hipEventDestroy(c->ref_event);
     for (auto &S : c->st) for (auto &p : S.carry) if (p) (void)hipFree(p);
     if (c->d_tables) (void)hipFree(c->d_tables);
     if (c->d_state) (void)hipFree(c->d_state);
@@ -493,7 +494,7 @@ fxrx_ctx *fxrx_create(const fxrx_config *cfg)
     if (const char *e = std::getenv("FXRX_WALK_PER_CU")) c->walk_per_cu = (uint32_t)std::min(8, std::max(1, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_VERIFY_PER_CU")) c->verify_per_cu = (uint32_t)std::min(64, std::max(1, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_MF_PER_CU")) c->mf_per_cu = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
-    if (const char *e = std::getenv("FXRX_INGEST_KERNEL_MAX")) c->ingest_kernel_max = (size_t)std::max<long long>(0, std::atoll(e));
+    if (const char *e = std::getenv("FXRX_INGEST_KERNEL_MAX")) c->ingest_limits.ingest_kernel_max = (size_t)std::max<long long>(0, std::atoll(e));
     if (const char *e = std::getenv("FXRX_PLAN_GRID")) c->plan_grid = (uint32_t)std::min(256, std::max(0, std::atoi(e)));
     if (const char *e = std::getenv("FXRX_DETWIN_RESERVE")) c->detwin_reserve = (uint32_t)std::max(0, std::atoi(e));
     if (const char *e = std::getenv("FXRX_VB_DEBUG")) c->vb_debug = (uint32_t)std::atoi(e);
@@ -738,11 +739,6 @@ static int reserve_block(fxrx_ctx_s *c, Slot &sl, const FrontBuild &fb)
         if (sl.h_win.reserve((size_t)sl.win_reserved * FX_NFFT) || sl.h_wintail.reserve(2 * (size_t)NS * FX_NFFT) || sl.h_winflag.reserve(1)) return FXRX_ERR_HIP;
         *sl.h_winflag.p = 0u;
     }
-    // the plan kernels' workspace: zeroed once, they leave it zero
-    if (!sl.d_plan_ws.p) {
-        if (sl.d_plan_ws.reserve(fx_plan_ws_words())) return FXRX_ERR_HIP;
-        HIP_OK(hipMemsetAsync(sl.d_plan_ws.p, 0, fx_plan_ws_words() * sizeof(uint32_t), sl.st));
-    }
     // batch Viterbi (the item list also without the path)
     if (sl.d_vb_items.reserve(2 * (size_t)sl.vb_slots_alloc) ||
         (sl.vb_blk && (sl.d_vb_vec.reserve(128 * (size_t)sl.vb_slots_alloc) || sl.d_vb_dw.reserve((size_t)sl.vb_dw_words) || sl.d_vb_st.reserve(sl.vb_slots_alloc)))) return FXRX_ERR_HIP;
@@ -776,15 +772,20 @@ static int enqueue_front(fxrx_ctx_s *c, Slot &sl, const FrontBuild &fb, hipStrea
     const unsigned n_early = (unsigned)fb.early.size(), n_late = (unsigned)fb.late.size(), n_spec = (unsigned)fb.spec.size();
     hipStream_t st = sl.st;
     const uint32_t *d_list = sl.job_list();
-    // (integer IQ first: raw copy where the source is not readable from the device, then fx_ingest_kernel into the staging buffer
-    // the descriptors point at.  Launched here, behind every check and reservation of the block; a replay finds the list empty.)
+    // (the block's input first, every format: a copy where the route has one -- float IQ into the staging buffer the descriptors point at, integer IQ into
+    // the raw one --, then fx_upload_kernel or fx_ingest_kernel where it has one.  Behind every check and reservation of the block; a replay finds the list empty.)
     if (!sl.ingest.empty()) {
         std::vector<IngestJob> todo; todo.swap(sl.ingest);
         const size_t bytes = iq_sample_bytes(sl.ingest_fmt);
         for (const IngestJob &j : todo) {
-            const void *src = j.dev_src;
-            if (!src) { HIP_OK(hipMemcpyAsync(sl.d_raw[j.stream].p, j.host_src, j.n * bytes, hipMemcpyHostToDevice, st)); src = sl.d_raw[j.stream].p; }
-            HIP_OK(fx_launch_ingest(st, sl.ingest_fmt, src, sl.d_in[j.stream].p, (size_t)j.n, sl.ingest_scale, (unsigned)c->n_cus));
+            float2 *x = sl.d_in[j.stream].p;
+            const void *src = j.src;
+            if (route_copies(j.route)) {
+                void *to = route_converts(j.route) ? (void *)sl.d_raw[j.stream].p : (void *)x;
+                HIP_OK(hipMemcpyAsync(to, src, j.n * bytes, hipMemcpyHostToDevice, st)); src = to;
+            }
+            if (j.route == kRouteUploadKernel) HIP_OK(fx_launch_upload(st, src, x, j.n * bytes, (unsigned)c->n_cus));
+            if (route_converts(j.route)) HIP_OK(fx_launch_ingest(st, sl.ingest_fmt, src, x, (size_t)j.n, sl.ingest_scale, (unsigned)c->n_cus));
         }
     }
     HIP_OK(fx_launch_upload(st, sl.hp_desc.p, sl.d_desc.p, fb.desc_bytes, (unsigned)c->n_cus));     // (descriptors: our own page-locked buffer)
@@ -832,22 +833,29 @@ static int enqueue_front(fxrx_ctx_s *c, Slot &sl, const FrontBuild &fb, hipStrea
     return 0;
 }
 
-static int enqueue_block(fxrx_ctx_s *c, Slot &sl, bool may_defer = false)
+// FXRX_DEBUG_SUBMIT_PROFILE: the host time since *t goes to part `part` of the profile, and *t moves on
+static inline void prof_lap(int part, double *t) { if (g_prof_on) { const double now = prof_now(); g_prof[part] += now - *t; *t = now; } }
+
+// steps 4 and 5 and the back part: only a HIP launch error can follow from here on
+static int launch_block(fxrx_ctx_s *c, Slot &sl, FrontBuild &fb, bool may_defer, double *t)
 {
-    const double tp0 = g_prof_on ? prof_now() : 0.0;
-    FrontBuild fb;
-    { const int r = plan_front(c, sl, fb.plan); if (r) return r; }
-    build_descriptors(c, sl, fb);
-    const double tp1 = g_prof_on ? prof_now() : 0.0;
-    { const int r = reserve_block(c, sl, fb); if (r) return r; }
-    pack_descriptors(sl, fb);
-    const double tp2 = g_prof_on ? prof_now() : 0.0;
+    pack_descriptors(sl, fb); prof_lap(2, t);
     hipStream_t cst = nullptr;
     { const int r = enqueue_front(c, sl, fb, &cst); if (r) return r; }
-    const double tp3 = g_prof_on ? prof_now() : 0.0;
+    prof_lap(3, t);
     const int rb = enqueue_back(c, sl, kChainFast, cst, may_defer);
-    if (g_prof_on) { const double tp4 = prof_now(); g_prof[1] += tp1 - tp0; g_prof[2] += tp2 - tp1; g_prof[3] += tp3 - tp2; g_prof[4] += tp4 - tp3; g_prof_n++; }
+    prof_lap(4, t); if (g_prof_on) g_prof_n++;
     return rb;
+}
+// a block whose snapshot the slot holds (a replay): plan, build, reserve, pack, enqueue
+static int enqueue_block(fxrx_ctx_s *c, Slot &sl)
+{
+    double t = g_prof_on ? prof_now() : 0.0;
+    FrontBuild fb;
+    { const int r = plan_front(c, sl, fb.plan); if (r) return r; }
+    build_descriptors(c, sl, fb); prof_lap(1, &t);
+    { const int r = reserve_block(c, sl, fb); if (r) return r; }
+    return launch_block(c, sl, fb, /* may_defer */ false, &t);
 }
 
 static FxVbpreMember vbpre_member(Slot &sl, uint32_t first_wave, uint32_t n_waves)
@@ -996,99 +1004,86 @@ static int enqueue_back(fxrx_ctx_s *c, Slot &sl, int chain_mode, hipStream_t cha
     return 0;
 }
 
-// Integer IQ of a block: everything that can fail for a reason the caller can mend -- format, alignment, the staging buffers of
-// ALL streams -- before the context is touched or anything is enqueued.  Leaves the list of conversions in the slot.
+// The input of a block, every format: the argument checks, a route per stream with new samples (fx_ingestplan.h), and whatever the
+// routes write to, reserved for ALL streams.  Nothing is enqueued: the block's sample pointers (sl.x) and the list of uploads and
+// conversions stay in the slot for enqueue_front.
 static int prepare_ingest(fxrx_ctx_s *c, Slot &sl, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt)
 {
     const unsigned NS = c->cfg.n_streams;
-    const size_t bytes = iq_sample_bytes(fmt);
-    sl.ingest.clear();
-    for (unsigned s = 0; s < NS; s++)
+    const bool flt = fmt == FXRX_IQ_FC32; const size_t bytes = iq_sample_bytes(fmt);
+    sl.ingest.clear(); sl.x.assign(NS, nullptr);
+    for (unsigned s = 0; s < NS && !flt; s++)
         if (n_samples[s] && (!iq[s] || (reinterpret_cast<uintptr_t>(iq[s]) & (bytes - 1)))) {
             set_err("fxrx_submit_fmt: integer IQ must be aligned to its sample size (sc16: 4 bytes, sc8: 2 bytes)"); return FXRX_ERR_ARG;
         }
-    if (sl.d_in.size() < NS) sl.d_in.resize(NS);
-    if (sl.d_raw.size() < NS) sl.d_raw.resize(NS);
+    if (sl.d_in.size() < NS) { sl.d_in.resize(NS); sl.d_raw.resize(NS); }
     std::vector<IngestJob> jobs;
     for (unsigned s = 0; s < NS; s++) {
-        const uint64_t nn = n_samples[s];
+        if (flt && on_device) { sl.x[s] = static_cast<const float2 *>(iq[s]); continue; }     // kRouteInPlace: nothing to launch
+        const uint64_t nn = n_samples[s]; const uintptr_t addr = reinterpret_cast<uintptr_t>(iq[s]);
         if (sl.d_in[s].reserve(nn + 1)) return FXRX_ERR_HIP;
-        if (!nn) continue;
-        IngestJob j; j.stream = s; j.n = nn;
-        // a device buffer is read in place; a small page-locked block (ingest_kernel_max) is read over the bus by the kernel itself;
-        // everything else goes through the copy engines into the raw staging buffer first, which measured faster from 2 MB raw on
-        if (on_device) j.dev_src = iq[s];
-        else if (!(nn * bytes <= c->ingest_kernel_max && pinned_device_ptr(iq[s], &j.dev_src, 0u))) {
-            j.dev_src = nullptr; j.host_src = iq[s];
-            if (sl.d_raw[s].reserve(nn * bytes + 16)) return FXRX_ERR_HIP;
-        }
-        jobs.push_back(j);
+        sl.x[s] = sl.d_in[s].p;
+        IngestJob j{ s, kRouteNone, iq[s], nn };
+        // (whether the memory is page-locked takes a call into the runtime: asked only where the answer changes the route)
+        const bool locked = nn && !on_device && kernel_may_read_host(fmt, addr, nn, c->ingest_limits) && pinned_device_ptr(iq[s], &j.src);
+        j.route = ingest_route(fmt, on_device != 0, locked, addr, nn, c->ingest_limits);
+        if (j.route == kRouteConvertCopy && sl.d_raw[s].reserve(nn * bytes + 16)) return FXRX_ERR_HIP;
+        if (j.route != kRouteNone) jobs.push_back(j);
     }
     sl.ingest.swap(jobs); sl.ingest_fmt = fmt; sl.ingest_scale = c->iq_scale[fmt];
     return 0;
 }
 
+// fxrx_debug_block_times: a common origin of the GPU's and the host's clocks, taken once per context
+static void clock_origin(fxrx_ctx_s *c, hipStream_t st)
+{
+    if (c->timing_level < 2 || c->ref_event || hipEventCreate(&c->ref_event) != hipSuccess) return;
+    (void)hipEventRecord(c->ref_event, st); (void)hipEventSynchronize(c->ref_event);
+    c->ref_host_ms = prof_now();
+}
+// fxrx_submit in three steps.  A submit that fails for a reason the caller can mend fails in the first two, which write to the block's
+// slot and to nothing else: the context is as it was, nothing is enqueued that reads the caller's buffers, and the next block -- the
+// same samples again, or others -- continues from the state before the call.
 static int submit_block(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, int on_device, int fmt)
 {
     if (!c || !iq || !n_samples) { set_err("fxrx_submit: null argument"); return FXRX_ERR_ARG; }
     if (iq_sample_bytes(fmt) == 0) { set_err("fxrx_submit_fmt: unknown IQ format"); return FXRX_ERR_ARG; }
     if (c->inflight >= c->depth) { set_err("fxrx_submit: pipeline full, call fxrx_collect first"); return FXRX_ERR_STATE; }
     HIP_OK(hipSetDevice(c->cfg.device));
-    const auto t_enter = std::chrono::steady_clock::now();
+    const double t_enter = prof_now(); double t = t_enter;
     const unsigned NS = c->cfg.n_streams;
-    const unsigned nslots = c->depth + 1;
     Slot &sl = *c->slots[c->head];
-    sl.ingest.clear();
-    if (fmt != FXRX_IQ_FC32) { const int r = prepare_ingest(c, sl, iq, n_samples, on_device, fmt); if (r) return r; }
-    sl.out.clear(); sl.timing = fxrx_timing{};
-    sl.kept_hops = sl.kept_cheap = sl.kept_vhops = sl.kept_vfail = sl.kept_repairs = 0;
-    const unsigned noskip_before = c->noskip_left;
-    sl.force_noskip = c->noskip_left > 0; if (c->noskip_left) c->noskip_left--;
-    sl.seq = c->seq;
-    sl.x.assign(NS, nullptr); sl.n.assign(n_samples, n_samples + NS); sl.snap.assign(NS, StreamSnap{});
-    if (sl.d_in.size() < NS) sl.d_in.resize(NS);
-    // A submit that fails leaves the context as it found it: per-stream positions, freshness and tail bounds are restored, so
-    // that the next block -- the same samples again, or others -- continues from the state before the call.  (Caller-recoverable
-    // failures happen before anything is launched: argument checks, arena sizing, allocations.)
-    struct Undo { fxrx_ctx_s *c; std::vector<StreamState> st; unsigned noskip; bool armed = true;
-                  ~Undo() { if (armed) { c->st = st; c->noskip_left = noskip; } } } undo{ c, c->st, noskip_before };
-    uint64_t total_new = 0;
+    // ---- stage: the block's snapshot of every stream, its plan, its input routes, its descriptors.  No call on a HIP stream; the
+    // streams' successor state is worked out in `next`, not in the context ----
+    sl.out.clear(); sl.timing = fxrx_timing{}; sl.kept_hops = sl.kept_cheap = sl.kept_vhops = sl.kept_vfail = sl.kept_repairs = 0;
+    sl.seq = c->seq; sl.force_noskip = c->noskip_left > 0;
+    sl.n.assign(n_samples, n_samples + NS); sl.snap.assign(NS, StreamSnap{});
+    std::vector<StreamState> next = c->st;
     for (unsigned s = 0; s < NS; s++) {
-        StreamState &S = c->st[s];
+        const StreamState &S = c->st[s]; StreamState &N = next[s]; StreamSnap &sn = sl.snap[s];
         const uint64_t nn = n_samples[s];
-        total_new += nn;
-        if (fmt != FXRX_IQ_FC32) sl.x[s] = sl.d_in[s].p;            // (prepare_ingest: converted into the staging buffer by the block's first kernels)
-        else if (on_device) sl.x[s] = (const float2 *)iq[s];
-        else {
-            if (sl.d_in[s].reserve(nn + 1)) return FXRX_ERR_HIP;
-            if (nn) {
-                // page-locked source, moderate size: the shader cores fetch it (fx_upload_kernel: the launch costs microseconds, the
-                // copy call held this thread for hundreds); pageable memory and very large blocks go through the runtime's copy engines
-                const void *dsrc = nullptr;
-                if (nn * sizeof(float2) <= kUploadKernelMax && pinned_device_ptr(iq[s], &dsrc)) HIP_OK(fx_launch_upload(sl.st, dsrc, sl.d_in[s].p, nn * sizeof(float2), (unsigned)c->n_cus));
-                else HIP_OK(hipMemcpyAsync(sl.d_in[s].p, iq[s], nn * sizeof(float2), hipMemcpyHostToDevice, sl.st));
-            }
-            sl.x[s] = sl.d_in[s].p;
-        }
-        sl.snap[s].tot0 = S.total; sl.snap[s].fresh_start = S.fresh_start; sl.snap[s].carry_bound = S.fresh_start ? 0 : S.carry_bound;
-        sl.snap[s].noskip = S.noskip_left > 0; if (S.noskip_left) S.noskip_left--;
-        S.total += (int64_t)nn; S.fresh_start = false;
-        S.carry_bound = std::min<int64_t>(S.carry_cap, sl.snap[s].carry_bound + (int64_t)nn);
+        sl.timing.samples += nn; if (N.noskip_left) N.noskip_left--;
+        sn.tot0 = S.total; sn.fresh_start = S.fresh_start; sn.carry_bound = S.fresh_start ? 0 : S.carry_bound; sn.noskip = S.noskip_left > 0;
+        N.total += (int64_t)nn; N.fresh_start = false; N.carry_bound = std::min<int64_t>(S.carry_cap, sn.carry_bound + (int64_t)nn);
     }
-    if (c->timing_level >= 2 && !c->ref_event) {
-        if (hipEventCreate(&c->ref_event) == hipSuccess) { (void)hipEventRecord(c->ref_event, sl.st); (void)hipEventSynchronize(c->ref_event); c->ref_host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    }
-    sl.dbg_submit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - c->ref_host_ms;
-    sl.timing.samples = total_new;
+    FrontBuild fb;
+    prof_lap(0, &t);
+    { const int r = plan_front(c, sl, fb.plan); if (r) return r; }           // (first: a batch too large fails before any staging buffer is sized for it)
+    prof_lap(1, &t);
+    { const int r = prepare_ingest(c, sl, iq, n_samples, on_device, fmt); if (r) return r; }
+    prof_lap(0, &t);
+    build_descriptors(c, sl, fb); prof_lap(1, &t);
+    // ---- reserve: every buffer of the block.  The last point at which a submit fails and the caller can mend it ----
+    { const int r = reserve_block(c, sl, fb); if (r) return r; }
     if (c->debug_fail_submit) { c->debug_fail_submit--; set_err("fxrx_submit: injected failure (fxrx_debug_fail)"); return FXRX_ERR_STATE; }
-    if (g_prof_on) g_prof[0] += prof_now() - std::chrono::duration<double, std::milli>(t_enter.time_since_epoch()).count();
-    int r = enqueue_block(c, sl, /* may_defer */ true);
-    if (r) return r;
-    undo.armed = false;
-    c->seq++;
-    sl.busy = true;
-    c->head = (c->head + 1) % nslots; c->inflight++;
-    sl.host_submit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
+    // ---- enqueue: the input's uploads and conversions, then the chain; then the context moves on.  enqueue_back changes the context
+    // once launches have begun (inchain_left, traffic.trellis_left, prev_chain, carry_reader, the open gang): only a HIP launch error
+    // can follow those, and that is fatal to the context -- every later call fails the same way ----
+    clock_origin(c, sl.st); sl.dbg_submit_ms = t_enter - c->ref_host_ms;
+    { const int r = launch_block(c, sl, fb, /* may_defer */ true, &t); if (r) return r; }
+    c->st.swap(next); if (c->noskip_left) c->noskip_left--;
+    c->seq++; sl.busy = true; c->head = (c->head + 1) % (c->depth + 1); c->inflight++;
+    sl.host_submit_ms = prof_now() - t_enter;
     return 0;
 }
 

@@ -4,7 +4,7 @@
 //   Traffic   what that block held                                  (written by fxrx_collect: observe)
 //   TailPlan  the grids and optional launches of a block's tail     (plan_tail, every time fx_host.cpp:enqueue_back runs)
 //   LateWork  what such a plan left undone for the block it met     (late_work, asked once by fx_host.cpp:finish_decode)
-// The front of a block reads the same Traffic (fx_frontplan.h, every time fx_host.cpp:enqueue_block runs): frames and samples for
+// The front of a block reads the same Traffic (fx_frontplan.h, every time fx_host.cpp:plan_front runs: a submit, a replay): frames and samples for
 // the depth of the pre-lock scan (and frames for the detector's window slots), vb_steps for the trellis block length and the batch
 // Viterbi arenas, verify_per for every walk job.
 // Host only and pure -- no HIP call, no allocation --, so that tests/cpp/traffic_check.cpp checks it with g++ alone.

@@ -313,7 +313,8 @@ int fxrx_submit(fxrx_ctx *c, const void *const *iq, const uint64_t *n_samples, i
 int fxrx_collect(fxrx_ctx *c);
 /* Failure semantics.  A failing fxrx_submit (bad arguments, a batch too large for the arenas, an allocation that fails) leaves
  * the context exactly as it was: the same block, or another, can be submitted next and continues the streams from where they
- * stood.  A failing fxrx_collect drops every block in flight (their samples are never searched) and restarts all streams
+ * stood.  Every argument check and reservation of a block, whatever its format, is done before anything is enqueued: nothing reads
+ * the input buffers of a submit that failed, and they may be reused or freed at once.  A failing fxrx_collect drops every block in flight (their samples are never searched) and restarts all streams
  * from a freshly reset synchroniser with the next block submitted; sample positions keep counting.  Either way the context
  * stays usable -- unless the HIP runtime itself reports errors, which every later call will report again. */
 /* Integer IQ (SDR-native samples).  A block may be handed over as interleaved 16-bit (sc16) or 8-bit (sc8) signed integer
@@ -328,7 +329,7 @@ int fxrx_collect(fxrx_ctx *c);
  * The format is a property of a block, not of the context: the blocks of a continuing stream may change format; all streams of
  * one block share it.  sc16 samples must be 4-byte aligned, sc8 samples 2-byte aligned (FXRX_ERR_ARG otherwise); any such
  * alignment and any n_samples work.  fxrx_submit(c, ...) is fxrx_submit_fmt(c, ..., FXRX_IQ_FC32).  Failure semantics as for
- * fxrx_submit; with an integer format every argument check and reservation is done before anything is enqueued. */
+ * fxrx_submit. */
 enum { FXRX_IQ_FC32 = 0, FXRX_IQ_SC16 = 1, FXRX_IQ_SC8 = 2 };
 unsigned int fxrx_iq_sample_bytes(int fmt);                 /* 8, 4, 2; 0 for an unknown fmt (no GPU needed) */
 /* scale of an integer format: default 1/32768 (sc16), 1/128 (sc8).  Must be finite and > 0; applies from the next submit on.

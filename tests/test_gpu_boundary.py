@@ -4,7 +4,10 @@ instance, :49), and what a failing fxrx_submit / fxrx_collect leaves behind (inc
 import ctypes as C
 import numpy as np
 import pytest
+import failing_submit_cases as fsc
 from parity_util import oracle_frames, compare_frames
+from test_gpu_ingest import route_ctx, same
+from test_ingest import capture
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +50,14 @@ def test_failing_submit_leaves_the_context_as_it_was(fx, oracle):
     got = [_key(g) for g in ctx.results(ctx.collect_raw())] + [_key(g) for g in ctx.results(ctx.collect_raw())]
     assert got == of
     ctx.close()
+
+
+@pytest.mark.parametrize("how,in_flight", [("injected", True), ("too_large", False)])
+@pytest.mark.parametrize("source", fsc.SOURCES)
+def test_failing_submit_reads_nothing_of_the_callers_buffer(fx, source, how, in_flight):
+    """tests/failing_submit_cases.py, every host-visible source of a block: the failure injected with a block in flight (depth 2),
+    and the batch too large for the arenas in its place.  Either way the submitted buffer is overwritten at once."""
+    fsc.run(fx, lambda route: route_ctx(fx, route), same, source, how, in_flight)
 
 
 def test_failing_collect_drops_what_is_in_flight_and_the_context_recovers(fx, oracle):
@@ -197,3 +208,33 @@ def test_pinned_host_blocks_take_the_upload_kernel_and_give_the_same_frames(fx, 
             got += [_key(g) for g in ctx.results(ctx.collect_raw())]
         assert got == of and len(of) > 10
         ctx.close()
+
+
+def test_float_blocks_give_the_same_results_from_every_source(fx, oracle):
+    """The three routes of float IQ (fx_ingestplan.h: the copy engines from pageable memory, fx_upload_kernel from page-locked
+    memory, device memory read in place): two blocks of one continuing stream, cut inside a frame, give results that are equal
+    field for field, floats by bit pattern, whichever way the samples came -- and those are the oracle's."""
+    import torch
+    x, _ = capture(fx, n_frames=6, payload_len=300, stream_id=318)
+    of = oracle_frames(oracle, x)
+    cut = of[len(of) // 2].info["start"] + 333
+    parts = [np.ascontiguousarray(x[:cut]), np.ascontiguousarray(x[cut:])]
+    pins = [fsc.HostBuf(fx, p, True) for p in parts]
+    dev = [torch.from_numpy(p).cuda() for p in parts]
+    torch.cuda.synchronize()
+    ptrs = {"pageable": [p.ctypes.data for p in parts], "pinned": [p.ptr for p in pins], "device": [d.data_ptr() for d in dev]}
+    got = {}
+    for where, pp in ptrs.items():
+        ctx = fx.RxContext(1, want_framesyms=True)
+        ctx.set_depth(2)
+        for p, part in zip(pp, parts):
+            ctx.submit_raw([p], [len(part)], where == "device")
+        got[where] = ctx.results(ctx.collect_raw()) + ctx.results(ctx.collect_raw())
+        ctx.close()
+    for p in pins:
+        p.free()
+    assert len(of) == 6
+    same(got["pageable"], got["device"], "pageable against device")
+    same(got["pinned"], got["device"], "page-locked against device")
+    same(got["pageable"], got["pinned"], "pageable against page-locked")
+    compare_frames(of, got["device"])

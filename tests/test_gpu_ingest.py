@@ -11,6 +11,7 @@ import struct
 import numpy as np
 import pytest
 
+import failing_submit_cases as fsc
 import ref_ingest as ri
 from test_ingest import capture, quantised, RMS_OF_FULL_SCALE
 from parity_util import oracle_frames, compare_frames
@@ -297,6 +298,19 @@ def test_a_failing_submit_leaves_the_context_as_it_was(fx):
     assert L.fxrx_inflight(ctx.h) == 0
     same(ctx.results(ctx.process_raw([p2], [len(q) - cut], False, fmt)), ref2, "the same block again")
     a.free(); ctx.close()
+
+
+def route_ctx(fx, route):
+    """RxContext for tests/failing_submit_cases.py: FXRX_INGEST_KERNEL_MAX = route while the context is created (None: the default)"""
+    where = {None: "pinned", ROUTE["pinned_kernel"]: "pinned_kernel", ROUTE["pinned_copy"]: "pinned_copy"}[route]
+    return make_ctx(fx, where, 1, want_framesyms=True)
+
+
+@pytest.mark.parametrize("source", fsc.SOURCES)
+def test_a_failing_submit_reads_nothing_of_the_callers_buffer(fx, source):
+    """tests/failing_submit_cases.py: an injected failure behind the last reservation, nothing in flight; the submitted buffer is
+    overwritten at once and the block submitted again from another one -- every host-visible source of a block"""
+    fsc.run(fx, lambda route: route_ctx(fx, route), same, source)
 
 
 @pytest.mark.parametrize("fmt", FMTS)
