@@ -10,6 +10,7 @@
 #include <cmath>
 #include <emmintrin.h>
 #include "../../include/fxrx.h"
+#include "fx_blockfeed.h"
 #include "fx_codec.hpp"
 
 namespace {
@@ -55,59 +56,40 @@ constexpr unsigned kQdetBlockDefault = 1u << 16;    // qdetector_cccf_execute: s
 constexpr unsigned kQdetDepthDefault = 1;           // ... blocks in flight (FXRX_QDET_DEPTH)
 constexpr unsigned kQdetPollEvery = 1u << 10;       // ... calls between two looks at the oldest block in flight
 
-// a ring of `count` page-locked buffers of `samples` each; all or nothing
-bool alloc_ring(std::vector<fx_complex *> &ring, unsigned count, size_t samples)
-{
-    std::vector<fx_complex *> r;
-    for (unsigned i = 0; i < count; i++) {
-        fx_complex *p = (fx_complex *)fxrx_pinned_alloc(samples * sizeof(fx_complex));
-        if (!p) { for (auto o : r) fxrx_pinned_free(o); return false; }
-        r.push_back(p);
-    }
-    ring.swap(r);
-    return true;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ flexframesync
 // The reference feeds 256 samples per call from pageable memory (/root/reference/lib/flex_rx_impl.cc:212-215).  Here a call
 // copies them into the pinned buffer being filled; a full buffer is submitted as one block of the continuing stream
 // (fxrx_submit: upload and the whole kernel chain are enqueued, nothing is waited for) and the next buffer of the ring is
-// filled while up to `depth` blocks are in flight.  Finished blocks are collected when a slot is needed or when a poll
-// (every few thousand samples) finds the oldest one done; their frames wait in `pending` and leave one per call.
-struct fxrx_sync_s {
+// filled while up to `depth` blocks are in flight (fx_blockfeed.h).  Finished blocks are collected when a slot is needed or when a
+// poll (every few thousand samples) finds the oldest one done; their frames wait in `pending` and leave one per call.
+struct fxrx_sync_s : BlockFeed<fxrx_sync_s> {
+    static constexpr const char *entry = "flexframesync_execute";
     framesync_callback cb = nullptr; void *ud = nullptr;
-    fxrx_ctx *ctx = nullptr; float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0, soft_block = 0, soft_chain = 0, soft_rs = 0, soft_rs_fmax = 0, soft_rs_chain = 0;
-    unsigned block = kSyncBlockDefault, depth = kSyncDepthDefault;
-    std::vector<fx_complex *> bufs; unsigned cur = 0; size_t fill = 0;     // ring of depth + 1 pinned input buffers of `block` samples
+    float threshold = 0.0f; int equalizer = 0, soft = 0, soft_header = 0, soft_block = 0, soft_chain = 0, soft_rs = 0, soft_rs_fmax = 0, soft_rs_chain = 0;
     std::deque<HeldFrame> pending; HeldFrame current;
-    unsigned errors = 0, since_poll = 0;
+    unsigned since_poll = 0;
     unsigned stream_floor = 0;          // streaming delivery (fxrx_sync_set_streaming / FXRX_SYNC_STREAMING): 0 off, else the fewest samples worth a block
 
-    ~fxrx_sync_s() { free_bufs(); }
-    void free_bufs() { for (auto p : bufs) fxrx_pinned_free(p); bufs.clear(); cur = 0; fill = 0; }
-    // a new ring of depth + 1 buffers of `samples`; the old one is given up only once the new one stands
-    bool alloc_bufs(unsigned samples)
+    fxrx_sync_s() : BlockFeed(kSyncBlockDefault, kSyncDepthDefault) {}
+    // what an option needs to be in force, as fxrx_create demands it: read by config() and by the setters that refuse without
+    bool soft_on() const { return soft != 0; }
+    bool soft_block_on() const { return soft && soft_block; }
+    bool soft_rs_on() const { return soft && soft_rs; }
+    fxrx_config config() const
     {
-        std::vector<fx_complex *> ring;
-        if (!alloc_ring(ring, depth + 1, samples)) return false;
-        free_bufs();
-        bufs.swap(ring); block = samples;
-        return true;
+        fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_FLEX_RX; cfg.n_streams = 1; cfg.want_framesyms = 1;
+        cfg.threshold = threshold; cfg.equalizer = equalizer; cfg.soft_decision = soft; cfg.soft_header = soft_header;
+        cfg.soft_block = soft_block_on(); cfg.soft_chain = soft_block_on() && soft_chain; cfg.soft_rs = soft_rs_on();
+        cfg.soft_rs_fmax = soft_rs_on() ? soft_rs_fmax : 0; cfg.soft_rs_chain = soft_rs_on() && soft_rs_chain;
+        return cfg;
     }
-    void report(const char *what, int rc)
+    void materialise_all() { for (auto &h : pending) h.materialise(); current.materialise(); }
+    void before_collect() { materialise_all(); }           // (rare: frames are normally delivered long before the next block is due)
+    // queue the frames of the block just collected
+    void take(int nr)
     {
-        if (errors++ == 0 || (errors & (errors - 1)) == 0)
-            std::fprintf(stderr, "libfxrx: %s failed (%d): %s [%u failures so far]\n", what, rc, ctx ? fxrx_last_error() : "no context", errors);
-    }
-    // the oldest block in flight: wait for it, queue its frames
-    void collect_one()
-    {
-        for (auto &h : pending) h.materialise();           // (rare: frames are normally delivered long before the next block is due)
-        current.materialise();
-        const int nr = fxrx_collect(ctx);
-        if (nr < 0) { report("flexframesync_execute: block", nr); return; }     // (every block in flight was dropped with it; the streams restart fresh)
         for (int i = 0; i < nr; i++) {
             fxrx_frame f; if (fxrx_result(ctx, (unsigned)i, &f) != 0) continue;
             pending.emplace_back();
@@ -119,23 +101,6 @@ struct fxrx_sync_s {
             h.stats.mod_scheme = f.mod_scheme; h.stats.mod_bps = f.mod_bps; h.stats.check = f.check; h.stats.fec0 = f.fec0; h.stats.fec1 = f.fec1;
         }
     }
-    // hand the buffer being filled to the GPU as the stream's next block
-    void submit_current()
-    {
-        if (!fill) return;
-        if (fxrx_inflight(ctx) >= depth) collect_one();
-        _mm_sfence();                                          // (the streamed samples are in memory before the upload is enqueued)
-        const void *p = bufs[cur]; uint64_t n = fill;
-        const int r = fxrx_submit(ctx, &p, &n, 0);
-        if (r < 0) {
-            // the context is as it was before the call; these samples are lost to it: restart the synchroniser behind the gap
-            report("flexframesync_execute: submit", r);
-            while (fxrx_inflight(ctx)) collect_one();
-            fxrx_reset(ctx);
-        }
-        cur = (cur + 1) % (unsigned)bufs.size(); fill = 0;
-    }
-    void drain() { while (fxrx_inflight(ctx)) collect_one(); }
     void deliver_one()
     {
         if (pending.empty()) return;
@@ -148,18 +113,6 @@ struct fxrx_sync_s {
     }
 };
 
-static fxrx_ctx *sync_make_ctx(const fxrx_sync_s *q)
-{
-    fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_FLEX_RX; cfg.n_streams = 1; cfg.want_framesyms = 1;
-    if (q) { cfg.threshold = q->threshold; cfg.equalizer = q->equalizer; cfg.soft_decision = q->soft; cfg.soft_header = q->soft_header;
-            cfg.soft_block = q->soft && q->soft_block; cfg.soft_chain = q->soft && q->soft_block && q->soft_chain; cfg.soft_rs = q->soft && q->soft_rs;
-            cfg.soft_rs_fmax = cfg.soft_rs ? q->soft_rs_fmax : 0; cfg.soft_rs_chain = cfg.soft_rs && q->soft_rs_chain; }
-    if (const char *d = std::getenv("FXRX_DEVICE")) cfg.device = std::atoi(d);
-    fxrx_ctx *ctx = fxrx_create(&cfg);
-    if (ctx && fxrx_set_depth(ctx, q ? q->depth : kSyncDepthDefault) != 0) { fxrx_destroy(ctx); return nullptr; }
-    return ctx;
-}
-
 extern "C" {
 
 // /root/reference/lib/flex_rx_impl.cc:49
@@ -168,24 +121,23 @@ flexframesync flexframesync_create(framesync_callback callback, void *userdata)
     std::unique_ptr<fxrx_sync_s> q(new fxrx_sync_s); q->cb = callback; q->ud = userdata;
     if (const char *e = std::getenv("FXRX_SYNC_BLOCK")) q->block = (unsigned)std::max(256, std::atoi(e));
     if (const char *e = std::getenv("FXRX_SYNC_DEPTH")) q->depth = (unsigned)std::min(15, std::max(1, std::atoi(e)));
-    q->ctx = sync_make_ctx(q.get());
-    if (!q->ctx) return nullptr;
+    if (!q->replace_ctx(q->config())) return nullptr;
     if (const char *e = std::getenv("FXRX_SYNC_STREAMING")) q->stream_floor = (unsigned)std::max(0, std::atoi(e));
-    if (!q->alloc_bufs(q->block)) { fxrx_destroy(q->ctx); return nullptr; }
+    if (!q->set_ring(q->block)) return nullptr;
     return q.release();
 }
 // /root/reference/lib/flex_rx_impl.cc:71
-void flexframesync_destroy(flexframesync q) { if (!q) return; fxrx_destroy(q->ctx); delete q; }
+void flexframesync_destroy(flexframesync q) { delete q; }
 void flexframesync_reset(flexframesync q)
 {
-    if (!q) return;
+    if (!q || !q->ctx) return;
     q->drain(); q->pending.clear(); q->fill = 0;
     fxrx_reset(q->ctx);
 }
 // /root/reference/lib/flex_rx_impl.cc:213
 void flexframesync_execute(flexframesync q, fx_complex *x, unsigned int n)
 {
-    if (!q) return;
+    if (!q || !q->ctx) return;
     if (q->bufs.empty()) { q->errors++; return; }           // (cannot happen: a ring is only ever swapped for a complete one)
     q->since_poll += n;
     while (n) {
@@ -203,90 +155,60 @@ void flexframesync_execute(flexframesync q, fx_complex *x, unsigned int n)
     if (q->stream_floor && q->fill >= q->stream_floor && fxrx_inflight(q->ctx) == 0) q->submit_current();
     q->deliver_one();
 }
-void fxrx_sync_flush(flexframesync q) { if (!q) return; q->submit_current(); q->drain(); }
+void fxrx_sync_flush(flexframesync q) { if (q) q->flush(); }
 void fxrx_sync_set_block(flexframesync q, unsigned int samples)
 {
-    if (!q) return;
+    if (!q || !q->ctx) return;
     const unsigned nb = samples < 256 ? 256u : samples;
     if (nb == q->block) return;
-    fxrx_sync_flush(q);                      // what is queued runs at the old size (buffers move)
-    for (auto &h : q->pending) h.materialise();
-    q->current.materialise();
-    if (!q->alloc_bufs(nb)) { q->errors++; std::fprintf(stderr, "libfxrx: fxrx_sync_set_block: %s (block length unchanged)\n", fxrx_last_error()); }
+    q->flush();                              // what is queued runs at the old size (buffers move)
+    q->materialise_all();
+    (void)q->resize(nb, "fxrx_sync_set_block");
 }
 void fxrx_sync_set_streaming(flexframesync q, unsigned int floor_samples) { if (q) q->stream_floor = floor_samples; }
 unsigned int fxrx_sync_pending(flexframesync q) { return q ? (unsigned)q->pending.size() : 0; }
 unsigned int fxrx_sync_errors(flexframesync q) { return q ? q->errors : 0; }
 fxrx_ctx *fxrx_sync_context(flexframesync q) { return q ? q->ctx : nullptr; }
-// threshold and equaliser live in the context configuration: make a new context first, swap only if that worked (state is
-// reset, as liquid's setters do not promise otherwise); on failure the old context stays and the error is reported
-static bool sync_recreate(flexframesync q, const char *what)
-{
-    fxrx_sync_flush(q);
-    for (auto &h : q->pending) h.materialise();
-    q->current.materialise();
-    fxrx_ctx *nc = sync_make_ctx(q);
-    if (!nc) { q->errors++; std::fprintf(stderr, "libfxrx: %s: %s (setting unchanged)\n", what, fxrx_last_error()); return false; }
-    fxrx_destroy(q->ctx);
-    q->ctx = nc;
-    return true;
-}
-// a setting that lives in the context configuration: the new value is tried on a new context and kept only if that context could be made
+// A setting lives in the context configuration: what is queued runs under the old value (pending frames are kept, as copies), the new
+// value is tried on a new context and kept only if that context could be made (state is reset, as liquid's setters do not promise
+// otherwise); else the old context and value stay and the error is reported
 extern "C++" template <class T> static int sync_set_value(flexframesync q, T fxrx_sync_s::*field, T value, const char *what)
 {
     if (!q) return -1;
+    q->flush();
+    q->materialise_all();
     const T old = q->*field;
     q->*field = value;
-    if (!sync_recreate(q, what)) { q->*field = old; return -1; }
-    return 0;
+    if (q->replace_ctx(q->config())) return 0;
+    q->*field = old; q->errors++;
+    std::fprintf(stderr, "libfxrx: %s: %s (setting unchanged)\n", what, fxrx_last_error());
+    return -1;
 }
-static int sync_set_option(flexframesync q, int fxrx_sync_s::*field, int on, const char *what) { return sync_set_value(q, field, on ? 1 : 0, what); }
+// an option.  `needs` (with its text): what must be on for a value other than 0 -- turning the option on without is refused, as
+// fxrx_create would; `bad_value`: the text of a value fxrx_create would not take, or null
+static int sync_set(flexframesync q, int fxrx_sync_s::*field, int value, const char *what, bool (fxrx_sync_s::*needs)() const = nullptr,
+                    const char *needs_text = nullptr, const char *bad_value = nullptr)
+{
+    if (q && value && needs && !(q->*needs)()) { std::fprintf(stderr, "libfxrx: %s: needs %s (setting unchanged)\n", what, needs_text); return -1; }
+    if (q && bad_value) { std::fprintf(stderr, "libfxrx: %s: %s (setting unchanged)\n", what, bad_value); return -1; }
+    return sync_set_value(q, field, value, what);
+}
 void fxrx_sync_set_threshold(flexframesync q, float t) { (void)sync_set_value(q, &fxrx_sync_s::threshold, t, "fxrx_sync_set_threshold"); }
-void fxrx_sync_set_equalizer(flexframesync q, int on) { (void)sync_set_option(q, &fxrx_sync_s::equalizer, on, "fxrx_sync_set_equalizer"); }
-void fxrx_sync_set_soft(flexframesync q, int on) { (void)sync_set_option(q, &fxrx_sync_s::soft, on, "fxrx_sync_set_soft"); }
-int fxrx_sync_set_soft_block(flexframesync q, int on) { return sync_set_option(q, &fxrx_sync_s::soft_block, on, "fxrx_sync_set_soft_block"); }
-// (in force while soft payload decoding and soft_block are on; turning it on without them is refused, as fxrx_create would)
-int fxrx_sync_set_soft_chain(flexframesync q, int on)
-{
-    if (q && on && !(q->soft && q->soft_block)) {
-        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_chain: needs soft payload decoding and soft_block (setting unchanged)\n");
-        return -1;
-    }
-    return sync_set_option(q, &fxrx_sync_s::soft_chain, on, "fxrx_sync_set_soft_chain");
-}
-// (in force while soft payload decoding is on; turning it on without is refused, as fxrx_create would)
-int fxrx_sync_set_soft_rs(flexframesync q, int on)
-{
-    if (q && on && !q->soft) {
-        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs: needs soft payload decoding (setting unchanged)\n");
-        return -1;
-    }
-    return sync_set_option(q, &fxrx_sync_s::soft_rs, on, "fxrx_sync_set_soft_rs");
-}
-// (in force while soft payload decoding and soft_rs are on; a value other than "no bound" without them, or one fxrx_create would not take, is refused)
+void fxrx_sync_set_equalizer(flexframesync q, int on) { (void)sync_set(q, &fxrx_sync_s::equalizer, on != 0, "fxrx_sync_set_equalizer"); }
+void fxrx_sync_set_soft(flexframesync q, int on) { (void)sync_set(q, &fxrx_sync_s::soft, on != 0, "fxrx_sync_set_soft"); }
+int fxrx_sync_set_soft_block(flexframesync q, int on) { return sync_set(q, &fxrx_sync_s::soft_block, on != 0, "fxrx_sync_set_soft_block"); }
+int fxrx_sync_set_soft_chain(flexframesync q, int on) { return sync_set(q, &fxrx_sync_s::soft_chain, on != 0, "fxrx_sync_set_soft_chain", &fxrx_sync_s::soft_block_on, "soft payload decoding and soft_block"); }
+int fxrx_sync_set_soft_rs(flexframesync q, int on) { return sync_set(q, &fxrx_sync_s::soft_rs, on != 0, "fxrx_sync_set_soft_rs", &fxrx_sync_s::soft_on, "soft payload decoding"); }
 int fxrx_sync_set_soft_rs_fmax(flexframesync q, int fmax_plus_1)
 {
-    if (q && fmax_plus_1 && !(q->soft && q->soft_rs)) {
-        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs_fmax: needs soft payload decoding and soft_rs (setting unchanged)\n");
-        return -1;
-    }
-    if (q && fmax_plus_1 && (fmax_plus_1 < 0 || fmax_plus_1 > 33 || (fmax_plus_1 & 1) == 0)) {
-        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs_fmax: 0, or an even bound 0 .. 32 plus one (setting unchanged)\n");
-        return -1;
-    }
-    return sync_set_value(q, &fxrx_sync_s::soft_rs_fmax, fmax_plus_1, "fxrx_sync_set_soft_rs_fmax");
+    const bool takes = fmax_plus_1 == 0 || (fmax_plus_1 > 0 && fmax_plus_1 <= 33 && (fmax_plus_1 & 1));
+    return sync_set(q, &fxrx_sync_s::soft_rs_fmax, fmax_plus_1, "fxrx_sync_set_soft_rs_fmax", &fxrx_sync_s::soft_rs_on, "soft payload decoding and soft_rs",
+                    takes ? nullptr : "0, or an even bound 0 .. 32 plus one");
 }
-int fxrx_sync_set_soft_rs_chain(flexframesync q, int on)
-{
-    if (q && on && !(q->soft && q->soft_rs)) {
-        std::fprintf(stderr, "libfxrx: fxrx_sync_set_soft_rs_chain: needs soft payload decoding and soft_rs (setting unchanged)\n");
-        return -1;
-    }
-    return sync_set_option(q, &fxrx_sync_s::soft_rs_chain, on, "fxrx_sync_set_soft_rs_chain");
-}
+int fxrx_sync_set_soft_rs_chain(flexframesync q, int on) { return sync_set(q, &fxrx_sync_s::soft_rs_chain, on != 0, "fxrx_sync_set_soft_rs_chain", &fxrx_sync_s::soft_rs_on, "soft payload decoding and soft_rs"); }
 // [RECALLED liquid 1.3.x] flexframesync_decode_header_soft / flexframesync_decode_payload_soft (include/liquid/liquid.h)
-int flexframesync_decode_header_soft(flexframesync q, int soft) { return sync_set_option(q, &fxrx_sync_s::soft_header, soft, "flexframesync_decode_header_soft"); }
-int flexframesync_decode_payload_soft(flexframesync q, int soft) { return sync_set_option(q, &fxrx_sync_s::soft, soft, "flexframesync_decode_payload_soft"); }
+int flexframesync_decode_header_soft(flexframesync q, int soft) { return sync_set(q, &fxrx_sync_s::soft_header, soft != 0, "flexframesync_decode_header_soft"); }
+int flexframesync_decode_payload_soft(flexframesync q, int soft) { return sync_set(q, &fxrx_sync_s::soft, soft != 0, "flexframesync_decode_payload_soft"); }
 
 }  // extern "C"
 
@@ -302,80 +224,49 @@ void msequence_destroy(msequence ms) { delete ms; }
 }
 
 // ------------------------------------------------------------------------------------------ qdetector_cccf
-// The reference hands over one sample per call (/root/reference/lib/frame_detector_cc_impl.cc:76-82).  Built like fxrx_sync_s: a
-// call is one store into the page-locked buffer being filled plus a counter; a full buffer is submitted as the next block of one
-// continuing stream on a detector context that returns the aligned windows (want_framesyms: fx_detwin_kernel), and the next
-// buffer of the ring fills meanwhile.  A block in flight is collected when its slot is needed, when a poll finds it done, or --
-// so that delivery never depends on how fast the GPU happens to be -- once an eighth of a block length (plus depth - 1 block lengths)
-// has been handed in since it was submitted: a detection leaves at most that long after its block filled, whatever the timing.
-// That bound is kept by a forced wait: the call that reaches the age limit blocks in fxrx_collect, on the caller's thread, until the
-// GPU has finished the block (a block takes far less than an eighth of its length to fill only above some hundred Msamples/s).
-// Detections wait in `pending` with their windows (copies: the context's are valid until its next collect) and leave one per
-// call.  There is no host-side history of the samples.
-struct fxrx_qdet_s {
+// The reference hands over one sample per call (/root/reference/lib/frame_detector_cc_impl.cc:76-82).  The same feeder
+// (fx_blockfeed.h) under a call that is one store into the buffer being filled plus a counter, on a detector context that returns the
+// aligned windows (want_framesyms: fx_detwin_kernel).  What differs from fxrx_sync_s: a block in flight is collected when its slot is
+// needed, when a poll finds it done, or -- so that delivery never depends on how fast the GPU happens to be -- once an eighth of a
+// block length (plus depth - 1 block lengths) has been handed in since it was submitted (`submitted_at`): a detection leaves at most
+// that long after its block filled, whatever the timing.  That bound is kept by a forced wait: the call that reaches the age limit
+// blocks in fxrx_collect, on the caller's thread, until the GPU has finished the block (a block takes far less than an eighth of its
+// length to fill only above some hundred Msamples/s).  Detections wait in `pending` with their windows (copies: the context's are
+// valid until its next collect) and leave one per call.  There is no host-side history of the samples.
+struct fxrx_qdet_s : BlockFeed<fxrx_qdet_s> {
+    static constexpr const char *entry = "qdetector_cccf_execute";
     struct Det { float tau, gamma, dphi, phi; fx_complex win[FX_NFFT]; };
-    fxrx_ctx *ctx = nullptr; float threshold = 0.5f;
-    unsigned block = kQdetBlockDefault, depth = kQdetDepthDefault;
-    std::vector<fx_complex *> bufs; unsigned cur = 0; size_t fill = 0;      // ring of depth + 1 pinned buffers of `block` samples
+    float threshold = 0.5f;
     std::deque<uint64_t> submitted_at;  // per block in flight: `count` when it was submitted
     uint64_t count = 0;                 // samples handed in so far
     std::deque<Det> pending;
     fx_complex window[FX_NFFT];         // what the last non-NULL call returned (valid until the next call)
     float tau = 0, gamma = 0, dphi = 0, phi = 0;
-    unsigned errors = 0, since_poll = 0;
+    unsigned since_poll = 0;
 
-    ~fxrx_qdet_s() { for (auto p : bufs) fxrx_pinned_free(p); }
-    fxrx_ctx *new_ctx()
+    fxrx_qdet_s() : BlockFeed(kQdetBlockDefault, kQdetDepthDefault) {}
+    bool make_ctx()                     // the detector starts over; a failed re-creation keeps the old context and what it holds
     {
         fxrx_config cfg{}; cfg.device = 0; cfg.mode = FXRX_MODE_DETECTOR; cfg.n_streams = 1; cfg.threshold = threshold; cfg.want_framesyms = 1;
-        if (const char *d = std::getenv("FXRX_DEVICE")) cfg.device = std::atoi(d);
-        fxrx_ctx *nc = fxrx_create(&cfg);
-        if (nc && fxrx_set_depth(nc, depth) != 0) { fxrx_destroy(nc); nc = nullptr; }
-        return nc;
-    }
-    bool make_ctx()                     // a failed re-creation keeps the old context
-    {
-        fxrx_ctx *nc = new_ctx();
-        if (!nc) { errors++; std::fprintf(stderr, "libfxrx: qdetector_cccf: %s\n", fxrx_last_error()); return false; }
-        if (ctx) fxrx_destroy(ctx);
-        ctx = nc; submitted_at.clear(); pending.clear(); fill = 0;
+        if (!replace_ctx(cfg)) { errors++; std::fprintf(stderr, "libfxrx: qdetector_cccf: %s\n", fxrx_last_error()); return false; }
+        submitted_at.clear(); pending.clear(); fill = 0;
         return true;
     }
-    void report(const char *what, int rc)
+    void submitted() { submitted_at.push_back(count); }
+    void dropped() { submitted_at.clear(); }
+    // queue the detections of the block just collected
+    void take(int nr)
     {
-        if (errors++ == 0 || (errors & (errors - 1)) == 0)
-            std::fprintf(stderr, "libfxrx: %s failed (%d): %s [%u failures so far]\n", what, rc, fxrx_last_error(), errors);
-    }
-    // the oldest block in flight: wait for it, queue its detections
-    void collect_one()
-    {
-        const int nr = fxrx_collect(ctx);
-        if (nr < 0) { report("qdetector_cccf_execute: block", nr); submitted_at.clear(); return; }   // (every block in flight went with it; the detector restarts fresh)
         if (!submitted_at.empty()) submitted_at.pop_front();
         for (int i = 0; i < nr; i++) {
             fxrx_frame f;
             // (a detection without its window cannot be handed out: it is dropped, counted and reported, never passed over in silence)
-            if (fxrx_result(ctx, (unsigned)i, &f) != 0 || !f.framesyms || f.num_framesyms != FX_NFFT) { report("qdetector_cccf_execute: a detection's window", FXRX_ERR_STATE); continue; }
+            if (fxrx_result(ctx, (unsigned)i, &f) != 0 || !f.framesyms || f.num_framesyms != FX_NFFT) { report("a detection's window", FXRX_ERR_STATE); continue; }
             pending.emplace_back();
             Det &d = pending.back();
             d.tau = f.tau; d.gamma = f.gamma; d.dphi = f.dphi; d.phi = f.phi;
             std::memcpy(d.win, f.framesyms, sizeof d.win);
         }
-    }
-    void drain() { while (fxrx_inflight(ctx)) collect_one(); }
-    // hand the buffer being filled to the GPU as the stream's next block
-    void submit_current()
-    {
-        if (!fill) return;
-        if (fxrx_inflight(ctx) >= depth) collect_one();
-        const void *p = bufs[cur]; uint64_t n = fill;
-        const int r = fxrx_submit(ctx, &p, &n, 0);
-        if (r < 0) {                    // these samples are lost to the detector, never fed again: it restarts freshly reset behind the gap
-            report("qdetector_cccf_execute: submit", r);
-            drain();
-            fxrx_reset(ctx);
-        } else submitted_at.push_back(count);
-        cur = (cur + 1) % (unsigned)bufs.size(); fill = 0;
     }
     void poll()
     {
@@ -394,12 +285,11 @@ qdetector_cccf qdetector_cccf_create_linear(fx_complex *seq, unsigned int len, i
     std::unique_ptr<fxrx_qdet_s> q(new fxrx_qdet_s);
     if (const char *e = std::getenv("FXRX_QDET_BLOCK")) q->block = (unsigned)std::max(FX_NFFT, std::atoi(e));
     if (const char *e = std::getenv("FXRX_QDET_DEPTH")) q->depth = (unsigned)std::min(15, std::max(1, std::atoi(e)));
-    if (!q->make_ctx()) return nullptr;
-    if (!alloc_ring(q->bufs, q->depth + 1, q->block)) { fxrx_destroy(q->ctx); return nullptr; }
+    if (!q->make_ctx() || !q->set_ring(q->block)) return nullptr;
     return q.release();
 }
 // /root/reference/lib/frame_detector_cc_impl.cc:63
-void qdetector_cccf_destroy(qdetector_cccf q) { if (!q) return; fxrx_destroy(q->ctx); delete q; }
+void qdetector_cccf_destroy(qdetector_cccf q) { delete q; }
 // /root/reference/lib/frame_detector_cc_impl.cc:55.  The detector starts over (what is queued or in flight is dropped), as before.
 void qdetector_cccf_set_threshold(qdetector_cccf q, float t)
 {
@@ -411,18 +301,14 @@ void qdetector_cccf_set_threshold(qdetector_cccf q, float t)
 unsigned int fxrx_qdet_errors(qdetector_cccf q) { return q ? q->errors : 0; }
 unsigned int fxrx_qdet_pending(qdetector_cccf q) { return q ? (unsigned)q->pending.size() : 0; }
 fxrx_ctx *fxrx_qdet_context(qdetector_cccf q) { return q ? q->ctx : nullptr; }
-void fxrx_qdet_flush(qdetector_cccf q) { if (!q || !q->ctx) return; q->submit_current(); q->drain(); }
+void fxrx_qdet_flush(qdetector_cccf q) { if (q) q->flush(); }
 void fxrx_qdet_set_block(qdetector_cccf q, unsigned int samples)
 {
     if (!q || !q->ctx) return;
     const unsigned nb = samples < FX_NFFT ? (unsigned)FX_NFFT : samples;
     if (nb == q->block) return;
-    fxrx_qdet_flush(q);                     // what is queued runs at the old size (buffers move)
-    std::vector<fx_complex *> ring;
-    if (!alloc_ring(ring, q->depth + 1, nb)) { q->errors++; std::fprintf(stderr, "libfxrx: fxrx_qdet_set_block: %s (block length unchanged)\n", fxrx_last_error()); return; }
-    q->bufs.swap(ring);
-    for (auto p : ring) fxrx_pinned_free(p);
-    q->block = nb; q->cur = 0; q->fill = 0;
+    q->flush();                              // what is queued runs at the old size (buffers move); pending detections are copies already
+    (void)q->resize(nb, "fxrx_qdet_set_block");
 }
 // /root/reference/lib/frame_detector_cc_impl.cc:77
 void *qdetector_cccf_execute(qdetector_cccf q, fx_complex x)

@@ -176,3 +176,79 @@ def test_set_block_and_back_with_frames_pending(fx):
     assert L.fxrx_sync_errors(q) == 0
     L.flexframesync_destroy(q)
     assert [g[3] for g in got] == [pl for _, pl in inj] and all(g[1] and g[2] for g in got)
+
+
+def test_qdetector_set_block_and_back_with_detections_pending(fx, det_stream):
+    """the detector's block length changed with detections pending, per sample from here: 4096 -> 1024 at sample 20 000, back at 30 000"""
+    L = fx.lib()
+    x = np.ascontiguousarray(det_stream[:40_000])
+    ctx = fx.RxContext(1, mode=fx.MODE_DETECTOR, threshold=THR, want_framesyms=True)
+    want = ctx.process([x])
+    ctx.close()
+    ms = L.msequence_create(7, 0x0089, 1)
+    pn = np.array([(1 if L.msequence_advance(ms) else -1) + 1j * (1 if L.msequence_advance(ms) else -1) for _ in range(64)]) * np.sqrt(0.5)
+    L.msequence_destroy(ms)
+    q = L.qdetector_cccf_create_linear(pn.astype(np.complex64).ctypes.data, 64, 7, 2, 7, C.c_float(0.3))
+    assert q
+    L.qdetector_cccf_set_threshold(q, THR)
+    L.fxrx_qdet_set_block(q, 4096)
+    got = []
+
+    def call(re, im):
+        p = L.qdetector_cccf_execute(q, fx._ffi.FxComplex(re, im))
+        if p:
+            e = tuple(np.float32(getattr(L, "qdetector_cccf_get_" + n)(q)) for n in ("tau", "gamma", "dphi", "phi"))
+            got.append((e, np.frombuffer(C.cast(p, C.POINTER(C.c_float * 1024)).contents, np.complex64).copy()))
+    xs = x.view(np.float32).reshape(-1, 2).tolist()
+    for i, (re, im) in enumerate(xs):
+        if i == 20_000:
+            # A detection leaves with the call after its block was collected, and a block is collected at most block / 8 + 1024
+            # samples after it filled: the detections of the blocks up to 16 384 are gone by now, none would be pending.  The flush
+            # (as in test_set_block_and_back_with_frames_pending) runs the 3616 samples queued, which hold two preambles, so that the
+            # ring is changed with detections pending.  A ring changed with samples queued (and whatever is in flight then), left to
+            # fxrx_qdet_set_block's own flush, is the change at 30 000 (784 samples queued, no flush from here).
+            L.fxrx_qdet_flush(q)
+            assert L.fxrx_qdet_pending(q) > 0
+            L.fxrx_qdet_set_block(q, 1024)                         # with detections pending: they are kept, the stream continues
+            assert L.fxrx_qdet_pending(q) > 0
+        if i == 30_000:
+            L.fxrx_qdet_set_block(q, 4096)                         # ... and back
+        call(re, im)
+    L.fxrx_qdet_flush(q)
+    while L.fxrx_qdet_pending(q):
+        call(0.0, 0.0)
+    assert L.fxrx_qdet_errors(q) == 0
+    L.qdetector_cccf_destroy(q)
+    assert len(want) >= 15 and len(got) == len(want)
+    for (e, w), b in zip(got, want):
+        assert e == (np.float32(b["tau"]), np.float32(b["gamma"]), np.float32(b["dphi"]), np.float32(b["phi"]))
+        assert np.array_equal(w, _win(x, b["start"]))
+
+
+def test_sync_setters_refuse_without_their_prerequisites(fx):
+    """no samples fed: a refusal returns -1 and makes no new context; with the prerequisites on, in order, each setter returns 0"""
+    L = fx.lib()
+    q, keep = _sync_handle(fx, [])
+    ctx = L.fxrx_sync_context(q)
+    assert ctx
+    needy = [(L.fxrx_sync_set_soft_chain, 1), (L.fxrx_sync_set_soft_rs, 1), (L.fxrx_sync_set_soft_rs_fmax, 5), (L.fxrx_sync_set_soft_rs_chain, 1)]
+    for f, v in needy:
+        ctx = L.fxrx_sync_context(q)
+        assert f(q, v) == -1 and L.fxrx_sync_context(q) == ctx
+        assert f(q, 0) == 0                                        # turning an option off is always taken, whatever else is off
+    ctx = L.fxrx_sync_context(q)
+    L.fxrx_sync_set_soft(q, 1)
+    assert L.fxrx_sync_context(q) != ctx
+    ctx = L.fxrx_sync_context(q)
+    assert L.fxrx_sync_set_soft_rs_fmax(q, 5) == -1 and L.fxrx_sync_set_soft_rs_chain(q, 1) == -1       # soft_rs is still off
+    assert L.fxrx_sync_set_soft_chain(q, 1) == -1 and L.fxrx_sync_context(q) == ctx                     # soft_block is still off
+    assert L.fxrx_sync_set_soft_rs(q, 1) == 0 and L.fxrx_sync_set_soft_rs_fmax(q, 5) == 0 and L.fxrx_sync_set_soft_rs_chain(q, 1) == 0
+    assert L.fxrx_sync_set_soft_block(q, 1) == 0 and L.fxrx_sync_set_soft_chain(q, 1) == 0
+    ctx = L.fxrx_sync_context(q)
+    for v in (4, 35, -1):
+        assert L.fxrx_sync_set_soft_rs_fmax(q, v) == -1 and L.fxrx_sync_context(q) == ctx
+    for f, _ in reversed(needy):
+        assert f(q, 0) == 0
+    assert L.fxrx_sync_set_soft_block(q, 0) == 0
+    assert L.fxrx_sync_errors(q) == 0
+    L.flexframesync_destroy(q)
