@@ -193,7 +193,8 @@ static int sync_set(flexframesync q, int fxrx_sync_s::*field, int value, const c
     if (q && bad_value) { std::fprintf(stderr, "libfxrx: %s: %s (setting unchanged)\n", what, bad_value); return -1; }
     return sync_set_value(q, field, value, what);
 }
-void fxrx_sync_set_threshold(flexframesync q, float t) { (void)sync_set_value(q, &fxrx_sync_s::threshold, t, "fxrx_sync_set_threshold"); }
+// (a NaN is no threshold -- fxrx_create refuses it --: the value stays, nothing is flushed, re-created or counted)
+void fxrx_sync_set_threshold(flexframesync q, float t) { if (t != t) return; (void)sync_set_value(q, &fxrx_sync_s::threshold, t, "fxrx_sync_set_threshold"); }
 void fxrx_sync_set_equalizer(flexframesync q, int on) { (void)sync_set(q, &fxrx_sync_s::equalizer, on != 0, "fxrx_sync_set_equalizer"); }
 void fxrx_sync_set_soft(flexframesync q, int on) { (void)sync_set(q, &fxrx_sync_s::soft, on != 0, "fxrx_sync_set_soft"); }
 int fxrx_sync_set_soft_block(flexframesync q, int on) { return sync_set(q, &fxrx_sync_s::soft_block, on != 0, "fxrx_sync_set_soft_block"); }
@@ -293,7 +294,7 @@ void qdetector_cccf_destroy(qdetector_cccf q) { delete q; }
 // /root/reference/lib/frame_detector_cc_impl.cc:55.  The detector starts over (what is queued or in flight is dropped), as before.
 void qdetector_cccf_set_threshold(qdetector_cccf q, float t)
 {
-    if (!q) return;
+    if (!q || t != t) return;                // (a NaN is no threshold: the value stays, nothing is dropped or counted)
     const float old = q->threshold;
     q->threshold = t;
     if (!q->make_ctx()) q->threshold = old;

@@ -453,6 +453,7 @@ void fxrx_destroy(fxrx_ctx *c)
 fxrx_ctx *fxrx_create(const fxrx_config *cfg)
 {
     if (!cfg || cfg->n_streams == 0) { set_err("fxrx_create: bad config"); return nullptr; }
+    if (cfg->threshold != cfg->threshold) { set_err("fxrx_create: threshold is NaN (FXRX_ERR_ARG)"); return nullptr; }
     if (cfg->mode == FXRX_MODE_DETECTOR && cfg->soft_header) { set_err("fxrx_create: soft_header needs flex_rx mode (FXRX_ERR_ARG)"); return nullptr; }
     if (cfg->soft_block && (cfg->mode == FXRX_MODE_DETECTOR || !cfg->soft_decision)) {
         set_err("fxrx_create: soft_block needs soft_decision and flex_rx mode (FXRX_ERR_ARG)"); return nullptr;

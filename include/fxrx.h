@@ -84,7 +84,7 @@ void fxrx_sync_set_block(flexframesync q, unsigned int samples);     /* (if the 
  * call, buffers valid until the next call on the handle.  0: off.  A sensible floor is 8192.  Environment: FXRX_SYNC_STREAMING=<floor>,
  * read by flexframesync_create -- how an unmodified caller turns it on. */
 void fxrx_sync_set_streaming(flexframesync q, unsigned int floor_samples);
-void fxrx_sync_set_threshold(flexframesync q, float threshold);
+void fxrx_sync_set_threshold(flexframesync q, float threshold);   /* values as fxrx_config.threshold; NaN: ignored */
 void fxrx_sync_set_equalizer(flexframesync q, int on);   /* re-creates the context like fxrx_sync_set_threshold */
 void fxrx_sync_set_soft(flexframesync q, int on);        /* likewise: soft-decision payload decoding */
 /* soft-input block decoders (fxrx_config.soft_block), in force while soft payload decoding is on.  Re-creates the context; returns 0,
@@ -125,7 +125,7 @@ typedef struct fxrx_qdet_s *qdetector_cccf;
 qdetector_cccf qdetector_cccf_create_linear(fx_complex *sequence, unsigned int sequence_len, int ftype,
                                             unsigned int k, unsigned int m, float beta);
 void   qdetector_cccf_destroy(qdetector_cccf q);
-void   qdetector_cccf_set_threshold(qdetector_cccf q, float threshold);
+void   qdetector_cccf_set_threshold(qdetector_cccf q, float threshold);   /* values as fxrx_config.threshold; NaN: ignored */
 /* Per-sample entry kept for link compatibility.  A call stores the sample in a page-locked buffer; a full buffer (65 536 samples;
  * FXRX_QDET_BLOCK / fxrx_qdet_set_block, at least 512) is searched on the GPU as the next block of one continuing stream while the
  * next buffer fills, FXRX_QDET_DEPTH (default 1) blocks in flight.  Every detection is reported exactly once, one per call, later
@@ -175,8 +175,16 @@ typedef struct {
     int          device;         /* HIP device ordinal */
     int          mode;           /* FXRX_MODE_* */
     unsigned int n_streams;
-    float        threshold;      /* 0 -> default (0.5 flex_rx like liquid's flexframesync, 0.45 detector like
-                                    /root/reference/lib/frame_detector_cc_impl.cc:55) */
+    float        threshold;      /* <= 0 -> default (0.5 flex_rx like liquid's flexframesync, 0.45 detector like
+                                    /root/reference/lib/frame_detector_cc_impl.cc:55).  Any other finite value, and +Inf, is taken as
+                                    given: a hop detects when rxy > threshold.  rxy is the peak over the root of the window's energy
+                                    taken as spread evenly over its 512 samples: near 1 at most in steady traffic, up to sqrt(512 / 156)
+                                    = 1.81 for a preamble alone in a silent window (1.4 in a fresh detector's first, half-empty
+                                    window), never more.  A threshold above that (2, +Inf) yields no results and no error; 1.5 is
+                                    still reached by a strong frame behind much weaker traffic.  NaN: fxrx_create fails with
+                                    FXRX_ERR_ARG (every comparison with it is false: it would silently detect nothing);
+                                    fxrx_sync_set_threshold and qdetector_cccf_set_threshold then keep the previous value, re-create
+                                    nothing and count no error */
     unsigned int segment_len;    /* speculation granularity in samples (0 -> auto) */
     int          want_framesyms; /* copy payload symbols back to the host with each result.  Detector mode: every detection carries its 512 aligned
                                     samples instead (fxrx_frame.framesyms, num_framesyms = 512): x[start, start + 512) of its stream, bit for bit,
@@ -301,8 +309,10 @@ int fxrx_result(const fxrx_ctx *c, unsigned int i, fxrx_frame *out);
  * results into pinned host memory -- and returns without waiting for any of it; what a stream carries from block to block
  * (resume state, unconsumed tail) stays on the device, so a block that continues the streams of the previous one simply
  * orders its first walkers behind that block's chain kernel.  fxrx_collect waits for the OLDEST submitted block and exposes
- * its results through fxrx_result / fxrx_last_timing.  With depth d (fxrx_set_depth, 1..16, default 1) up to d blocks may
- * be in flight.  After fxrx_reset the next block starts from a freshly reset synchroniser.  Blocks of one stream must be
+ * its results through fxrx_result / fxrx_last_timing.  With depth d (fxrx_set_depth, 1..32, default 1; 0 or more: FXRX_ERR_ARG; with blocks in flight: FXRX_ERR_STATE, the depth stays either way) up to d blocks may
+ * be in flight; one more fxrx_submit fails with FXRX_ERR_STATE ("pipeline full") and changes nothing.  After fxrx_reset the next
+ * block starts from a freshly reset synchroniser (positions count from 0 again, no carried tail, nothing in front of its first sample);
+ * blocks in flight at that moment deliver what they would have delivered without it.  Blocks of one stream must be
  * submitted in order; input buffers, host or device, must stay valid until their block has been collected; results stay
  * valid until the next fxrx_collect / fxrx_process on the context (a submit in between does not touch them).  Returns 0
  * (submit) / result count (collect) or FXRX_ERR_*. */

@@ -1,7 +1,7 @@
 """The captures and block-cut layouts of tests/test_ref_cuts.py and tests/test_gpu_cuts.py, as data.
 
 A continuing stream reaches the library in blocks (fxrx_submit / fxrx_collect); DESIGN.md sections 2.1-2.2 promise the frames of
-a single pass for any cut.  What bridges a cut is the state ring (19 entries per stream), three rotating carry buffers per
+a single pass for any cut.  What bridges a cut is the state ring (35 entries per stream), three rotating carry buffers per
 stream (block b reads carry[b % 3] and writes carry[(b + 1) % 3]) and two-piece addressing (samples below index 0 of a block
 come from the carried tail).  The layouts below put a cut at every place where one of those has to hand something over, named
 by the geometry tests/ref_stream.py and tests/ref_sync.py state -- their constants, not copies of them:
@@ -151,9 +151,10 @@ def pieces(total, cuts, n_blocks=None):
     return out + [0] * ((n_blocks or len(out)) - len(out))
 
 
-def many_blocks(total, n=45):
-    """n blocks of unequal small sizes (weights 1..11 by a quadratic residue pattern): the state ring of 19 entries wraps twice
-    and every b % 3 meets a frame boundary"""
+def many_blocks(total, n=72):
+    """n blocks of unequal small sizes (weights 1..11 by a quadratic residue pattern): the state ring wraps twice -- it has
+    kStateRing = kMaxDepth + 3 = 35 entries per stream (fx_host.cpp; tests/test_gpu_controls.py reads both there), block b uses
+    entry b % 35, so blocks 35 and 70 start a new round -- and every b % 3 meets a frame boundary"""
     w = np.array([1 + (k * k * 37) % 11 for k in range(n)], np.float64)
     cuts = [int(v) for v in np.floor(np.cumsum(w)[:-1] / w.sum() * total)]
     assert len(set(cuts)) == n - 1 and len(set(np.diff([0] + cuts + [total]))) > 5

@@ -187,9 +187,12 @@ def test_cut_sweep(fx, world, seg, depth, on_device):
 
 @pytest.mark.parametrize("depth", [1, 3, 12])
 def test_45_blocks(fx, world, depth):
-    """every capture in 45 unequal small blocks: the state ring of 19 entries wraps twice"""
-    _sweep(fx, world, CC.CAPTURES, lambda c: [("45 blocks", CC.many_blocks(c["total"]))], depth, segment_len=4096)
-    _sweep(fx, world, CC.CAPTURES, lambda c: [("45 blocks", CC.many_blocks(c["total"]))], depth, segment_len=0)
+    """every capture in 72 unequal small blocks (45 when the test got its name, for a ring of 19): the state ring has kStateRing =
+    kMaxDepth + 3 = 32 + 3 = 35 entries per stream (fx_host.cpp), block b uses entry b % 35, so 72 blocks wrap it twice"""
+    lay = lambda c: [("72 blocks", CC.many_blocks(c["total"]))]
+    assert all(len(ct) + 1 == 72 for c in CC.CAPTURES for _, ct in lay(c))
+    _sweep(fx, world, CC.CAPTURES, lay, depth, segment_len=4096)
+    _sweep(fx, world, CC.CAPTURES, lay, depth, segment_len=0)
 
 
 # ---------------------------------------------------------------------------------------------------- a noisy neighbour

@@ -64,7 +64,7 @@ def test_captures_are_certain_and_in_their_roles(oracle, cap):
     assert not S.detect(x, cap["threshold"])[1]
     names = [n for n, _ in CC.layouts(cap)]
     assert {CC.ZERO_BLOCK, CC.THREE_CUTS, "frame 0: a-512", "frame 0: a+156", "frame 0: header symbol 230 +1", "frame 0: resume"} <= set(names)
-    assert len(CC.many_blocks(cap["total"])) == 44
+    assert len(CC.many_blocks(cap["total"])) == 71
 
 
 def test_the_qpsk_capture_holds_what_it_promises(oracle):
@@ -85,7 +85,7 @@ def test_oracle_piecewise_equals_oracle_whole_and_the_reference(oracle, cap):
     worst = {}
     bad = S.compare(ref, [S.view_oracle(f) for f in whole], x, worst=worst)
     assert not bad, bad
-    for name, cuts in CC.layouts(cap) + [("45 blocks", CC.many_blocks(cap["total"]))]:
+    for name, cuts in CC.layouts(cap) + [("72 blocks", CC.many_blocks(cap["total"]))]:
         d = _oracle_differences(whole, _piecewise(oracle, x, cuts, cap["threshold"]))
         assert not d, (cap["name"], name, cuts, d[:4])
 
